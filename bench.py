@@ -86,7 +86,43 @@ def parse():
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launch path only (no GPU work, no metric): spawn / rendezvous / all-reduce / invariant checks of the N-rank job with "
                          "CPU tensors; what tests/test_host_logic.py runs with --gpus 2 --backend gloo in a container without a GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0): the loss values, G's and D's "
+                         "parameters and BatchNorm buffers after the update, the guide pyramids the step trained on; arrays above "
+                         f"{1 << 18} elements as a fixed, seeded sample of them (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 18               # elements written of a larger array
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: {name: tensor or float} -> outdir/<name>.npy, float32 (float64 for integer buffers and Python floats).  An array
+    of more than DUMP_SAMPLE elements is written as a 1-D sample of its logical (NCHW / [O,I,kh,kw]) flattening, at sorted indices drawn
+    from a generator seeded with crc32(name): the same elements for the same name and size, so that two builds' dumps compare element
+    for element."""
+    import zlib
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach() if torch.is_tensor(t) else torch.tensor(t, dtype=torch.float64)
+        dt = torch.float32 if t.dtype == torch.float32 else torch.float64
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.contiguous().view(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.to(dt).cpu().contiguous().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return len(out), nbytes
 
 
 
@@ -232,11 +268,19 @@ def main():
     # step, the last included, launches one; with --warmup 0 (the profiled runs: rocprofv3 then sees exactly the timed launches) the first
     # step launches its own pair first and the last one launches none
     for i in range(args.steps):
-        one_step(last=(args.warmup == 0 and i == args.steps - 1))
+        hr, lr = one_step(last=(args.warmup == 0 and i == args.steps - 1))
     elapsed_rank = time.perf_counter() - t0               # this rank's own steps (before the closing barrier): per_rank_images_per_s
     sync()
     elapsed = time.perf_counter() - t0
     log(f"timed region done: {args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:                   # (before the repeats below move the weights on)
+        outs = {f"loss.{k}": v for k, v in step.metrics(check_finite=False).items()}
+        outs.update({f"G.{k}": v for k, v in G.state_dict().items()})
+        outs.update({f"D.{k}": v for k, v in D.state_dict().items()})
+        outs.update({f"guide.hr_p{d + 2}": t for d, t in enumerate(hr)})
+        outs.update({f"guide.lr_p{d + 2}": t for d, t in enumerate(lr)})
+        n_files, n_bytes = dump_outputs(args.dump_outputs, outs)
+        log(f"--dump-outputs: {n_files} arrays, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}")
     host_timed = {k: list(v[-args.steps:]) for k, v in host_ms.items()}      # (the profiled repeat below appends its own)
     profiled_ms_per_step = None
     if not args.profile_timed:

@@ -55,6 +55,13 @@ def spawn_ranks(args):
     raise SystemExit(rc)
 
 
+def cpu_barrier(dist, torch):
+    """dist.barrier() for a process group that only ever sees CPU tensors: torch's barrier() first asks which accelerator the machine has
+    (torch._C._get_accelerator), which starts the GPU runtime -- every rank of a rehearsal would open the GPU.  A one-element all-reduce
+    waits for all ranks the same way."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def allreduce_alone(dist, torch, bufs, dev, world, reps=5):
     """Each gradient exchange of a step with nothing beside it: {tag: {bytes, ms (max over ranks), bus_gb_per_s}} for the flat buffers
     in `bufs`.  Zeroes the buffers afterwards.  Used by the real run (device buffers) and by --rehearse-launch
@@ -66,7 +73,9 @@ def allreduce_alone(dist, torch, bufs, dev, world, reps=5):
             dist.all_reduce(buf)
         if cuda:
             torch.cuda.synchronize()
-        dist.barrier()
+            dist.barrier()
+        else:
+            cpu_barrier(dist, torch)
         t0 = time.perf_counter()
         for _ in range(reps):
             dist.all_reduce(buf)
@@ -127,7 +136,7 @@ def rehearse_launch(args, world, rank):
         overlap = bool(args.overlap_comm) if args.overlap_comm is not None else False       # (the engine's default: blocking)
         comm = {"backend": dist.get_backend(), "world_size_reported": dist.get_world_size(), "rank0_device": "cpu (rehearsal)",
                 "overlap_comm": overlap, "allreduce_alone": allreduce_alone(dist, torch, bufs, None, world, reps=2)}
-        dist.barrier()
+        cpu_barrier(dist, torch)
         t0 = time.perf_counter()
         for _ in range(args.steps):
             for tag in ("D", "G"):
@@ -141,12 +150,12 @@ def rehearse_launch(args, world, rank):
             for p_, tag in zip(params, ("G", "D")):
                 p_.sub_(1e-3 / world * bufs[tag][:p_.numel()])     # "SGD" on the averaged gradient: identical on every rank
         mine = time.perf_counter() - t0
-        dist.barrier()
+        cpu_barrier(dist, torch)
         el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         rates = per_rank_rates(dist, torch, B * args.steps, mine, None, world)
         same = identical_across_ranks(dist, torch, params)
-        dist.barrier()
+        cpu_barrier(dist, torch)
         dist.destroy_process_group()
         elapsed = float(el.item())
     else:
