@@ -76,6 +76,7 @@ SIGNATURES = {
     "afi_generator_fwd_ws_floats": (_ll, [_i] * 6),
     "afi_generator_bwd_ws_floats": (_ll, [_i] * 6),
     "afi_generator_fwd": (_i, [_vp, _GP, View, _i, _i, _i, View, _vp, _ll, _vp]),
+    "afi_generator_fwd_out16": (_i, [_vp, _GP, View, _i, _i, _i, View, _i, _vp, _ll, _vp]),
     "afi_generator_bwd": (_i, [_vp, _GP, _GP, View, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "afi_discriminator_fwd_ws_floats": (_ll, [C.POINTER(C.c_int), _i, _i, _i]),
     "afi_discriminator_fwd_ws_floats_ex": (_ll, [_vp, C.POINTER(C.c_int), _i, _i, _i, _i]),
@@ -87,13 +88,16 @@ SIGNATURES = {
     "afi_discriminator_fwd_paired": (_i, [_vp, _DP, View, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
     "afi_discriminator_bwd_paired": (_i, [_vp, _DP, _DP, View, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "afi_conv3x3_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _f, _f, _i, _vp]),
+    "afi_conv3x3_fwd_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _f, _f, _i, _vp]),
     "afi_conv3x3_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _f, _f, View, _vp]),
     "afi_conv3x3_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "afi_conv1x1_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _f, _f, View, _f, _i, _vp]),
     "afi_conv1x1_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _f, _f, _vp]),
+    "afi_conv1x1_dgrad_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _i, _f, _f, _vp]),
     "afi_conv1x1_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "afi_conv3x3_wino_ws_floats": (_ll, [_i] * 5),
     "afi_conv3x3_wino_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _vp, _ll, _vp]),
+    "afi_conv3x3_wino_fwd_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp, _ll, _vp]),
     "afi_conv3x3_wino_infer": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp, _ll, _vp]),
     "afi_conv3x3_wino_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, View, _vp, _ll, _vp]),
     "afi_conv3x3_wino_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp, _ll, _vp]),
@@ -137,6 +141,8 @@ SIGNATURES = {
     "afi_scale_inplace": (_i, [_vp, _ll, _f, _vp]),
     "afi_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "afi_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "afi_cast_to_f32_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp]),
+    "afi_cast_from_f32_nhwc": (_i, [View, _i, _i, _i, _i, _vp, _i, _vp]),
     "afi_profile_enable": (_i, [_i]),
     "afi_profile_num_kinds": (_i, []),
     "afi_profile_kind_name": (C.c_char_p, [_i]),

@@ -13,6 +13,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define AFI_ERR_BAD_ARG 1
 #define AFI_ERR_UNSUPPORTED 2
 #define AFI_ERR_LAUNCH 3
+
+// storage dtype of a tensor at the module boundary (include/afigan_hip.h: AFI_STORE_*); the kernels compute in fp32 whatever it is
+#define AFI_STORE_F32 0
+#define AFI_STORE_BF16 1
+#define AFI_STORE_F16 2
 #ifndef AFI_TRY
 #define AFI_TRY(expr) do { int _s = (expr); if (_s != AFI_OK) return _s; } while (0)
 #endif
@@ -100,7 +105,18 @@ struct AfiPixGemm {
     // pass can take them instead of transforming the input again (nets.hip: disc_v_shared decides on both sides)
     float* v_keep;
     int nt_local_sums;                                        // Winograd form under f16x3: the NT GEMM sums each k-step in a fresh fragment (AFI_OPT_F16_LOCAL_SUMS)
+    // storage dtype of O (AFI_STORE_*): the epilogue computes v in fp32 and rounds it once, to nearest even, at the store.  O.p then points at
+    // 2-byte elements and its strides count them.  A 2-byte O is write-only: beta (reads O_old), r2_post / O2 and the fused statistics (read
+    // or accumulate the stored fp32 value) are refused by every launcher (afi_o16_refused).
+    int o_dtype;
 };
+// what a launcher refuses for a 2-byte output (AFI_ERR_UNSUPPORTED), or an unknown storage dtype (AFI_ERR_BAD_ARG); AFI_OK otherwise
+static inline int afi_o16_refused(const AfiPixGemm& p) {
+    if (p.o_dtype == AFI_STORE_F32) return AFI_OK;
+    if (p.o_dtype != AFI_STORE_BF16 && p.o_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
+    if (p.beta != 0.f || p.r2_post || p.O2.p || p.stats || p.stats_mm || p.bstats) return AFI_ERR_UNSUPPORTED;
+    return AFI_OK;
+}
 #define AFI_WK6_STAGE_BYTES 6144
 // one weight (or weight view) to turn into such an image: the B addressing of AfiPixGemm (b_rc = 0: row n at B + n*b_sRow + tap*b_sTap + c;
 // b_rc = 1: row (kphase*Ck + c) at B + ...*b_sRow + tap*b_sTap + n), image bytes = ceil(Ncols/32) * ceil(Ck/32)*nKphase*ntaps * 6144

@@ -1,6 +1,7 @@
 // Fused epilogue of the pixel GEMMs (and of the Winograd output transform): shared device code, internal to the library.
 #pragma once
 #include "afi_common.h"
+#include "afi_half.h"
 
 __device__ __forceinline__ float afi_lrelu(float v) { return v > 0.f ? v : v * AFI_LRELU_SLOPE; }
 
@@ -59,7 +60,7 @@ __device__ __forceinline__ void afi_epilogue_store(const AfiPixGemm& p, int img,
         v *= p.post_scale;
         if (p.R2.p) v += p.r2s * *(const f32x4*)(p.R2.p + (long long)img * p.R2.sN + (long long)yo * p.R2.sH + (long long)xo * p.R2.sW + ch);
     }
-    *(f32x4*)dst = v;
+    afi_out_store(p, dst, v);
 }
 
 // The common case of the big Winograd convs (D forward: bias only; D / G data gradients: the LeakyReLU' mask over every channel;
@@ -83,7 +84,7 @@ __device__ __forceinline__ f32x4 afi_epilogue_store_simple(const AfiPixGemm& p, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= (z[j] > 0.f ? 1.f : AFI_LRELU_SLOPE);
     }
-    *(f32x4*)(p.O.p + pix) = v;
+    afi_out_store(p, p.O.p + pix, v);
     return v;                                               // (the stored value: what fused statistics accumulate)
 }
 

@@ -20,25 +20,8 @@ __device__ __forceinline__ float afi_wave_sum(float v) {
 }
 
 // ---------------------------------------------------------------- layout: NCHW <-> NHWC
-// in [N][C][P] -> out [N][P][C]   (P = H*W); 32x32 LDS tile, +1 pad
-__global__ __launch_bounds__(256) void afi_nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int P) {
-    __shared__ float tile[32][33];
-    const int n = blockIdx.z, c0 = blockIdx.y * 32, p0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const float* src = in + (long long)n * C * P;
-    float* dst = out + (long long)n * C * P;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int c = c0 + ty + 8 * i, pp = p0 + tx;
-        if (c < C && pp < P) tile[ty + 8 * i][tx] = src[(long long)c * P + pp];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int pp = p0 + ty + 8 * i, c = c0 + tx;
-        if (c < C && pp < P) dst[(long long)pp * C + c] = tile[tx][ty + 8 * i];
-    }
-}
+// in [N][C][P] -> out [N][P][C]: afi_launch_nchw_to_nhwc, the fp32 instance of the widening transpose (csrc/halfio.hip)
+// in [N][P][C] -> out [N][C][P]   (P = H*W); 32x32 LDS tile, +1 pad
 __global__ __launch_bounds__(256) void afi_nhwc_to_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int P) {
     __shared__ float tile[32][33];
     const int n = blockIdx.z, c0 = blockIdx.y * 32, p0 = blockIdx.x * 32;
@@ -58,11 +41,6 @@ __global__ __launch_bounds__(256) void afi_nhwc_to_nchw_kernel(const float* __re
     }
 }
 
-int afi_launch_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, hipStream_t st) {
-    if (N <= 0 || C <= 0 || P <= 0) return AFI_ERR_BAD_ARG;
-    hipLaunchKernelGGL(afi_nchw_to_nhwc_kernel, dim3(afi_cdiv(P, 32), afi_cdiv(C, 32), N), dim3(256), 0, st, in, out, C, P);
-    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
-}
 int afi_launch_nhwc_to_nchw(const float* in, float* out, int N, int C, int P, hipStream_t st) {
     if (N <= 0 || C <= 0 || P <= 0) return AFI_ERR_BAD_ARG;
     hipLaunchKernelGGL(afi_nhwc_to_nchw_kernel, dim3(afi_cdiv(P, 32), afi_cdiv(C, 32), N), dim3(256), 0, st, in, out, C, P);

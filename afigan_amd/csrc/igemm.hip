@@ -990,6 +990,7 @@ int afi_launch_wgrad6_group(const AfiWgradGemm* probs, int n, hipStream_t st);
 // grouped small-map launches, bracketed for the live roofline like every other GEMM launch
 int afi_launch_pix_gemm_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st) {
     double fl = 0.0; long long m = 0; int nn = 0;
+    for (int i = 0; i < n; ++i) AFI_TRY(afi_o16_refused(probs[i]));
     for (int i = 0; i < n; ++i) {
         const long long M = (long long)probs[i].N * probs[i].H * probs[i].W;
         fl += 2.0 * (double)M * probs[i].Ncols * probs[i].ntaps * probs[i].nKphase * probs[i].Ck;
@@ -1026,6 +1027,7 @@ int afi_launch_pix_gemm(const AfiPixGemm& p_in, int b_rc, hipStream_t st) {
     AfiPixGemm p = p_in;
     const long long M = (long long)p.N * p.H * p.W;
     if (M <= 0 || p.Ncols <= 0 || p.Ck <= 0) return AFI_ERR_BAD_ARG;
+    AFI_TRY(afi_o16_refused(p));
     if (p.a_bn.mean) return AFI_ERR_UNSUPPORTED;            // an operand read through a BatchNorm affine: the Winograd input transforms only
     if (p.b_sImg != 0 && ((long long)p.H * p.W) % 128 != 0) return AFI_ERR_BAD_ARG;   // per-image weights: tiles must not straddle images
     if (b_rc && (p.Ncols & 3)) return AFI_ERR_UNSUPPORTED;       // RC weight rows are read as float4 along n

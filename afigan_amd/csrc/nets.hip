@@ -37,6 +37,9 @@ int afi_launch_wk6_images(const AfiWk6ImgJob* jobs, int n, hipStream_t st, const
 int afi_launch_rdb_chain6(const AfiChain6& c, hipStream_t st);                                   // smallmap.hip: a dense block's chain of 32-channel convs in one launch
 int afi_launch_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, hipStream_t st);
 int afi_launch_nhwc_to_nchw(const float* in, float* out, int N, int C, int P, hipStream_t st);
+int afi_launch_cast_to_f32_nhwc(const void* in, int dt, int N, int C, int H, int W, long long sN, long long sC, long long sH, long long sW, float* out,
+                                hipStream_t st);      // halfio.hip
+int afi_launch_cast_from_f32_nhwc(const AfiView& in, int N, int H, int W, int C, void* out, int dt, hipStream_t st);
 int afi_launch_convT_pack(const float* W, float* Wp, int Cin, int Cout, hipStream_t st);
 int afi_launch_convT_unpack_grad(const float* dWp, float* dW, int Cin, int Cout, hipStream_t st);
 int afi_launch_rdb_wgrad_unpack(const float* dWp, float* const dw[4], int C, int G, float alpha, hipStream_t st);
@@ -463,6 +466,7 @@ static long long gen_wk6_bwd_floats(int C, int G, int R, long long P) {
 
 static int wino_run(afi_ctx* cx, const AfiPixGemm& g, int b_rc, float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st,
                     bool fwd_f4 = false) {
+    AFI_TRY(afi_o16_refused(g));                           // (before any pass: the output transform would refuse it last)
     const int nph = g.nKphase;                             // 1, or 4 phase views of a pixel-shuffled A (conv-transpose data gradient)
     const int K = g.Ck * nph, Nc = g.Ncols;
     if (ws_floats < wino_ws_floats(g.N, g.H, g.W, K, Nc)) return AFI_ERR_WORKSPACE;
@@ -853,6 +857,16 @@ int afi_conv3x3_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, 
     g.alpha = alpha; g.beta = beta; g.lrelu = lrelu;
     return launch_pix_op(cx, g, 0, (hipStream_t)stream);
 }
+int afi_conv3x3_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, afi_view_t out,
+                          int out_dtype, float alpha, float beta, int lrelu, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if (out_dtype != AFI_STORE_BF16 && out_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
+    if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
+    AfiPixGemm g = conv_fwd_desc(V(x), N, H, W, Cin, w, bias, Cout, V(out));
+    g.alpha = alpha; g.beta = beta; g.lrelu = lrelu; g.o_dtype = out_dtype;
+    return launch_pix_op(cx, g, 0, (hipStream_t)stream);
+}
 int afi_conv3x3_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
                       afi_view_t z, void* stream) {
     afi_ctx* cx = ctx; (void)cx;
@@ -877,6 +891,17 @@ int afi_conv3x3_wino_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int 
     AFI_CTX_CHECK(ctx);
     if (N <= 0 || H <= 0 || W <= 0 || !ws) return AFI_ERR_BAD_ARG;
     return wino_conv(cx, 0, V(x), N, H, W, Cin, w, Cout, bias, V(out), null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
+}
+int afi_conv3x3_wino_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, afi_view_t out,
+                               int out_dtype, float* ws, long long ws_floats, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if (out_dtype != AFI_STORE_BF16 && out_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
+    if (N <= 0 || H <= 0 || W <= 0 || !ws) return AFI_ERR_BAD_ARG;
+    if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
+    AfiPixGemm g = conv_fwd_desc(V(x), N, H, W, Cin, w, bias, Cout, V(out));
+    g.o_dtype = out_dtype;
+    return wino_run(cx, g, 0, ws, ws_floats, nullptr, 0, (hipStream_t)stream);
 }
 int afi_conv3x3_wino_infer(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, afi_view_t out, int act,
                            float* ws, long long ws_floats, void* stream) {
@@ -925,6 +950,18 @@ int afi_conv1x1_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Co
     g.ntaps = 1; g.a_sgn = -1; g.Ck = Cout; g.Ncols = Cin; g.CoutPhase = Cin;
     g.A = V(dy); g.B = w; g.b_sRow = Cin; g.b_sTap = 0;
     g.O = V(dx); g.alpha = alpha; g.beta = beta;
+    return launch_pix_op(cx, g, 1, (hipStream_t)stream);
+}
+int afi_conv1x1_dgrad_out16(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, int dx_dtype, float alpha,
+                            float beta, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if (dx_dtype != AFI_STORE_BF16 && dx_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
+    if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
+    AfiPixGemm g = pix_default(N, H, W);
+    g.ntaps = 1; g.a_sgn = -1; g.Ck = Cout; g.Ncols = Cin; g.CoutPhase = Cin;
+    g.A = V(dy); g.B = w; g.b_sRow = Cin; g.b_sTap = 0;
+    g.O = V(dx); g.alpha = alpha; g.beta = beta; g.o_dtype = dx_dtype;
     return launch_pix_op(cx, g, 1, (hipStream_t)stream);
 }
 int afi_conv1x1_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, void* stream) {
@@ -1121,6 +1158,13 @@ int afi_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, void* str
 int afi_nhwc_to_nchw(const float* in, float* out, int N, int C, int P, void* stream) {
     return afi_launch_nhwc_to_nchw(in, out, N, C, P, (hipStream_t)stream);
 }
+int afi_cast_to_f32_nhwc(const void* src, int src_dtype, int N, int C, int H, int W, long long sN, long long sC, long long sH, long long sW, float* dst,
+                         void* stream) {
+    return afi_launch_cast_to_f32_nhwc(src, src_dtype, N, C, H, W, sN, sC, sH, sW, dst, (hipStream_t)stream);
+}
+int afi_cast_from_f32_nhwc(afi_view_t src, int N, int H, int W, int C, void* dst, int dst_dtype, void* stream) {
+    return afi_launch_cast_from_f32_nhwc(V(src), N, H, W, C, dst, dst_dtype, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------------ generator
 // forward workspace layout (floats):  [Wp 36*C*C][buf_r : n_rdb x P*L][t : P*C][a7 : P*C][u : 4P*C]     L = C + 4G
@@ -1212,12 +1256,14 @@ static int gen_check(const afi_gen_params_t* p) {
     return AFI_OK;
 }
 
-int afi_generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, float* ws, long long ws_floats,
-                      void* stream) {
+// out_dtype (AFI_STORE_*): storage of `out` only -- the final conv's epilogue rounds there; everything before it is fp32
+static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, int out_dtype, float* ws,
+                         long long ws_floats, void* stream) {
     afi_ctx* cx = ctx; (void)cx;
     AFI_CTX_CHECK(ctx);
     AFI_TRY(gen_check(prm));
     if (N <= 0 || H <= 0 || W <= 0 || !ws || !xv.p || !outv.p) return AFI_ERR_BAD_ARG;
+    if (out_dtype != AFI_STORE_F32 && out_dtype != AFI_STORE_BF16 && out_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
     const int C = prm->C, G = prm->G, R = prm->n_rdb;
     const GenWs l = gen_ws(C, G, R, N, H, W);
     if (ws_floats < l.total) return AFI_ERR_WORKSPACE;
@@ -1415,10 +1461,21 @@ int afi_generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv
     {   // final conv (:107-108) + bilinear x2 skip of the input (:125,130) fused in the epilogue
         AfiPixGemm g = conv_fwd_desc(u, N, 2 * H, 2 * W, C, prm->w9, prm->b9, C, V(outv));
         g.R1 = x; g.r1s = 1.f; g.r1_lo = 0; g.r1_hi = C; g.r1_bilinear = 1;
+        g.o_dtype = out_dtype;
         im.attach(g, prm->w9);                              // (small maps only: no image was requested otherwise)
         AFI_TRY(PG(g, 0));
     }
     return AFI_OK;
+}
+
+int afi_generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, float* ws, long long ws_floats,
+                      void* stream) {
+    return generator_fwd(ctx, prm, xv, N, H, W, outv, AFI_STORE_F32, ws, ws_floats, stream);
+}
+int afi_generator_fwd_out16(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, int out_dtype, float* ws,
+                            long long ws_floats, void* stream) {
+    if (out_dtype != AFI_STORE_BF16 && out_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
+    return generator_fwd(ctx, prm, xv, N, H, W, outv, out_dtype, ws, ws_floats, stream);
 }
 
 int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen_params_t* gr, afi_view_t xv, int N, int H, int W, const float* ws,

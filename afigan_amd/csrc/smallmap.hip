@@ -476,7 +476,7 @@ __device__ __forceinline__ void afi_epilogue_finish(const AfiPixGemm& p, const A
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= (e.zv[j] > 0.f ? 1.f : AFI_LRELU_SLOPE);
     }
-    *(f32x4*)e.dst = v;
+    afi_out_store(p, e.dst, v);
 }
 __device__ __forceinline__ void afi_epilogue_store_fast(const AfiPixGemm& p, int img, int y, int x, int col, f32x4 accv, afi_gfloat* zpage) {
     const AfiEpiPre e = afi_epilogue_prefetch(p, img, y, x, col, zpage);

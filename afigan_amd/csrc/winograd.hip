@@ -375,6 +375,7 @@ __global__ __launch_bounds__(256) void afi_wino_output_epi_kernel(const float* _
     if (STATS) afi_stats_block_write(p, st0, st1, smn, smx, STATS == 2 ? p.bstats : nullptr);
 }
 int afi_launch_wino_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st) {
+    AFI_TRY(afi_o16_refused(p));
     if (p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ncols <= 0 || (p.Ncols & 3)) return AFI_ERR_BAD_ARG;
     const int Th = (p.H + 1) / 2, Tw = (p.W + 1) / 2;
     const long long T = (long long)p.N * Th * Tw;
@@ -786,6 +787,7 @@ __global__ __launch_bounds__(256) void afi_wino4_output_epi_kernel(const float* 
     if (STATS) afi_stats_block_write(p, st0, st1, smn, smx, STATS == 2 ? p.bstats : nullptr);
 }
 int afi_launch_wino4_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st) {
+    AFI_TRY(afi_o16_refused(p));
     if (p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ncols <= 0 || (p.Ncols & 3)) return AFI_ERR_BAD_ARG;
     const int Th = (p.H + 3) / 4, Tw = (p.W + 3) / 4;
     const long long T = (long long)p.N * Th * Tw;

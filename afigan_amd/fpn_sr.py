@@ -30,13 +30,20 @@ def _dense_pm(t):
     return t if ops.is_dense_pm(t) else t.contiguous(memory_format=torch.channels_last)
 
 
+def _grad_pm(dy):
+    """The gradient at a pyramid output as a dense fp32 pixel-major tensor: a bf16 / fp16 one (of a 2-byte level) widened."""
+    return _dense_pm(dy) if dy.dtype == torch.float32 else ops.ingest(dy)[0]
+
+
 class _LateralMergeFn(torch.autograd.Function):
-    """prev = conv1x1(feat, w) + b + top_down   (fpn_sr.py:152-153), add fused into the GEMM epilogue."""
+    """prev = conv1x1(feat, w) + b + top_down   (fpn_sr.py:152-153), add fused into the GEMM epilogue.  boundary=True (the FPN / PAFPN
+    laterals): `feat` may be bf16 / fp16 (the bottom-up features under torch.autocast); it is widened, `prev` is fp32, and feat's gradient
+    is stored in its dtype by the dgrad epilogue.  boundary=False (the BiFPN's convs): fp32 only."""
 
     @staticmethod
     @_lib.ctx_forward
-    def forward(ctx, feat, w, b, top_down):
-        featp = ops.pixel_major(feat.detach())
+    def forward(ctx, feat, w, b, top_down, boundary=False):
+        featp, ctx.feat_dtype = ops.ingest(feat.detach()) if boundary else (ops.pixel_major(feat.detach()), torch.float32)
         td = ops.pixel_major(top_down.detach()) if top_down is not None else None
         out = ops.conv1x1_fwd(featp, w.detach(), b.detach() if b is not None else None, add=td)
         ctx.save_for_backward(featp, w.detach())
@@ -49,11 +56,11 @@ class _LateralMergeFn(torch.autograd.Function):
         featp, w = ctx.saved_tensors
         dy = _dense_pm(dy)
         need = ctx.needs_input_grad
-        dfeat = ops.conv1x1_dgrad(dy, w.reshape(w.shape[0], -1)) if need[0] else None
+        dfeat = ops.conv1x1_dgrad(dy, w.reshape(w.shape[0], -1), out_dtype=ctx.feat_dtype) if need[0] else None
         dw = ops.conv1x1_wgrad(dy, featp).reshape(w.shape) if need[1] else None
         db = ops.bias_grad(dy) if (ctx.has_bias and need[2]) else None
         dtd = dy if (ctx.has_td and need[3]) else None
-        return dfeat, dw, db, dtd
+        return dfeat, dw, db, dtd, None
 
 
 def _winograd_pays(x, cout):
@@ -63,16 +70,16 @@ def _winograd_pays(x, cout):
 
 
 class _Conv3x3Fn(torch.autograd.Function):
-    """p = conv3x3(prev, w) + b   (fpn_sr.py:145,158)."""
+    """p = conv3x3(prev, w) + b   (fpn_sr.py:145,158); out_dtype: the pyramid's storage dtype (bf16 / fp16: rounded by the epilogue)."""
 
     @staticmethod
     @_lib.ctx_forward
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, out_dtype=torch.float32):
         xp = ops.pixel_major(x.detach())
         wk = ops.ohwi(w.detach())
         ctx.wino = _winograd_pays(xp, wk.shape[0])
         fwd = ops.conv3x3_wino_fwd if ctx.wino else ops.conv3x3_fwd
-        out = fwd(xp, wk, b.detach() if b is not None else None)
+        out = fwd(xp, wk, b.detach() if b is not None else None, out_dtype=out_dtype)
         ctx.save_for_backward(xp, wk)
         ctx.has_bias = b is not None
         return out
@@ -81,13 +88,13 @@ class _Conv3x3Fn(torch.autograd.Function):
     @_lib.ctx_backward
     def backward(ctx, dy):
         xp, wk = ctx.saved_tensors
-        dy = _dense_pm(dy)
+        dy = _grad_pm(dy)
         need = ctx.needs_input_grad
         dgrad, wgrad = (ops.conv3x3_wino_dgrad, ops.conv3x3_wino_wgrad) if ctx.wino else (ops.conv3x3_dgrad, ops.conv3x3_wgrad)
         dx = dgrad(dy, wk) if need[0] else None
         dw = wgrad(dy, xp) if need[1] else None
         db = ops.bias_grad(dy) if (ctx.has_bias and need[2]) else None
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -147,15 +154,18 @@ class _FpnConv(nn.Module):
         self.bias = nn.Parameter(torch.zeros(cout)) if self.norm is None else None     # fpn_sr.py:76: use_bias = norm == ""
         nn.init.kaiming_uniform_(self.weight, a=1)           # c2_xavier_fill (fvcore): kaiming_uniform_(a=1), zero bias
 
-    def forward(self, x, add=None):
+    def forward(self, x, add=None, out_dtype=torch.float32):
+        """out_dtype (output convs): the storage dtype of the pyramid level; the lateral conv's output (the top-down chain) is always fp32."""
         if self.norm is not None:                          # conv -> norm (torch) -> top-down add: the add cannot ride in the GEMM epilogue
-            y = _LateralMergeFn.apply(x, self.weight, None, None) if self.k == 1 else _Conv3x3Fn.apply(x, self.weight, None)
+            y = _LateralMergeFn.apply(x, self.weight, None, None, True) if self.k == 1 else _Conv3x3Fn.apply(x, self.weight, None)
             y = self.norm(y)
+            if out_dtype != torch.float32:                 # (the norm runs on the fp32 conv output; the level is rounded once, after it)
+                y = y.to(out_dtype)
             return y if add is None else y + add
         if self.k == 1:
-            return _LateralMergeFn.apply(x, self.weight, self.bias, add)
+            return _LateralMergeFn.apply(x, self.weight, self.bias, add, True)
         assert add is None
-        return _Conv3x3Fn.apply(x, self.weight, self.bias)
+        return _Conv3x3Fn.apply(x, self.weight, self.bias, out_dtype)
 
 
 class LastLevelMaxPool(nn.Module):
@@ -226,9 +236,10 @@ class FPN_AFIGAN(nn.Module):
     def _forward_impl(self, x):
         bottom_up_features = self.bottom_up(x)
         feats = [bottom_up_features[f] for f in self.in_features[::-1]]
+        dt = ops.boundary_dtype(*feats)                       # fp32, or the bf16 / fp16 of a 2-byte backbone: p2..p6 are stored in it
         results = []
         prev = self.lateral_convs[0](feats[0])
-        results.append(self.output_convs[0](prev))
+        results.append(self.output_convs[0](prev, out_dtype=dt))
         for f, lateral, output in zip(feats[1:], self.lateral_convs[1:], self.output_convs[1:]):
             top_down = self.srf_module(prev)                  # fpn_sr.py:151
             if top_down.shape[-2:] != f.shape[-2:]:
@@ -237,7 +248,7 @@ class FPN_AFIGAN(nn.Module):
             prev = lateral(f, add=top_down)                   # :152-153 in one GEMM
             if self._fuse_type == "avg":
                 prev = prev / 2
-            results.insert(0, output(prev))
+            results.insert(0, output(prev, out_dtype=dt))
         if self.top_block is not None:
             tb_in = bottom_up_features.get(self.top_block.in_feature, None)
             if tb_in is None:

@@ -80,15 +80,20 @@ class _GeneratorFn(torch.autograd.Function):
     @staticmethod
     @_lib.ctx_forward
     def forward(ctx, x, gen, *params):
-        xp = ops.pixel_major(x.detach())
+        xp, dt = ops.ingest(x.detach())                    # a bf16 / fp16 x: widened to fp32 here, the output rounded by the final conv's store
         N, Cc, H, W = xp.shape
         lib = _lib.load()
         prm, keep = gen._param_struct(params)
         ws_floats = lib.afi_generator_fwd_ws_floats(gen.in_channels, gen.growth_rate, gen.n_residual_dense_blocks, N, H, W)
         ws = ops.new_workspace(ws_floats, x.device)
-        out = ops.new_pixel_major(N, Cc, 2 * H, 2 * W, x.device)
-        call("afi_generator_fwd", C.byref(prm), ops.view_of(xp), N, H, W, ops.view_of(out), C.c_void_p(ws.data_ptr()), ws_floats,
-             ops.stream_ptr())
+        out = ops.new_pixel_major(N, Cc, 2 * H, 2 * W, x.device, dtype=dt)
+        if dt == torch.float32:
+            call("afi_generator_fwd", C.byref(prm), ops.view_of(xp), N, H, W, ops.view_of(out), C.c_void_p(ws.data_ptr()), ws_floats,
+                 ops.stream_ptr())
+        else:
+            call("afi_generator_fwd_out16", C.byref(prm), ops.view_of(xp), N, H, W, ops.view_of(out), ops.STORE_DTYPES[dt],
+                 C.c_void_p(ws.data_ptr()), ws_floats, ops.stream_ptr())
+        ctx.dt = dt
         ctx.gen = gen
         ctx.shape = (N, H, W)
         ctx.x_needs_grad = x.requires_grad
@@ -102,7 +107,10 @@ class _GeneratorFn(torch.autograd.Function):
         xp, ws, *weights = ctx.saved_tensors
         N, H, W = ctx.shape
         lib = _lib.load()
-        dout = dout if ops.is_dense_pm(dout) else ops.pixel_major(dout.contiguous())
+        if dout.dtype == torch.float32:
+            dout = dout if ops.is_dense_pm(dout) else ops.pixel_major(dout.contiguous())
+        else:
+            dout, _ = ops.ingest(dout)                        # (dense fp32 [N][2H][2W][C])
         prm, _ = gen._param_struct(weights, already_packed=True)
         # only the parameters that require a gradient get one (MODEL.AFI_FREEZE, fpn_sr.py:67-69, freezes them all: the
         # library then skips every weight-gradient GEMM); zeros_like keeps the [O][kh][kw][I] memory layout
@@ -118,7 +126,7 @@ class _GeneratorFn(torch.autograd.Function):
         if grad_tap is not None:
             grad_tap.append({"shape": (N, gen.in_channels, H, W), "ctx": ctx.afi_cx.handle.value, "dtype": ctx.afi_cx.dtype,
                              "grads": [g.clone() if g is not None else None for g in grads]})
-        return (dx, None, *grads)
+        return (ops.narrow(dx, ctx.dt) if dx is not None else None, None, *grads)
 
 
 class Generator(nn.Module):
@@ -188,9 +196,11 @@ class Generator(nn.Module):
     def forward(self, features):
         """bilinear_x2(features) + Generators[0](features)   (generator_rdb.py:123-130).
 
-        `features`: [N, C, H, W] fp32 on the GPU, NCHW-contiguous or channels_last.  Returns [N, C, 2H, 2W] in
-        channels_last memory format (same values / logical shape as the reference)."""
-        ops._check_cuda(features)
+        `features`: [N, C, H, W] fp32 on the GPU (or bf16 / fp16 inside torch.autocast: ops.generator_input_dtype), NCHW-contiguous or
+        channels_last.  Returns [N, C, 2H, 2W] of the same dtype in channels_last memory format (same values / logical shape as the
+        reference).  A 2-byte input runs the same fp32 computation (its gradient comes back in its dtype, the parameters' stay fp32): the
+        output is the fp32 result rounded once."""
+        ops.generator_input_dtype(features)
         if features.dim() != 4 or features.shape[1] != self.in_channels:
             raise _lib.AfiError(f"expected [N,{self.in_channels},H,W], got {tuple(features.shape)}")
         if features.numel() == 0:

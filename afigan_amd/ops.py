@@ -46,12 +46,78 @@ def new_workspace(floats: int, device) -> torch.Tensor:
     return torch.empty(int(floats), device=device, dtype=torch.float32)
 
 
-def new_pixel_major(N, C_, H, W, device, zero=False) -> torch.Tensor:
+def new_pixel_major(N, C_, H, W, device, zero=False, dtype=torch.float32) -> torch.Tensor:
     """Fresh [N,C,H,W] tensor whose memory is [N][H][W][C]."""
     if _POISON and not zero:
-        return torch.full((N, H, W, C_), float("nan"), device=device, dtype=torch.float32).permute(0, 3, 1, 2)
+        return torch.full((N, H, W, C_), float("nan"), device=device, dtype=dtype).permute(0, 3, 1, 2)
     f = torch.zeros if zero else torch.empty
-    return f((N, H, W, C_), device=device, dtype=torch.float32).permute(0, 3, 1, 2)
+    return f((N, H, W, C_), device=device, dtype=dtype).permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------ storage dtype at the module boundary
+# The interpolator and the AFI FPN / PAFPN accept bf16 / fp16 activations (torch.autocast): they are widened to fp32 on the way in, every
+# kernel computes in fp32 under the context's compute dtype, and the module's outputs (and its inputs' gradients) are rounded back ONCE, by
+# the epilogue that stores them (DESIGN.md 10).  Only the helpers below let a 2-byte tensor in; _check_cuda keeps refusing it everywhere else.
+STORE_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # AFI_STORE_* of include/afigan_hip.h
+
+
+def boundary_dtype(*ts) -> torch.dtype:
+    """The storage dtype of the tensors a module receives: fp32, bf16 or fp16, on the GPU, one dtype for all of them (AfiError otherwise)."""
+    dts = {t.dtype for t in ts if t is not None}
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise _lib.AfiError("the AFI-GAN hot path runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if len(dts) > 1:
+        raise _lib.AfiError(f"the inputs of one module must share one dtype, got {sorted(str(d) for d in dts)}")
+    dt = dts.pop() if dts else torch.float32
+    if dt not in STORE_DTYPES:
+        raise _lib.AfiError(f"fp32, bf16 or fp16 activations only at this boundary, got {dt}")
+    return dt
+
+
+def _autocast_on() -> bool:
+    try:
+        return torch.is_autocast_enabled("cuda")
+    except TypeError:                                       # (torch < 2.4: the CUDA flag takes no argument)
+        return torch.is_autocast_enabled()
+
+
+def generator_input_dtype(t) -> torch.dtype:
+    """boundary_dtype of the interpolator's own input (Generator.forward).  A 2-byte map reaches a stand-alone interpolator from the reference's
+    FPN code run under torch.autocast("cuda"), and is taken there; outside an autocast region the stand-alone module keeps the fp32-only
+    contract tests/test_gpu_modules.py::test_error_paths pins (an fp16 input raises).  FPN_AFIGAN / PAFPN_AFIGAN take 2-byte bottom-up
+    features with or without autocast (boundary_dtype alone): they never hand the interpolator anything but their fp32 top-down chain."""
+    dt = boundary_dtype(t)
+    if dt != torch.float32 and not _autocast_on():
+        raise _lib.AfiError(f"Generator: fp32 only outside torch.autocast, got {dt} (a 2-byte map is taken under torch.autocast(\"cuda\"))")
+    return dt
+
+
+def ingest(t: torch.Tensor):
+    """(fp32 pixel-major tensor, storage dtype of t): fp32 goes through pixel_major as always; a bf16 / fp16 tensor (NCHW, channels_last
+    or any strided view) is widened into a fresh dense fp32 [N][H][W][C] by afi_cast_to_f32_nhwc (exact)."""
+    dt = boundary_dtype(t)
+    if dt == torch.float32:
+        return pixel_major(t), dt
+    N, C_, H, W = t.shape
+    out = new_pixel_major(N, C_, H, W, t.device)
+    sN, sC, sH, sW = t.stride()
+    call("afi_cast_to_f32_nhwc", C.c_void_p(t.data_ptr()), STORE_DTYPES[dt], N, C_, H, W, sN, sC, sH, sW, C.c_void_p(out.data_ptr()), stream_ptr())
+    return out, dt
+
+
+def narrow(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """A pixel-major fp32 tensor stored as `dtype`: itself for fp32, else a dense channels_last bf16 / fp16 copy rounded to nearest even
+    (afi_cast_from_f32_nhwc; for gradients that no GEMM epilogue writes)."""
+    _check_cuda(t)
+    if dtype == torch.float32:
+        return t
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise _lib.AfiError(f"narrow: fp32, bf16 or fp16 only, got {dtype}")
+    N, C_, H, W = t.shape
+    out = new_pixel_major(N, C_, H, W, t.device, dtype=dtype)
+    call("afi_cast_from_f32_nhwc", view_of(t), N, H, W, C_, C.c_void_p(out.data_ptr()), STORE_DTYPES[dtype], stream_ptr())
+    return out
 
 
 def pixel_major(t: torch.Tensor) -> torch.Tensor:
@@ -80,7 +146,7 @@ def view_of(t: torch.Tensor, c0: int = 0) -> View:
     """afi_view_t of a pixel-major tensor (optionally starting at channel c0)."""
     if not is_pixel_major(t):
         raise _lib.AfiError(f"tensor is not pixel-major: shape {tuple(t.shape)} strides {t.stride()}")
-    return View(t.data_ptr() + 4 * c0, t.stride(0), t.stride(2), t.stride(3))
+    return View(t.data_ptr() + t.element_size() * c0, t.stride(0), t.stride(2), t.stride(3))
 
 
 def is_dense_pm(t: torch.Tensor) -> bool:
@@ -208,12 +274,20 @@ def _ensure_op_scratch(device):
     return buf
 
 
-def conv3x3_fwd(x, w, bias=None, lrelu=False, out=None, alpha=1.0, beta=0.0):
+def conv3x3_fwd(x, w, bias=None, lrelu=False, out=None, alpha=1.0, beta=0.0, out_dtype=torch.float32):
+    """out_dtype bf16 / fp16: a fresh 2-byte output rounded by the epilogue (afi_conv3x3_fwd_out16; write-only: beta must be 0)."""
     _check_cuda(x, w, bias, out)
     _ensure_op_scratch(x.device)
     N, Cin, H, W = x.shape
     Cout = w.shape[0]
     w = ohwi(w)
+    if out_dtype != torch.float32:
+        if out is not None:
+            raise _lib.AfiError("conv3x3_fwd: a 2-byte output is always a fresh tensor")
+        out = new_pixel_major(N, Cout, H, W, x.device, dtype=out_dtype)
+        call("afi_conv3x3_fwd_out16", view_of(x), N, H, W, Cin, _p(w), _p(bias), Cout, view_of(out), STORE_DTYPES[out_dtype], float(alpha),
+             float(beta), int(lrelu), stream_ptr())
+        return out
     if out is None:
         out = new_pixel_major(N, Cout, H, W, x.device)
     call("afi_conv3x3_fwd", view_of(x), N, H, W, Cin, _p(w), _p(bias), Cout, view_of(out), float(alpha), float(beta), int(lrelu),
@@ -245,15 +319,20 @@ def conv3x3_wgrad(dy, x, dw=None, alpha=1.0):
     return dw
 
 
-def conv3x3_wino_fwd(x, w, bias=None):
-    """3x3 conv in Winograd F(2x2,3x3) form (large maps, many channels): out = conv(x, w) + bias."""
+def conv3x3_wino_fwd(x, w, bias=None, out_dtype=torch.float32):
+    """3x3 conv in Winograd F(2x2,3x3) form (large maps, many channels): out = conv(x, w) + bias, stored as out_dtype (fp32, bf16 or fp16:
+    the output transform rounds)."""
     _check_cuda(x, w, bias)
     N, Cin, H, W = x.shape
     Cout = w.shape[0]
     w = ohwi(w)
     n = _lib.load().afi_conv3x3_wino_ws_floats(N, H, W, Cin, Cout)
     ws = new_workspace(n, x.device)
-    out = new_pixel_major(N, Cout, H, W, x.device)
+    out = new_pixel_major(N, Cout, H, W, x.device, dtype=out_dtype)
+    if out_dtype != torch.float32:
+        call("afi_conv3x3_wino_fwd_out16", view_of(x), N, H, W, Cin, _p(w), _p(bias), Cout, view_of(out), STORE_DTYPES[out_dtype], _p(ws), n,
+             stream_ptr())
+        return out
     call("afi_conv3x3_wino_fwd", view_of(x), N, H, W, Cin, _p(w), _p(bias), Cout, view_of(out), _p(ws), n, stream_ptr())
     return out
 
@@ -371,12 +450,20 @@ def conv1x1_fwd(x, w, bias=None, add=None, add_scale=1.0, alpha=1.0, out=None, a
     return out
 
 
-def conv1x1_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0):
+def conv1x1_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, out_dtype=torch.float32):
+    """out_dtype bf16 / fp16: a fresh 2-byte dx rounded by the epilogue (afi_conv1x1_dgrad_out16; beta must be 0)."""
     _check_cuda(dy, w, dx)
     _ensure_op_scratch(dy.device)
     N, Cout, H, W = dy.shape
     Cin = w.shape[1]
     w2 = w.reshape(Cout, Cin).contiguous()
+    if out_dtype != torch.float32:
+        if dx is not None:
+            raise _lib.AfiError("conv1x1_dgrad: a 2-byte output is always a fresh tensor")
+        dx = new_pixel_major(N, Cin, H, W, dy.device, dtype=out_dtype)
+        call("afi_conv1x1_dgrad_out16", view_of(dy), N, H, W, Cout, _p(w2), Cin, view_of(dx), STORE_DTYPES[out_dtype], float(alpha), float(beta),
+             stream_ptr())
+        return dx
     if dx is None:
         dx = new_pixel_major(N, Cin, H, W, dy.device)
     call("afi_conv1x1_dgrad", view_of(dy), N, H, W, Cout, _p(w2), Cin, view_of(dx), float(alpha), float(beta), stream_ptr())

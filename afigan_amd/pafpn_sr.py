@@ -153,6 +153,7 @@ class PAFPN_AFIGAN(nn.Module):
     def _forward_impl(self, x):
         bottom_up_features = self.bottom_up(x)
         feats = [bottom_up_features[f] for f in self.in_features[::-1]]
+        dt = ops.boundary_dtype(*feats)                       # fp32, or the bf16 / fp16 of a 2-byte backbone: p2..p6 are stored in it
         fs = 0.5 if self._fuse_type == "avg" else 1.0
         prev = self.lateral_convs[0](feats[0])
         topdown = [prev]
@@ -166,12 +167,12 @@ class PAFPN_AFIGAN(nn.Module):
                 prev = prev * fs
             topdown.insert(0, prev)
         pa = topdown[0]
-        results = [self.output_convs[0](pa)]
+        results = [self.output_convs[0](pa, out_dtype=dt)]
         for inter, ds, output in zip(topdown[1:], self.downsample_convs, self.output_convs[1:]):   # bottom-up augmentation
             if tuple(inter.shape[-2:]) != ((pa.shape[-2] + 1) // 2, (pa.shape[-1] + 1) // 2):
                 raise _lib.AfiError(f"stride-2 output of {tuple(pa.shape[-2:])} does not match the next level {tuple(inter.shape[-2:])}")
             pa = ds(pa, inter, fs)
-            results.append(output(pa))
+            results.append(output(pa, out_dtype=dt))
         if self.top_block is not None:
             tb_in = bottom_up_features.get(self.top_block.in_feature, None)
             if tb_in is None:

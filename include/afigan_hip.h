@@ -244,6 +244,17 @@ int afi_generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t x,
 int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen_params_t* grads, afi_view_t x, int N, int H, int W,
                       const float* ws, const float* dout, float* dx, float* scratch, long long scratch_floats, void* stream);
 
+/* Storage dtype of a tensor at the module boundary (bf16 / fp16 activations under torch.autocast).  It is not an arithmetic setting:
+ * every kernel computes in fp32 under the context's compute dtype, and a 2-byte result is the fp32 one rounded ONCE, to nearest even
+ * (torch's .to(dtype)), by the epilogue that stores it.  Views of 2-byte tensors (afi_view_t.p) point at 2-byte elements, strides in elements. */
+#define AFI_STORE_F32 0
+#define AFI_STORE_BF16 1
+#define AFI_STORE_F16 2
+/* afi_generator_fwd with a 2-byte `out` (out_dtype AFI_STORE_BF16 / _F16): `x` is fp32 (widened by afi_cast_to_f32_nhwc), the workspace and
+ * everything afi_generator_bwd reads are the fp32 call's, bit for bit; only the final conv's store rounds. */
+int afi_generator_fwd_out16(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t x, int N, int H, int W, afi_view_t out, int out_dtype,
+                            float* ws, long long ws_floats, void* stream);
+
 /* Parameters of Discriminator.Discriminators[0] (feature_patch_discriminator.py:32-41). */
 typedef struct afi_disc_params {
     int F[4];               /* channels: in (256), 512, 1024, 1024 */
@@ -334,6 +345,9 @@ int afi_conv3x3_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Co
                       float alpha, float beta, afi_view_t z_or_null, void* stream);
 /* dw[Cout][3][3][Cin] += alpha * sum_pix dy (x) x */
 int afi_conv3x3_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, void* stream);
+/* afi_conv3x3_fwd storing a 2-byte `out` (out_dtype AFI_STORE_BF16 / _F16).  A 2-byte output is write-only: beta != 0 is AFI_ERR_UNSUPPORTED. */
+int afi_conv3x3_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                          afi_view_t out, int out_dtype, float alpha, float beta, int lrelu, void* stream);
 
 /* 1x1 convs of the AFI FPN lateral merge (fpn_sr.py:79-81,152-153), w [Cout][Cin]:
  * out = act(alpha*conv1x1(x, w) + bias + beta*out + r1_scale*r1)   -- r1 = the up-sampled top-down feature (or NULL) */
@@ -342,6 +356,9 @@ int afi_conv1x1_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, 
 int afi_conv1x1_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
                       void* stream);
 int afi_conv1x1_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, void* stream);
+/* afi_conv1x1_dgrad storing a 2-byte `dx` (dx_dtype AFI_STORE_BF16 / _F16; beta != 0: AFI_ERR_UNSUPPORTED) -- the lateral conv's input gradient */
+int afi_conv1x1_dgrad_out16(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, int dx_dtype,
+                            float alpha, float beta, void* stream);
 
 /* The same 3x3 / stride-1 / pad-1 conv in Winograd F(2x2,3x3) form (2.25x fewer matrix-core FLOPs; large maps with many
  * channels): weight + input transforms, one batched 1x1 GEMM over the 16 transform points, output transform with the
@@ -350,6 +367,9 @@ int afi_conv1x1_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H,
 long long afi_conv3x3_wino_ws_floats(int N, int H, int W, int Cin, int Cout);
 int afi_conv3x3_wino_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w_ohwi, const float* bias_or_null, int Cout,
                          afi_view_t out, float* ws, long long ws_floats, void* stream);
+/* afi_conv3x3_wino_fwd storing a 2-byte `out` (out_dtype AFI_STORE_BF16 / _F16), rounded in the output transform */
+int afi_conv3x3_wino_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w_ohwi, const float* bias_or_null, int Cout,
+                               afi_view_t out, int out_dtype, float* ws, long long ws_floats, void* stream);
 /* inference form: out = act(conv + bias), act 0 none / 1 LeakyReLU(0.2) / 2 ReLU; no backward will follow, so maps of >= 8192 pixels
  * take the F(4x4,3x3) tiling (4x fewer multiplies, ~3e-5 relative rounding) */
 int afi_conv3x3_wino_infer(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w_ohwi, const float* bias_or_null, int Cout,
@@ -466,6 +486,13 @@ int afi_scale_inplace(float* p, long long n, float s, void* stream);
 /* layout changes at the detectron2 boundary: [N][C][P] <-> [N][P][C] */
 int afi_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, void* stream);
 int afi_nhwc_to_nchw(const float* in, float* out, int N, int C, int P, void* stream);
+/* storage-dtype casts at the module boundary.  to_f32: dst = the DENSE fp32 [N][H][W][C] copy of src (src_dtype AFI_STORE_*), whose element
+ * (n, c, y, x) is at src + n*sN + c*sC + y*sH + x*sW (strides in elements; exact).  from_f32: dst = the DENSE 2-byte [N][H][W][C] copy of the
+ * pixel-major fp32 view src (dst_dtype AFI_STORE_BF16 / _F16), rounded to nearest even.  Buffers need only their element's alignment:
+ * 8- / 16-byte vector accesses are used where src, dst, C and the strides allow them, one element per thread otherwise. */
+int afi_cast_to_f32_nhwc(const void* src, int src_dtype, int N, int C, int H, int W, long long sN, long long sC, long long sH, long long sW,
+                         float* dst, void* stream);
+int afi_cast_from_f32_nhwc(afi_view_t src, int N, int H, int W, int C, void* dst, int dst_dtype, void* stream);
 
 /* ------------------------------------------------------------------ dual-scale data path
  * afi_resize_bilinear_u8: what ResizeTransform.apply_image does to a uint8 image under the reference's DatasetMapper
