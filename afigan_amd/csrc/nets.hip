@@ -307,6 +307,43 @@ static float* wino_amax_take(afi_ctx* cx, float* ws, long long ws_floats, int n,
     e->next += n;
     return slot;
 }
+// What a Winograd conv runs as, decided once: wino_run, wino_conv and wino_wgrad run the form, disc_plan reads it.  Kinds: a forward on F(2x2);
+// a forward that may take F(4x4) (its masks decide no gradient, or AFI_OPT_WINOGRAD_F4_FORWARD names its block); a data gradient (K = Cout x nph
+// phase views of a pixel-shuffled A, Nc = Cin); a weight gradient (K = Cin, Nc = Cout, nph phase views of dy).
+enum WinoKind { kWinoFwd, kWinoFwdF4, kWinoDgrad, kWinoWgrad };
+struct WinoForm {
+    WinoKind kind; int dtype;
+    bool f4; int np;           // F(4x4,3x3): 36 transform points over 4x4 tiles; else F(2x2,3x3): 16 over 2x2
+    long long Tpad, T;         // tiles: padded to the GEMM's 128 rows / the map's own
+    bool dma, f16;             // the LDS-DMA NT GEMM on U's pre-split image (forward / data gradient); the GEMM in f16x3
+    bool presplit;             // a transform whose source maximum is known writes its planes already split (AFI_OPT_F16_PRESPLIT)
+    bool keep;                 // F(4x4) and pre-split: the planes a forward writes can serve its weight gradient
+};
+// gradients take F(4x4,3x3) (their error decides no LeakyReLU mask), forwards only where their kind says so.  bf16 operands (2^-9) cannot carry
+// the F(4x4) transforms (their 1/24 .. 8 coefficients cost two more digits: 3 % error), split-bf16 (2^-17) can; small maps have too few 4x4 tiles.
+constexpr long long kWinoF4MinPixels = 8192;
+static WinoForm wino_form(const afi_ctx* cx, int N, int H, int W, int K, int Nc, WinoKind kind, int nph = 1) {
+    WinoForm f;
+    f.kind = kind;
+    f.dtype = cx ? cx->dtype : afi_default_dtype();
+    f.f4 = kind != kWinoFwd && wino_f4(cx) && f.dtype != AFI_DTYPE_BF16 && (long long)N * H * W >= kWinoF4MinPixels;
+    f.np = f.f4 ? 36 : 16;
+    f.Tpad = f.f4 ? wino4_tpad(N, H, W) : wino_tpad(N, H, W);
+    f.T = f.f4 ? (long long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long long)N * ((H + 1) / 2) * ((W + 1) / 2);
+    // forward / data gradient: the bf16 settings run the LDS-DMA GEMM on tile-aligned shapes (every layer of the reference nets): its B operand
+    // is U split into bf16 parts in LDS-image order, made once per weight transform and cached in that form.  Weight gradient: the f16x3 TN GEMM
+    // where both channel counts fill its 128-wide tiles, else the fp32 one
+    const bool wgrad = kind == kWinoWgrad;
+    f.dma = !wgrad && f.dtype != AFI_DTYPE_F32 && !(f.Tpad % 128) && !(Nc % 128) && !(K % 32);
+    f.f16 = f.dtype == AFI_DTYPE_F16X3 && (wgrad ? !(f.Tpad % 32) && !(Nc % 128) && !(K % 128) : f.dma);
+    f.presplit = afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && f.f16 && nph == 1;
+    f.keep = f.f4 && f.presplit;
+    return f;
+}
+// the form of a pixel-GEMM descriptor wino_eligible accepted (b_rc = 1: its data gradient)
+static WinoForm wino_form(const afi_ctx* cx, const AfiPixGemm& g, int b_rc, bool fwd_f4 = false) {
+    return wino_form(cx, g.N, g.H, g.W, g.Ck * g.nKphase, g.Ncols, b_rc ? kWinoDgrad : fwd_f4 ? kWinoFwdF4 : kWinoFwd, g.nKphase);
+}
 static long long wino_ws_floats(int N, int H, int W, int K, int Nc) {
     const long long T2 = wino_tpad(N, H, W), T4 = wino4_tpad(N, H, W);
     const long long a = align4(16LL * K * Nc) + align4(16 * T2 * K) + align4(16 * T2 * Nc) + wino_usplit_floats(16, (long long)K * Nc);
@@ -464,29 +501,20 @@ static long long gen_wk6_bwd_floats(int C, int G, int R, long long P) {
     return f + (long long)R * (wk6_req_floats(L, C, 1) + wk6_req_floats(C, 4 * G, 1));           // (+ the growth convs' block-input columns side by side)
 }
 
-static int wino_run(afi_ctx* cx, const AfiPixGemm& g, int b_rc, float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st,
-                    bool fwd_f4 = false) {
+// a forward or data-gradient descriptor in the form f (wino_form of the same descriptor)
+static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st) {
     AFI_TRY(afi_o16_refused(g));                           // (before any pass: the output transform would refuse it last)
+    const int b_rc = f.kind == kWinoDgrad;
     const int nph = g.nKphase;                             // 1, or 4 phase views of a pixel-shuffled A (conv-transpose data gradient)
     const int K = g.Ck * nph, Nc = g.Ncols;
     if (ws_floats < wino_ws_floats(g.N, g.H, g.W, K, Nc)) return AFI_ERR_WORKSPACE;
-    // data gradients take F(4x4,3x3) (their error does not decide a LeakyReLU mask); forwards take F(2x2,3x3) unless the caller says
-    // fwd_f4: a forward whose activations feed no backward pass (its masks decide no gradient), or one of the blocks AFI_OPT_WINOGRAD_F4_FORWARD names
-    // bf16 operands (2^-9) cannot carry the F(4x4) transforms (their 1/24 .. 8 coefficient range costs two more digits: 3 % error);
-    // split-bf16 (2^-17) can
-    const int dtype = cx ? cx->dtype : afi_default_dtype();
-    const bool f4 = (b_rc || fwd_f4) && wino_f4(cx) && dtype != AFI_DTYPE_BF16 && (long long)g.N * g.H * g.W >= 8192;     // small maps: too few 4x4 tiles to fill the chip
-    const int np = f4 ? 36 : 16;
-    const long long Tpad = f4 ? wino4_tpad(g.N, g.H, g.W) : wino_tpad(g.N, g.H, g.W);
+    const int dtype = f.dtype, np = f.np; const long long Tpad = f.Tpad;
+    const bool f4 = f.f4, dma = f.dma, f16 = f.f16;
     float* U = ws;
     float* Vb = U + align4((long long)np * K * Nc);
     float* Mb = Vb + align4(np * Tpad * K);
     float* Usp = Mb + align4(np * Tpad * Nc);              // pre-split bf16 image of U (DMA GEMM), when it is not served from the cache
-    const bool f16 = dtype == AFI_DTYPE_F16X3;
     float* amax = nullptr;                                 // f16x3: the largest magnitude of A, raised by the input transform(s)
-    // the bf16 settings run the LDS-DMA GEMM on tile-aligned shapes (every layer of the reference nets): its B operand is U split into
-    // bf16 parts in LDS-image order, made once per weight transform and cached in that form
-    const bool dma = dtype != AFI_DTYPE_F32 && !(Tpad % 128) && !(Nc % 128) && !(K % 32);
     bool have_u = false;
     if (g.no_wcache) {
     } else if (dma) {
@@ -503,19 +531,18 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, int b_rc, float* ws, long 
     // f16x3: the largest magnitude of A.  g.a_amax given and known (its producer published it): the transform writes the planes already
     // split into fp16 pieces; given and not known: a zero-filled slot of the caller's that the transform raises (the caller keeps it, e.g. for
     // the backward pass); not given: a slot of the call's pool.
-    const bool want_amax = dma && f16;
     // (an input read through a BatchNorm affine -- AFI_OPT_D_FOLD_BN_APPLY -- is split like any other once its maximum is known: the statistics
     //  finalizer derives it from the conv output's per-channel extremes, afi_launch_bn_act_amax)
-    const bool a_pre = afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && want_amax && g.a_amax && g.a_amax_known && nph == 1 && !(g.Ck & 31);
-    if (want_amax && !(amax = g.a_amax ? g.a_amax : wino_amax_take(cx, ws, ws_floats, 1, st))) return AFI_ERR_LAUNCH;
+    const bool a_pre = f.presplit && g.a_amax && g.a_amax_known;
+    if (f16 && !(amax = g.a_amax ? g.a_amax : wino_amax_take(cx, ws, ws_floats, 1, st))) return AFI_ERR_LAUNCH;
     const AfiF16Bound abound = afi_f16_bound(amax, f4 ? 2 : 1);
-    if (g.v_keep && !(f4 && a_pre)) return AFI_ERR_BAD_ARG; // (the caller's predicate and this function's disagree: the backward would read planes nobody wrote)
+    if (g.v_keep && !(f.keep && a_pre)) return AFI_ERR_BAD_ARG;   // (never hand the weight gradient planes that were not written pre-split)
     if (g.v_keep) Vb = g.v_keep;                           // kept for the weight gradient of the same conv
     for (int ph = 0; ph < nph; ++ph) {                     // phase ph = (py, px): pixel (y, x) of its view is (2y + py, 2x + px) of A
         AfiView a = g.A;
         if (nph == 4) { a.p += (ph >> 1) * g.A.sH + (ph & 1) * g.A.sW; a.sH *= 2; a.sW *= 2; }
         // (a caller's not-yet-known slot is raised under every arithmetic: a later pass may read it)
-        float* raise = g.a_amax ? (g.a_amax_known ? nullptr : g.a_amax) : (want_amax ? amax : nullptr);
+        float* raise = g.a_amax ? (g.a_amax_known ? nullptr : g.a_amax) : (f16 ? amax : nullptr);
         AFI_TRY(f4 ? afi_launch_wino4_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, &g.a_bn, raise, a_pre ? &abound : nullptr)
                    : afi_launch_wino_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, &g.a_bn, raise, a_pre ? &abound : nullptr));
     }
@@ -542,38 +569,37 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, int b_rc, float* ws, long 
 
 // what a data gradient's output transform needs to take the BatchNorm-backward sums of its output along (AfiPixGemm::bstats)
 struct AfiBwdSums { double* rows; const float* c; AfiBnLoad bn; float slope; };
-// forward (mode 0: out = conv(in, w) + bias) or data gradient (mode 1: out = conv^T(in, w) * lrelu'(z)) by descriptor
-// stats (forward only): fp64 partial rows for the BatchNorm statistics of the output, accumulated by the output transform (afi_common.h);
-// *stats_rows receives the number of rows written, 0 when this call did not fuse them (the caller then runs the separate pass)
-// in_bn: `in` is read through a BatchNorm affine + LeakyReLU (AfiBnLoad): the activation of the block that produced it is never written
-static int wino_conv(afi_ctx* cx, int mode, AfiView in, int N, int H, int W, int K, const float* w, int Nc, const float* bias, AfiView out, AfiView z,
-                     float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st, bool fwd_f4 = false,
-                     double* stats = nullptr, int* stats_rows = nullptr, const AfiBnLoad* in_bn = nullptr, float* in_amax = nullptr, bool in_amax_known = false,
-                     float* v_keep = nullptr, float* stats_mm = nullptr, bool local_sums = false, const AfiBwdSums* bsums = nullptr, int* bsums_rows = nullptr) {
+// what a whole-net call adds to a plain Winograd conv (wino_conv); every member is optional
+struct WinoConvOpt {
+    // forward: fp64 partial rows for the BatchNorm statistics of the output, accumulated by the output transform (afi_common.h), with (stats_mm)
+    // the output's per-channel minimum / maximum; *stats_rows: the rows written, 0 when this call did not fuse them (the caller runs the separate pass)
+    double* stats = nullptr; float* stats_mm = nullptr; int* stats_rows = nullptr;
+    const AfiBnLoad* in_bn = nullptr;   // `in` is read through a BatchNorm affine + LeakyReLU: the activation of the block that produced it is never written
+    float* in_amax = nullptr; bool in_amax_known = false;   // f16x3: the slot of in's largest magnitude, and whether its producer published it
+    float* v_keep = nullptr;            // forward in a keeping form (WinoForm::keep): write the input planes here, for the weight gradient
+    bool local_sums = false;            // f16x3: the NT GEMM takes k-step-local sums (AFI_OPT_F16_LOCAL_SUMS)
+    const AfiBwdSums* bsums = nullptr; int* bsums_rows = nullptr;   // data gradient: the BatchNorm-backward sums of its output, as stats
+};
+// forward (kinds kWinoFwd / kWinoFwdF4: out = conv(in, w) + bias) or data gradient (kWinoDgrad: out = conv^T(in, w) * lrelu'(z)) by descriptor
+static int wino_conv(afi_ctx* cx, WinoKind kind, AfiView in, int N, int H, int W, int K, const float* w, int Nc, const float* bias, AfiView out, AfiView z,
+                     float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st, const WinoConvOpt& o = WinoConvOpt()) {
     if ((K & 3) || (Nc & 3)) return AFI_ERR_UNSUPPORTED;
-    AfiPixGemm g = mode ? conv_dgrad_desc(in, N, H, W, K, w, Nc, out) : conv_fwd_desc(in, N, H, W, K, w, bias, Nc, out);
-    if (in_bn) g.a_bn = *in_bn;
-    g.a_amax = in_amax; g.a_amax_known = in_amax_known ? 1 : 0;
-    g.v_keep = v_keep;
-    g.nt_local_sums = local_sums ? 1 : 0;
-    if (mode && z.p) { g.Z = z; g.z_lo = 0; g.z_hi = Nc; }
-    if (stats_rows) *stats_rows = 0;
-    if (stats && stats_rows && !mode) {
-        const int dtype = cx ? cx->dtype : afi_default_dtype();
-        const bool f4 = fwd_f4 && wino_f4(cx) && dtype != AFI_DTYPE_BF16 && (long long)N * H * W >= 8192;     // (the tiling wino_run will pick)
-        const long long T = f4 ? (long long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long long)N * ((H + 1) / 2) * ((W + 1) / 2);
-        const int rows = afi_wino_stats_rows(T, Nc);
-        if (rows > 0) { g.stats = stats; g.stats_mm = stats_mm; *stats_rows = rows; }
+    const bool dgrad = kind == kWinoDgrad;
+    AfiPixGemm g = dgrad ? conv_dgrad_desc(in, N, H, W, K, w, Nc, out) : conv_fwd_desc(in, N, H, W, K, w, bias, Nc, out);
+    if (o.in_bn) g.a_bn = *o.in_bn;
+    g.a_amax = o.in_amax; g.a_amax_known = o.in_amax_known ? 1 : 0;
+    g.v_keep = o.v_keep;
+    g.nt_local_sums = o.local_sums ? 1 : 0;
+    if (dgrad && z.p) { g.Z = z; g.z_lo = 0; g.z_hi = Nc; }
+    const WinoForm f = wino_form(cx, g, dgrad, kind == kWinoFwdF4);
+    const int rows = afi_wino_stats_rows(f.T, Nc);
+    if (o.stats_rows) *o.stats_rows = 0;
+    if (o.stats && o.stats_rows && !dgrad && rows > 0) { g.stats = o.stats; g.stats_mm = o.stats_mm; *o.stats_rows = rows; }
+    if (o.bsums_rows) *o.bsums_rows = 0;
+    if (o.bsums && o.bsums_rows && dgrad && o.bsums->rows && !z.p && rows > 0) {
+        g.bstats = o.bsums->rows; g.bstats_c = o.bsums->c; g.bstats_bn = o.bsums->bn; g.bstats_slope = o.bsums->slope; *o.bsums_rows = rows;
     }
-    if (bsums_rows) *bsums_rows = 0;
-    if (bsums && bsums_rows && mode && bsums->rows && !z.p) {   // the BatchNorm-backward sums of the gradient this call writes, by its output transform
-        const int dtype = cx ? cx->dtype : afi_default_dtype();
-        const bool f4 = wino_f4(cx) && dtype != AFI_DTYPE_BF16 && (long long)N * H * W >= 8192;               // (the tiling wino_run will pick)
-        const long long T = f4 ? (long long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long long)N * ((H + 1) / 2) * ((W + 1) / 2);
-        const int rows = afi_wino_stats_rows(T, Nc);
-        if (rows > 0) { g.bstats = bsums->rows; g.bstats_c = bsums->c; g.bstats_bn = bsums->bn; g.bstats_slope = bsums->slope; *bsums_rows = rows; }
-    }
-    return wino_run(cx, g, mode, ws, ws_floats, part, part_floats, st, fwd_f4);
+    return wino_run(cx, g, f, ws, ws_floats, part, part_floats, st);
 }
 
 // Caller-owned accumulator for the transform-domain weight gradients (afi_ctx_set_wino_wgrad_accum): dW = A'^T dU A' is linear in dU,
@@ -604,37 +630,39 @@ static float* wino_wgacc_slot(afi_ctx* cx, float* dw, int f4, int O, int I, floa
 // dy_phases = 4: dy is the hi-res gradient of a 4-phase conv-transpose; its phase views fill the four channel blocks of Q and
 // dw is the packed weight gradient [4*CoutPhase][3][3][Cin] (Cout = 4*CoutPhase).  accumulate = false keeps the call out of the
 // phase accumulator (its dw is a per-call scratch that is unpacked right away).
-// x_bn: x is read through a BatchNorm affine + LeakyReLU (AfiBnLoad)
+// what a whole-net call adds to a plain Winograd weight gradient (wino_wgrad); every member is optional
+struct WinoWgradOpt {
+    int dy_phases = 1; bool accumulate = true;
+    const AfiBnLoad* x_bn = nullptr;    // x is read through a BatchNorm affine + LeakyReLU (AfiBnLoad)
+    // f16x3: the largest magnitudes of the two source tensors where their producers published them: both transforms then write their planes
+    // already split into fp16 pieces and the GEMM stages them by DMA alone; otherwise the transforms raise two slots of the pool
+    const float* dy_amax = nullptr; const float* x_amax = nullptr;
+    const float* v_have = nullptr;      // the forward of this conv kept its input planes (WinoForm::keep), split with the very bound used here (x_amax)
+};
 static int wino_wgrad(afi_ctx* cx, AfiView dy, AfiView x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, float* ws, long long ws_floats,
-                      hipStream_t st, int dy_phases = 1, bool accumulate = true, const AfiBnLoad* x_bn = nullptr, const float* dy_amax = nullptr,
-                      const float* x_amax = nullptr, const float* v_have = nullptr) {
+                      hipStream_t st, const WinoWgradOpt& o = WinoWgradOpt()) {
     if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
     if (ws_floats < wino_ws_floats(N, H, W, Cin, Cout)) return AFI_ERR_WORKSPACE;
-    const int dtype = cx ? cx->dtype : afi_default_dtype();
-    const bool f4 = wino_f4(cx) && dtype != AFI_DTYPE_BF16 && (long long)N * H * W >= 8192;   // F(3x3,4x4): 36 transform points over 4x4 blocks of dY
-    const int np = f4 ? 36 : 16;
-    const long long Tpad = f4 ? wino4_tpad(N, H, W) : wino_tpad(N, H, W);
+    const int dy_phases = o.dy_phases;
+    const WinoForm f = wino_form(cx, N, H, W, Cin, Cout, kWinoWgrad, dy_phases);     // F(3x3,4x4): 36 transform points over 4x4 blocks of dY
+    const int dtype = f.dtype, np = f.np; const long long Tpad = f.Tpad;
+    const bool f4 = f.f4, f16 = f.f16;
     float* dU = ws;
     float* Vb = dU + align4((long long)np * Cin * Cout);
     float* Qb = Vb + align4(np * Tpad * Cin);
-    const bool f16 = dtype == AFI_DTYPE_F16X3 && !(Tpad % 32) && !(Cout % 128) && !(Cin % 128);
     float* amax = nullptr;                                 // f16x3: [0] the largest magnitude of x, [4] of dy, raised by their transforms
     bool fresh = true, accum = false;
-    if (accumulate)
+    if (o.accumulate)
         if (float* slot = wino_wgacc_slot(cx, dw, f4, Cout, Cin, alpha, align4((long long)np * Cin * Cout), fresh)) { dU = slot; accum = true; }
     if (fresh && hipMemsetAsync(dU, 0, sizeof(float) * np * (size_t)Cin * Cout, st) != hipSuccess) return AFI_ERR_LAUNCH;
-    // dy_amax, x_amax (f16x3): the largest magnitudes of the two source tensors where their producers published them: both transforms then
-    // write their planes already split into fp16 pieces and the GEMM stages them by DMA alone; otherwise the transforms raise two slots of the pool
-    const bool pre = afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && f16 && dy_amax && x_amax && dy_phases == 1;
-    const bool known = f16 && dy_amax && x_amax;           // (known but not split: the in-register kernel with the known maxima; nothing is raised)
+    const bool known = f16 && o.dy_amax && o.x_amax;       // (known but not split: the in-register kernel with the known maxima; nothing is raised)
+    const bool pre = f.presplit && known;
     if (f16 && !known && !(amax = wino_amax_take(cx, ws, ws_floats, 2, st))) return AFI_ERR_LAUNCH;
-    const AfiF16Bound vbound = afi_f16_bound(known ? x_amax : amax, f4 ? 2 : 1), qbound = afi_f16_bound(known ? dy_amax : amax + 4, f4 ? 4 : 3);
-    // v_have: the forward of this conv kept its F(4x4) input planes, split with the very bound used here (x_amax): nothing to transform
-    if (v_have && f4 && pre) Vb = (float*)v_have;
-    else if (v_have) return AFI_ERR_BAD_ARG;               // (the caller's predicate and this function's disagree: never read planes that were not written)
-    else
-    AFI_TRY(f4 ? afi_launch_wino4_input(x, N, H, W, Cin, Tpad, Vb, st, 0, x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr)
-               : afi_launch_wino_input(x, N, H, W, Cin, Tpad, Vb, st, 0, x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr));
+    const AfiF16Bound vbound = afi_f16_bound(known ? o.x_amax : amax, f4 ? 2 : 1), qbound = afi_f16_bound(known ? o.dy_amax : amax + 4, f4 ? 4 : 3);
+    if (o.v_have && !(f.keep && pre)) return AFI_ERR_BAD_ARG;      // (never read planes that were not written pre-split)
+    if (o.v_have) Vb = (float*)o.v_have;
+    else AFI_TRY(f4 ? afi_launch_wino4_input(x, N, H, W, Cin, Tpad, Vb, st, 0, o.x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr)
+                    : afi_launch_wino_input(x, N, H, W, Cin, Tpad, Vb, st, 0, o.x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr));
     const int cph = Cout / dy_phases;
     for (int ph = 0; ph < dy_phases; ++ph) {
         AfiView d = dy;
@@ -666,13 +694,6 @@ static int wino_wgrad(afi_ctx* cx, AfiView dy, AfiView x, int N, int H, int W, i
     return f4 ? afi_launch_wino4_dw(dU, dw, Cout, Cin, alpha, st) : afi_launch_wino_dw(dU, dw, Cout, Cin, alpha, st);
 }
 
-// Winograd or direct for a 3x3 conv of the discriminator: from ~1 K pixels on the 2.25x fewer matrix-core FLOPs win over the
-// transform traffic (measured: 2x336x200 1024->1024 18.8 -> 11.8 ms, 2x84x50 1.38 -> 0.72 ms).  AFI_OPT_WINOGRAD = 0 switches it off,
-// AFI_OPT_D_WINOGRAD_MIN_PIXELS moves the threshold (not below the 1024 pixels the workspace queries size the scratch from).
-static bool use_wino(const afi_ctx* cx, long long P) {
-    const long long minpix = afi_opt(cx, AFI_OPT_D_WINOGRAD_MIN_PIXELS);
-    return afi_opt(cx, AFI_OPT_WINOGRAD) && P >= (minpix < 1024 ? 1024 : minpix);
-}
 static long long disc_wino_floats(const int F[4], int N, int H, int W) {
     if ((long long)N * H * W < 1024) return 0;
     long long m = 0;
@@ -890,7 +911,7 @@ int afi_conv3x3_wino_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int 
     afi_ctx* cx = ctx; (void)cx;
     AFI_CTX_CHECK(ctx);
     if (N <= 0 || H <= 0 || W <= 0 || !ws) return AFI_ERR_BAD_ARG;
-    return wino_conv(cx, 0, V(x), N, H, W, Cin, w, Cout, bias, V(out), null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
+    return wino_conv(cx, kWinoFwd, V(x), N, H, W, Cin, w, Cout, bias, V(out), null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
 }
 int afi_conv3x3_wino_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, afi_view_t out,
                                int out_dtype, float* ws, long long ws_floats, void* stream) {
@@ -901,7 +922,7 @@ int afi_conv3x3_wino_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W
     if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
     AfiPixGemm g = conv_fwd_desc(V(x), N, H, W, Cin, w, bias, Cout, V(out));
     g.o_dtype = out_dtype;
-    return wino_run(cx, g, 0, ws, ws_floats, nullptr, 0, (hipStream_t)stream);
+    return wino_run(cx, g, wino_form(cx, g, 0), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
 }
 int afi_conv3x3_wino_infer(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, afi_view_t out, int act,
                            float* ws, long long ws_floats, void* stream) {
@@ -911,14 +932,14 @@ int afi_conv3x3_wino_infer(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, in
     if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
     AfiPixGemm g = conv_fwd_desc(V(x), N, H, W, Cin, w, bias, Cout, V(out));
     g.lrelu = act;
-    return wino_run(cx, g, 0, ws, ws_floats, nullptr, 0, (hipStream_t)stream, /*fwd_f4=*/true);
+    return wino_run(cx, g, wino_form(cx, g, 0, /*fwd_f4=*/true), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
 }
 int afi_conv3x3_wino_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, afi_view_t z, float* ws,
                            long long ws_floats, void* stream) {
     afi_ctx* cx = ctx; (void)cx;
     AFI_CTX_CHECK(ctx);
     if (N <= 0 || H <= 0 || W <= 0 || !ws) return AFI_ERR_BAD_ARG;
-    return wino_conv(cx, 1, V(dy), N, H, W, Cout, w, Cin, nullptr, V(dx), z.p ? V(z) : null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
+    return wino_conv(cx, kWinoDgrad, V(dy), N, H, W, Cout, w, Cin, nullptr, V(dx), z.p ? V(z) : null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream);
 }
 
 int afi_conv3x3_wino_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, float* ws,
@@ -1272,7 +1293,7 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
     const long long part_n_ = l.n_part;
     auto PG = [&](AfiPixGemm g, int b_rc) {
         // (value 16 of AFI_OPT_WINOGRAD_F4_FORWARD: the interpolator's own forwards on F(4x4) as well -- measured, off: DESIGN.md 9)
-        if (!g.Bimg && l.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, b_rc, ws + l.o_wino, l.n_wino, part_, part_n_, st, (afi_opt(cx, AFI_OPT_WINOGRAD_F4_FORWARD) & 16) != 0);
+        if (!g.Bimg && l.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, wino_form(cx, g, b_rc, (afi_opt(cx, AFI_OPT_WINOGRAD_F4_FORWARD) & 16) != 0), ws + l.o_wino, l.n_wino, part_, part_n_, st);
         g.partial = part_; g.partial_floats = part_n_;
         return afi_launch_pix_gemm(g, b_rc, st);
     };
@@ -1492,7 +1513,7 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
     float* const part_ = scratch + s.o_part;
     const long long part_n_ = s.n_part;
     auto PG = [&](AfiPixGemm g, int b_rc) {
-        if (!g.Bimg && s.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, b_rc, scratch + s.o_wino, s.n_wino, part_, part_n_, st);
+        if (!g.Bimg && s.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, wino_form(cx, g, b_rc), scratch + s.o_wino, s.n_wino, part_, part_n_, st);
         g.partial = part_; g.partial_floats = part_n_;
         return afi_launch_pix_gemm(g, b_rc, st);
     };
@@ -1631,7 +1652,9 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
             AFI_TRY(defer(convT_wgrad_desc(dU, a7, N, H, W, C, C, dwp, 1.f)));
             n_wide_has_convT = true; unpack_pending = true;
         } else if (s.n_wino > 0 && C >= 128 && P >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD)) {    // the four phases as channel blocks of one Winograd weight gradient
-            AFI_TRY(wino_wgrad(cx, dU, a7, N, H, W, 4 * C, C, dwp, 1.f, scratch + s.o_wino2, s.n_wino, sd, /*dy_phases=*/4, /*accumulate=*/false));
+            WinoWgradOpt o;
+            o.dy_phases = 4; o.accumulate = false;
+            AFI_TRY(wino_wgrad(cx, dU, a7, N, H, W, 4 * C, C, dwp, 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
         } else {
             AFI_TRY(wgrad_launch(cx, convT_wgrad_desc(dU, a7, N, H, W, C, C, dwp, 1.f), sd));
         }
@@ -1777,7 +1800,9 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
             const AfiView dy4 = ch_off(d, C);
             const bool wino_ok = s.n_wino > 0 && 4 * G >= 128 && L >= 128 && P >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD) &&
                                  s.n_wino >= wino_ws_floats(N, H, W, L, 4 * G);
-            if (wino_ok) AFI_TRY(wino_wgrad(cx, dy4, b, N, H, W, 4 * G, L, packed, 1.f, scratch + s.o_wino2, s.n_wino, sd, /*dy_phases=*/1, /*accumulate=*/false));
+            WinoWgradOpt o;
+            o.accumulate = false;
+            if (wino_ok) AFI_TRY(wino_wgrad(cx, dy4, b, N, H, W, 4 * G, L, packed, 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
             else AFI_TRY(wgrad_launch(cx, conv_wgrad_desc(dy4, b, N, H, W, 4 * G, L, packed, 1.f), sd));
             float* const dws[4] = {gr->rdb_w[r][0], gr->rdb_w[r][1], gr->rdb_w[r][2], gr->rdb_w[r][3]};
             AFI_TRY(afi_launch_rdb_wgrad_unpack(packed, dws, C, G, 1.f, sd));
@@ -1807,17 +1832,13 @@ struct DiscWs {
     long long P;
     long long o_c[3], o_y[3], o_d9, o_mean[3], o_invstd[3], o_red, o_stats, o_stats_mm, o_amax, o_part, n_part, o_wino, n_wino, o_mean_b[3], o_invstd_b[3], o_vkeep[3], total;
 };
-// AFI_OPT_D_FUSE_TAIL in force for a discriminator of F3 last-block channels: block 2's apply pass, the last conv and their backward run as the
-// fused passes of csrc/elementwise.hip (afi_launch_disc_tail_*): y[2] and the gradient with respect to it are never written.  Evaluated by
-// the forward AND the backward (one more reason afi_discriminator_bwd runs under its forward's options).
-static bool disc_tail_fused(const afi_ctx* cx, int F3) { return afi_opt(cx, AFI_OPT_D_FUSE_TAIL) != 0 && !(F3 & 15) && F3 <= 1024; }
-// keep_mask: bit n reserves the kept F(4x4) input planes of block n (disc_v_shared).  The planes sit at the END of the layout, so every other
-// offset is the same under every mask; the context-free size query reserves both (an upper bound every context's call fits into), the
-// context-aware one (afi_discriminator_fwd_ws_floats_ex) and the two passes what disc_keep_mask says (an fp32 / bf16x6 context, a
+// keep_mask: bit n reserves the kept F(4x4) input planes of block n (DiscPlan::Block::keep).  The planes sit at the END of the layout, so every other
+// offset is the same under every mask; the context-free queries reserve them wherever some context could keep them (disc_ws_bound), the
+// context-aware one (afi_discriminator_fwd_ws_floats_ex) and the two passes where the plan keeps them (an fp32 / bf16x6 context, a
 // forward no backward follows and the F(2x2) blocks paid 0.6 + 1.25 GB per workspace at P2 for planes nobody writes)
 // y2: reserve the last block's activation (P x F3 floats, the largest tensor of the network): not under AFI_OPT_D_FUSE_TAIL, where nobody writes
 // it.  It sits behind every fixed region (its offset is the same either way: afi_discriminator_ws_layout is context-free) and in front of the kept planes.
-static DiscWs disc_ws(const int F[4], int N, int H, int W, int keep_mask = 6, bool y2 = true) {
+static DiscWs disc_ws(const int F[4], int N, int H, int W, int keep_mask, bool y2) {
     DiscWs w;
     w.P = (long long)N * H * W;
     long long o = 0;
@@ -1846,34 +1867,15 @@ static DiscWs disc_ws(const int F[4], int N, int H, int W, int keep_mask = 6, bo
     }
     w.o_y[2] = o;
     if (y2) o += align4(w.P * F[3]);
-    // the F(4x4) input planes of blocks 1 and 2, kept by a forward that a backward follows for that block's weight gradient (disc_v_shared)
     for (int n = 0; n < 3; ++n) {
         w.o_vkeep[n] = o;
-        if (n > 0 && ((keep_mask >> n) & 1) && w.P >= 8192 && w.n_wino > 0) o += align4(36 * wino4_tpad(N, H, W) * F[n]);
+        if ((keep_mask >> n) & 1) o += align4(36 * wino4_tpad(N, H, W) * F[n]);
     }
     w.total = o;
     return w;
 }
-long long afi_discriminator_fwd_ws_floats(const int F[4], int N, int H, int W) { return disc_ws(F, N, H, W).total; }
-static int disc_keep_mask(const afi_ctx* cx, const int F[4], int N, int H, int W, int training, int halves);
-long long afi_discriminator_fwd_ws_floats_ex(const afi_ctx_t* ctx, const int F[4], int N, int H, int W, int training) {
-    if (!F || N <= 0 || H <= 0 || W <= 0) return 0;
-    return disc_ws(F, N, H, W, disc_keep_mask(ctx, F, N, H, W, training, 1) | disc_keep_mask(ctx, F, N, H, W, training, 2), !disc_tail_fused(ctx, F[3])).total;     // (plain or paired call)
-}
-// where the forward keeps what the backward reads (offsets in floats into the forward workspace): 12 entries,
-// conv outputs c[0..2] ([P][F_{n+1}]), activations y[0..2], batch means [F_{n+1}], 1/sqrt(var + eps) [F_{n+1}]
-int afi_discriminator_ws_layout(const int F[4], int N, int H, int W, long long* off12) {
-    if (!F || !off12 || N <= 0 || H <= 0 || W <= 0) return AFI_ERR_BAD_ARG;
-    const DiscWs l = disc_ws(F, N, H, W);
-    for (int n = 0; n < 3; ++n) { off12[n] = l.o_c[n]; off12[3 + n] = l.o_y[n]; off12[6 + n] = l.o_mean[n]; off12[9 + n] = l.o_invstd[n]; }
-    return AFI_OK;
-}
-int afi_discriminator_saved_activations(const afi_ctx_t* ctx, const int F[4], int N, int H, int W) {
-    if (!F || N <= 0 || H <= 0 || W <= 0) return -1;
-    const DiscWs l = disc_ws(F, N, H, W);
-    const int tail = disc_tail_fused(ctx, F[3]) ? 0 : 4;     // (y[2]: read by the last conv only)
-    return ((l.n_wino > 0 && use_wino(ctx, l.P) && afi_opt(ctx, AFI_OPT_D_FOLD_BN_APPLY) != 0) ? 0 : 3) | tail;
-}
+// blocks 1 and 2 (the only ones that keep planes) wherever their form can be F(4x4), and y2
+static DiscWs disc_ws_bound(const int F[4], int N, int H, int W) { return disc_ws(F, N, H, W, (long long)N * H * W >= kWinoF4MinPixels ? 6 : 0, true); }
 struct DiscBwdWs { long long o_g[3], o_dd9, o_amax, o_red, o_red2, o_tail, o_bsums, o_part, n_part, o_wino, n_wino, o_wino2, total; };
 static DiscBwdWs disc_bwd_ws(const int F[4], int N, int H, int W) {
     DiscBwdWs w;
@@ -1896,35 +1898,96 @@ static DiscBwdWs disc_bwd_ws(const int F[4], int N, int H, int W) {
     w.total = o;
     return w;
 }
-long long afi_discriminator_bwd_ws_floats(const int F[4], int N, int H, int W) { return disc_bwd_ws(F, N, H, W).total; }
 
-// Does the forward (training == 1) of block n keep its input planes for the backward's weight gradient?  Evaluated by BOTH passes, which is why
-// afi_discriminator_bwd must run under the options and the arithmetic of its forward: F(4x4) forward in that block, f16x3 with pre-split planes
-// (the block's input maximum is known before its transform runs: blocks 1 and 2), channel counts the DMA GEMMs take
-static bool disc_fold_opt(const afi_ctx* cx, bool wino, int halves) {
-    // AFI_OPT_D_FOLD_BN_APPLY in force for this call: Winograd form, and ONE affine per tensor (a paired call normalises its halves separately:
-    // it runs unfolded, whatever the option says)
-    return wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FOLD_BN_APPLY) != 0;
-}
-static bool disc_stats_fusable(const afi_ctx* cx, int C) { return afi_opt(cx, AFI_OPT_BN_STATS_FP64) != 0 && (C == 256 || C == 512 || C == 1024); }
-static bool disc_v_shared(const afi_ctx* cx, const int F[4], int n, long long P, bool wino, int halves = 1) {
+// Everything a discriminator call decides.  A forward (training as afi_discriminator_fwd's) and the backward that follows it (training == 1) build
+// their plan from the same context, shape and pairing, which is why afi_discriminator_bwd must run under the options and the arithmetic of its
+// forward: the backward reads the layout and the kept planes this plan says the forward wrote.
+struct DiscPlan {
+    // the three 3x3 convs in Winograd form: from ~1 K pixels on the 2.25x fewer matrix-core FLOPs win over the transform traffic (measured:
+    // 2x336x200 1024->1024 18.8 -> 11.8 ms, 2x84x50 1.38 -> 0.72 ms).  AFI_OPT_WINOGRAD = 0 switches it off, AFI_OPT_D_WINOGRAD_MIN_PIXELS moves
+    // the threshold (not below the 1024 pixels the workspace queries size the scratch from)
+    bool wino;
+    // AFI_OPT_D_FUSE_TAIL in force for F3 last-block channels: block 2's apply pass, the last conv and their backward run as the fused passes of
+    // csrc/elementwise.hip (afi_launch_disc_tail_*): y[2] and the gradient with respect to it are never written
+    bool tail;
+    // AFI_OPT_D_FOLD_BN_APPLY in force (off by default: measured slower, include/afigan_hip.h): Winograd form and ONE affine per tensor (a paired
+    // call normalises its halves separately: it runs unfolded).  The activation of blocks 0 and 1 is never written -- the next block's input
+    // transform reads the saved conv output through the block's BatchNorm affine + LeakyReLU (AfiBnLoad: the arithmetic of the apply pass, bit
+    // for bit), and so do the backward's weight-gradient input transforms.  Block 2's activation feeds the last conv and is always written.
+    bool fold;
+    // the forward leaves every block input's largest magnitude in DiscWs::o_amax, whatever arithmetic it runs in (the backward trusts the slots):
+    // x's by the first input transform; y0's / y1's by the BatchNorm apply passes, or -- folded apply pass -- by the statistics finalizer, from
+    // the conv output's per-channel extremes; where neither exists (an eval-mode folded call) by the transform that reads it
+    bool fwd_amax;
+    // the backward (f16x3) raises the largest magnitude of every d(conv output) into DiscBwdWs::o_amax, by the BatchNorm backward that writes it:
+    // with the forward's slots every Winograd transform of the pass knows its source's maximum beforehand and writes its planes pre-split
+    bool bwd_amax;
+    // x comes from outside the library: where block 0's GEMM is to take the k-step-local sums its maximum is measured first, one streaming pass
+    // over x (137 MB, ~30 us at 2x200x336).  This test asks less than block 0's form (F[0] % 32 == 0 but not WinoForm::presplit's F[1] % 128):
+    // it is the one that governs, so at F0 = 32 x is measured although block 0's planes are not written pre-split
+    bool x_amax;
+    // AFI_OPT_D_FUSE_BWD_SUMS (off: measured, no gain): the data gradient of block n + 1 leaves the BatchNorm-backward sums of block n beside the
+    // gradient it writes (one affine per tensor: not a paired call)
+    bool fuse_bsums;
+    struct Block {
+        WinoForm fwd, wgrad;   // the forms of the block's forward conv and of its weight gradient
+        bool local_sums;       // AFI_OPT_F16_LOCAL_SUMS: the forward's GEMM takes k-step-local sums
+        bool stats;            // the forward's output transform accumulates the BatchNorm statistics (training, one affine per tensor, shapes it takes)
+        // the forward keeps its input planes for the backward's weight gradient: both forms keep, and the input's maximum is known before its
+        // transform runs (blocks 1 and 2; under the folded apply pass the previous block's statistics -- with them the conv output's extremes --
+        // must be fused into its output transform).  The weight gradient's channel test governs: F[n] % 128 == 0, where the forward's form asks
+        // F[n] % 32 == 0 (at F0 = 32 block 1 keeps nothing)
+        bool keep;
+    } b[3];
+    DiscWs ws;        // the forward's layout: planes reserved where a plain OR a paired call of this training mode keeps them
+    DiscBwdWs bws;
+};
+static DiscPlan disc_plan(const afi_ctx* cx, const int F[4], int N, int H, int W, int training, int halves) {
+    DiscPlan p;
+    const long long minpix = afi_opt(cx, AFI_OPT_D_WINOGRAD_MIN_PIXELS);
+    p.wino = disc_wino_floats(F, N, H, W) > 0 && afi_opt(cx, AFI_OPT_WINOGRAD) && (long long)N * H * W >= (minpix < 1024 ? 1024 : minpix);
+    p.tail = afi_opt(cx, AFI_OPT_D_FUSE_TAIL) != 0 && !(F[3] & 15) && F[3] <= 1024;
+    p.fold = p.wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FOLD_BN_APPLY) != 0;
     const int dtype = cx ? cx->dtype : afi_default_dtype();
-    // (under the folded apply pass the input's maximum is known beforehand only where the producing block's statistics -- and with them the
-    //  conv output's extremes -- were fused into its output transform: a training forward, which is the only kind that keeps planes)
-    const bool known = !disc_fold_opt(cx, wino, halves) || disc_stats_fusable(cx, F[n]);
-    return wino && n > 0 && wino_d_f4(cx, n) && wino_f4(cx) && dtype == AFI_DTYPE_F16X3 && P >= 8192 && afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 &&
-           known && !(F[n] % 128) && !(F[n + 1] % 128);
+    p.fwd_amax = p.wino;
+    p.bwd_amax = p.wino && dtype == AFI_DTYPE_F16X3;
+    p.x_amax = p.wino && training == 1 && disc_local_sums(cx, 0) && dtype == AFI_DTYPE_F16X3 && afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && !(F[0] & 31);
+    p.fuse_bsums = p.wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FUSE_BWD_SUMS) != 0;
+    int keep_mask = 0;
+    for (int n = 0; n < 3; ++n) {
+        DiscPlan::Block& b = p.b[n];
+        b.fwd = wino_form(cx, N, H, W, F[n], F[n + 1], training != 1 || wino_d_f4(cx, n) ? kWinoFwdF4 : kWinoFwd);
+        b.wgrad = wino_form(cx, N, H, W, F[n], F[n + 1], kWinoWgrad);
+        b.local_sums = training == 1 && disc_local_sums(cx, n);
+        b.stats = p.wino && training && halves == 1 && afi_opt(cx, AFI_OPT_BN_STATS_FP64) != 0 && afi_wino_stats_rows(b.fwd.T, F[n + 1]) > 0;
+        const bool can_keep = n > 0 && training == 1 && p.wino && b.fwd.keep && b.wgrad.keep;
+        b.keep = can_keep && (!p.fold || p.b[n - 1].stats);
+        if (can_keep) keep_mask |= 1 << n;               // (a paired call never folds: it keeps wherever the forms allow)
+    }
+    p.ws = disc_ws(F, N, H, W, keep_mask, !p.tail);
+    p.bws = disc_bwd_ws(F, N, H, W);
+    return p;
 }
 
-// the blocks whose planes a forward of this context keeps (training == 1 only: the other forwards feed no backward)
-static int disc_keep_mask(const afi_ctx* cx, const int F[4], int N, int H, int W, int training, int halves = 1) {
-    if (training != 1) return 0;
-    const long long P = (long long)N * H * W;
-    const bool wino = disc_wino_floats(F, N, H, W) > 0 && use_wino(cx, P);
-    int m = 0;
-    for (int n = 1; n < 3; ++n) if (disc_v_shared(cx, F, n, P, wino, halves)) m |= 1 << n;
-    return m;
+long long afi_discriminator_fwd_ws_floats(const int F[4], int N, int H, int W) { return disc_ws_bound(F, N, H, W).total; }
+long long afi_discriminator_fwd_ws_floats_ex(const afi_ctx_t* ctx, const int F[4], int N, int H, int W, int training) {
+    if (!F || N <= 0 || H <= 0 || W <= 0) return 0;
+    return disc_plan(ctx, F, N, H, W, training, 1).ws.total;     // (plain or paired call)
 }
+// where the forward keeps what the backward reads (offsets in floats into the forward workspace, the same in every plan's layout): 12 entries,
+// conv outputs c[0..2] ([P][F_{n+1}]), activations y[0..2], batch means [F_{n+1}], 1/sqrt(var + eps) [F_{n+1}]
+int afi_discriminator_ws_layout(const int F[4], int N, int H, int W, long long* off12) {
+    if (!F || !off12 || N <= 0 || H <= 0 || W <= 0) return AFI_ERR_BAD_ARG;
+    const DiscWs l = disc_ws_bound(F, N, H, W);
+    for (int n = 0; n < 3; ++n) { off12[n] = l.o_c[n]; off12[3 + n] = l.o_y[n]; off12[6 + n] = l.o_mean[n]; off12[9 + n] = l.o_invstd[n]; }
+    return AFI_OK;
+}
+int afi_discriminator_saved_activations(const afi_ctx_t* ctx, const int F[4], int N, int H, int W) {
+    if (!F || N <= 0 || H <= 0 || W <= 0) return -1;
+    const DiscPlan p = disc_plan(ctx, F, N, H, W, 1, 1);
+    return (p.fold ? 0 : 3) | (p.tail ? 0 : 4);            // (y[2]: read by the last conv only)
+}
+long long afi_discriminator_bwd_ws_floats(const int F[4], int N, int H, int W) { return disc_bwd_ws(F, N, H, W).total; }
 
 static int disc_check(const afi_disc_params_t* p) {
     if (!p) return AFI_ERR_BAD_ARG;
@@ -1947,10 +2010,9 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
     AFI_TRY(disc_check(prm));
     const bool stats_only = training == 3;                 // BatchNorm side effects only: no last activation, last conv or logits
     if (N <= 0 || H <= 0 || W <= 0 || !ws || !xv.p || (!logits && !stats_only)) return AFI_ERR_BAD_ARG;
-    if (halves != 1 && halves != 2) return AFI_ERR_BAD_ARG;
-    if (N % halves) return AFI_ERR_BAD_ARG;
-    // (the layout afi_discriminator_fwd_ws_floats_ex sizes)
-    const DiscWs l = disc_ws(prm->F, N, H, W, disc_keep_mask(cx, prm->F, N, H, W, training, 1) | disc_keep_mask(cx, prm->F, N, H, W, training, 2), !disc_tail_fused(cx, prm->F[3]));
+    if ((halves != 1 && halves != 2) || N % halves) return AFI_ERR_BAD_ARG;
+    const DiscPlan pl = disc_plan(cx, prm->F, N, H, W, training, halves);
+    const DiscWs& l = pl.ws;                               // (the layout afi_discriminator_fwd_ws_floats_ex sizes)
     if (ws_floats < l.total) return AFI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* const part_ = ws + l.o_part;
@@ -1959,27 +2021,13 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
     const long long P = l.P;
     float* red = ws + l.o_red;
     AfiView in = V(xv);
-    // AFI_OPT_D_FOLD_BN_APPLY (off by default: measured slower, include/afigan_hip.h): under the Winograd path the activation of blocks 0 and 1
-    // is never written -- the next block's input transform reads the saved conv output through the block's BatchNorm affine + LeakyReLU
-    // (AfiBnLoad: the arithmetic of the apply pass, bit for bit), and so do the backward's weight-gradient input transforms.  Block 2's
-    // activation feeds the last conv (a direct GEMM) and is always written.
-    const bool wino = l.n_wino > 0 && use_wino(cx, P);
-    const bool fold = disc_fold_opt(cx, wino, halves);     // (a paired call runs unfolded: one affine per HALF there)
-    const bool tail = disc_tail_fused(cx, prm->F[3]);
+    const bool wino = pl.wino, fold = pl.fold, tail = pl.tail;
     const long long Ph = P / halves;
     AfiBnLoad in_bn{nullptr, nullptr, nullptr, nullptr};
-    // the largest magnitude of every block's input, for the f16x3 arithmetic of this pass and of the backward pass that may follow (whatever
-    // arithmetic THIS pass runs in: the backward trusts the slots): x's by the first input transform; y0's / y1's by the BatchNorm apply passes, or --
-    // where the apply pass is folded into the readers -- by the statistics finalizer, from the conv output's per-channel extremes (the exact
-    // maximum, before any kernel has evaluated the activation); where neither exists (an eval-mode folded call) by the transform that reads it
-    float* amax = ws + l.o_amax;
-    const bool slots = wino;
-    if (slots && hipMemsetAsync(amax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
+    float* amax = ws + l.o_amax;                            // (DiscPlan::fwd_amax)
+    if (pl.fwd_amax && hipMemsetAsync(amax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
     bool in_known = false;                                  // block n's input maximum is published before its transform runs
-    // the first block's input comes from outside the library: where its GEMM is to take the k-step-local sums (pre-split planes only) its
-    // maximum is measured first, one streaming pass over x (137 MB, ~30 us at 2x200x336)
-    if (slots && training == 1 && disc_local_sums(cx, 0) && (cx ? cx->dtype : afi_default_dtype()) == AFI_DTYPE_F16X3 &&
-        afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && !(prm->F[0] & 31)) {
+    if (pl.x_amax) {
         AFI_TRY(afi_launch_view_absmax(in, N, H, W, prm->F[0], amax, st));
         in_known = true;
     }
@@ -1987,17 +2035,20 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
         const int ci = prm->F[n], co = prm->F[n + 1];
         float* c = ws + l.o_c[n]; float* y = ws + l.o_y[n];
         float* mean = ws + l.o_mean[n]; float* invstd = ws + l.o_invstd[n];
+        const DiscPlan::Block& b = pl.b[n];
         int stats_rows = 0;
         double* stats = (double*)(ws + l.o_stats);          // (8-byte aligned: every offset of the layout is a multiple of 4 floats and ws comes from an allocator)
-        const bool fuse_stats = training && halves == 1 && afi_opt(cx, AFI_OPT_BN_STATS_FP64) != 0 && (((uintptr_t)stats) & 7) == 0;
+        const bool fuse_stats = b.stats && (((uintptr_t)stats) & 7) == 0;
         const bool fold_n = fold && n < 2;                  // this block's activation is never written: its readers evaluate it
         if (wino) {
-            const bool keep = training == 1 && slots && disc_v_shared(cx, prm->F, n, P, wino, halves);
-            if (keep && !in_known) return AFI_ERR_LAUNCH;   // (disc_v_shared promised a known maximum: never hand the backward planes this pass cannot split)
-            AFI_TRY(wino_conv(cx, 0, in, N, H, W, ci, prm->w[n], co, prm->b[n], dense_view(c, H, W, co), null_view(), ws + l.o_wino, l.n_wino, part_,
-                              part_n_, st, /*fwd_f4=*/training != 1 || wino_d_f4(cx, n), fuse_stats ? stats : nullptr, &stats_rows, in_bn.mean ? &in_bn : nullptr,
-                              slots ? amax + 4 * n : nullptr, /*known=*/in_known, keep ? ws + l.o_vkeep[n] : nullptr,
-                              fuse_stats && fold_n ? ws + l.o_stats_mm : nullptr, /*local_sums=*/training == 1 && disc_local_sums(cx, n)));
+            if (b.keep && !in_known) return AFI_ERR_LAUNCH; // (the plan promised a known maximum: never hand the backward planes this pass cannot split)
+            WinoConvOpt o;
+            if (fuse_stats) { o.stats = stats; o.stats_rows = &stats_rows; o.stats_mm = fold_n ? ws + l.o_stats_mm : nullptr; }
+            o.in_bn = in_bn.mean ? &in_bn : nullptr;
+            o.in_amax = pl.fwd_amax ? amax + 4 * n : nullptr; o.in_amax_known = in_known;
+            o.v_keep = b.keep ? ws + l.o_vkeep[n] : nullptr; o.local_sums = b.local_sums;
+            AFI_TRY(wino_conv(cx, b.fwd.kind, in, N, H, W, ci, prm->w[n], co, prm->b[n], dense_view(c, H, W, co), null_view(), ws + l.o_wino, l.n_wino, part_,
+                              part_n_, st, o));
         } else {
             AFI_TRY(PG(conv_fwd_desc(in, N, H, W, ci, prm->w[n], prm->b[n], co, dense_view(c, H, W, co)), 0));
         }
@@ -2016,7 +2067,7 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
             if (training && stats_rows > 0) {               // the output transform accumulated the sums while it stored c: only the finalizer is left
                 AFI_TRY(afi_launch_bn_stats_from_partials(stats, stats_rows, P, co, mean, invstd, nullptr, prm->running_mean[n], prm->running_var[n], st,
                                                           prm->num_batches_tracked[n]));
-                if (fold_n && slots) {                      // ... and, the apply pass being folded away, the activation's maximum from the extremes of c
+                if (fold_n && pl.fwd_amax) {                      // ... and, the apply pass being folded away, the activation's maximum from the extremes of c
                     AFI_TRY(afi_launch_bn_act_amax(ws + l.o_stats_mm, stats_rows, co, mean, invstd, prm->gamma[n], prm->beta[n], AFI_LRELU_SLOPE, amax + 4 * (n + 1), st));
                     in_known = true;
                 }
@@ -2026,8 +2077,8 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
             }
             if (!skip_apply) {
                 AFI_TRY(afi_launch_bn_apply_lrelu(ch, y + (long long)h * Ph * co, training ? mean_h : mean_used, training ? invstd_h : invstd, prm->gamma[n],
-                                                  prm->beta[n], Ph, co, st, AFI_LRELU_SLOPE, slots && n < 2 ? amax + 4 * (n + 1) : nullptr));
-                in_known = slots && n < 2;                  // (published by the pass that wrote the activation)
+                                                  prm->beta[n], Ph, co, st, AFI_LRELU_SLOPE, pl.fwd_amax && n < 2 ? amax + 4 * (n + 1) : nullptr));
+                in_known = pl.fwd_amax && n < 2;                 // (published by the pass that wrote the activation)
             }
         }
         if (fold_n) {
@@ -2067,9 +2118,9 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
     AFI_TRY(disc_check(prm));
     if (!gr || N <= 0 || H <= 0 || W <= 0 || !ws || !dlogits || !scratch) return AFI_ERR_BAD_ARG;
     if ((halves != 1 && halves != 2) || N % halves) return AFI_ERR_BAD_ARG;
-    // the layout its forward (training == 1, same context settings) wrote
-    const DiscWs l = disc_ws(prm->F, N, H, W, disc_keep_mask(cx, prm->F, N, H, W, 1, 1) | disc_keep_mask(cx, prm->F, N, H, W, 1, 2), !disc_tail_fused(cx, prm->F[3]));
-    const DiscBwdWs s = disc_bwd_ws(prm->F, N, H, W);
+    const DiscPlan pl = disc_plan(cx, prm->F, N, H, W, 1, halves);
+    const DiscWs& l = pl.ws;                               // the layout its forward (training == 1, same context settings) wrote
+    const DiscBwdWs& s = pl.bws;
     if (scratch_floats < s.total) return AFI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* const part_ = scratch + s.o_part;
@@ -2083,21 +2134,17 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
     //  two A/B pairs on one box -- the chip has no room left beside the GEMMs)
     Fork fk(cx, st, P <= kSideStreamMaxPixels);
     hipStream_t sd = fk.side;                              // weight / bias gradients run beside the data-gradient chain
-    const bool wino = s.n_wino > 0 && use_wino(cx, P);
+    const bool wino = pl.wino, fold = pl.fold, tail = pl.tail;
     const int F3 = prm->F[3];
-    // f16x3: the largest magnitude of every d(conv output), raised by the BatchNorm backward that writes it; with the forward's slots
-    // (DiscWs::o_amax) every Winograd transform of this pass knows its source's maximum beforehand and writes its planes split into fp16 pieces
-    float* gmax = scratch + s.o_amax;
-    // (folded apply pass or not: the forward left every block input's maximum in its slots either way)
-    const bool slots = wino && (cx ? cx->dtype : afi_default_dtype()) == AFI_DTYPE_F16X3;
-    const bool fold = disc_fold_opt(cx, wino, halves);
-    if (slots && hipMemsetAsync(gmax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
+    float* gmax = scratch + s.o_amax;                      // (DiscPlan::bwd_amax; folded apply pass or not, the forward filled its slots, xmax)
+    const bool bwd_amax = pl.bwd_amax;
+    if (bwd_amax && hipMemsetAsync(gmax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
     const float* xmax = ws + l.o_amax;
     // ---- last conv
     if (gr->b3) AFI_TRY(afi_launch_sum_accum(dlogits, P, 1.f, gr->b3, sd));
     AFI_TRY(afi_launch_stencil9_scatter(dlogits, dd9, 16, N, H, W, st));
     fk.after_main();                                       // dd9 is complete
-    const bool tail = disc_tail_fused(cx, F3);              // (the forward wrote no y2: its readers below are the fused passes)
+    // (under the fused tail the forward wrote no y2: its readers below are the fused passes)
     AfiView y2 = dense_view(ws + l.o_y[2], H, W, F3);
     if (gr->w3 && !tail) {
         AfiWgradGemm g = conv_wgrad_desc(dense_view(dd9, H, W, 16), y2, N, H, W, 9, F3, gr->w3, 1.f);
@@ -2112,9 +2159,7 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
         AFI_TRY(PG(g, 1));
     }
     // ---- conv + BN + LReLU blocks, last first
-    // AFI_OPT_D_FUSE_BWD_SUMS (off: measured, no gain): the data gradient of block n + 1 leaves the BatchNorm-backward sums of block n beside the
-    // gradient it writes (one affine per tensor: not a paired call)
-    const bool fuse_bsums = wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FUSE_BWD_SUMS) != 0 && (((uintptr_t)(scratch + s.o_bsums)) & 7) == 0;
+    const bool fuse_bsums = pl.fuse_bsums && (((uintptr_t)(scratch + s.o_bsums)) & 7) == 0;
     int bsums_rows = 0;                               // rows the previous iteration's data gradient left for THIS block (0: the separate pass)
     for (int n = 2; n >= 0; --n) {
         const int ci = prm->F[n], co = prm->F[n + 1];
@@ -2128,18 +2173,18 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
             if (n == 2 && tail) {                     // the gradient w.r.t. y2 is generated from dd9, the last conv's weight gradient rides with the sums
                 const AfiBnLoad bn{ws + (h ? l.o_mean_b[n] : l.o_mean[n]), ws + (h ? l.o_invstd_b[n] : l.o_invstd[n]), prm->gamma[n], prm->beta[n]};
                 AFI_TRY(afi_launch_disc_tail_bwd(c + o, dd9 + (long long)h * Ph * 16, bn, AFI_LRELU_SLOPE, prm->w3, g_ + o, gr->gamma[n], gr->beta[n], gr->w3, Ph, co,
-                                                 scratch + s.o_tail, slots ? gmax + 4 * n : nullptr, st));
+                                                 scratch + s.o_tail, bwd_amax ? gmax + 4 * n : nullptr, st));
                 continue;
             }
             if (bsums_rows > 0) {                     // (halves == 1) the sums came with g_: finalize + apply
                 AFI_TRY(afi_launch_bn_bwd_from_partials((const double*)(scratch + s.o_bsums), bsums_rows, g_, c, g_, ws + l.o_mean[n], ws + l.o_invstd[n], prm->gamma[n],
                                                         gr->gamma[n], gr->beta[n], 1.f, P, co, red, st, prm->beta[n],
-                                                        AFI_LRELU_SLOPE, slots ? gmax + 4 * n : nullptr));
+                                                        AFI_LRELU_SLOPE, bwd_amax ? gmax + 4 * n : nullptr));
                 continue;
             }
             AFI_TRY(afi_launch_bn_bwd(g_ + o, c + o, g_ + o, ws + (h ? l.o_mean_b[n] : l.o_mean[n]), ws + (h ? l.o_invstd_b[n] : l.o_invstd[n]), prm->gamma[n],
                                       gr->gamma[n], gr->beta[n], 1.f, Ph, co, red, st, prm->beta[n], AFI_LRELU_SLOPE,
-                                      slots ? gmax + 4 * n : nullptr));                                              // in place: g_ = d(conv output)
+                                      bwd_amax ? gmax + 4 * n : nullptr));                                              // in place: g_ = d(conv output)
         }
         fk.after_main();                              // g_ = d(conv output) is complete
         // d(loss)/d(bias) of a conv that feeds a train-mode BatchNorm is EXACTLY zero: g_ = BN backward's dx, whose sum over the pixels
@@ -2154,24 +2199,28 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
         AfiView xin = (n == 0) ? V(xv) : dense_view(ws + (xin_folded ? l.o_c[n - 1] : l.o_y[n - 1]), H, W, ci);
         AfiBnLoad x_bn{nullptr, nullptr, nullptr, nullptr};
         if (xin_folded) x_bn = AfiBnLoad{ws + l.o_mean[n - 1], ws + l.o_invstd[n - 1], prm->gamma[n - 1], prm->beta[n - 1]};
-        if (gr->w[n] && wino) AFI_TRY(wino_wgrad(cx, gy, xin, N, H, W, co, ci, gr->w[n], 1.f, scratch + s.o_wino2, s.n_wino, sd, 1, true, xin_folded ? &x_bn : nullptr,
-                                                 slots ? gmax + 4 * n : nullptr, slots ? xmax + 4 * n : nullptr,
-                                                 slots && disc_v_shared(cx, prm->F, n, P, wino, halves) ? ws + l.o_vkeep[n] : nullptr));
-        else if (gr->w[n]) AFI_TRY(wgrad_launch(cx, conv_wgrad_desc(gy, xin, N, H, W, co, ci, gr->w[n], 1.f), sd));
+        if (gr->w[n] && wino) {
+            WinoWgradOpt o;
+            o.x_bn = xin_folded ? &x_bn : nullptr;
+            if (bwd_amax) { o.dy_amax = gmax + 4 * n; o.x_amax = xmax + 4 * n; }
+            o.v_have = pl.b[n].keep ? ws + l.o_vkeep[n] : nullptr;
+            AFI_TRY(wino_wgrad(cx, gy, xin, N, H, W, co, ci, gr->w[n], 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
+        } else if (gr->w[n]) AFI_TRY(wgrad_launch(cx, conv_wgrad_desc(gy, xin, N, H, W, co, ci, gr->w[n], 1.f), sd));
         bsums_rows = 0;
-        if (n > 0 && wino) {
-            const AfiBwdSums bs{fuse_bsums ? (double*)(scratch + s.o_bsums) : nullptr, ws + l.o_c[n - 1],
+        float* gx = n > 0 ? scratch + s.o_g[n - 1] : dx;   // d(activation of block n - 1), or dx
+        if (gx && wino) {
+            WinoConvOpt o;
+            o.in_amax = bwd_amax ? gmax + 4 * n : nullptr; o.in_amax_known = true;
+            AfiBwdSums bs;
+            if (n > 0) {
+                bs = AfiBwdSums{fuse_bsums ? (double*)(scratch + s.o_bsums) : nullptr, ws + l.o_c[n - 1],
                                 AfiBnLoad{ws + l.o_mean[n - 1], ws + l.o_invstd[n - 1], prm->gamma[n - 1], prm->beta[n - 1]}, AFI_LRELU_SLOPE};
-            AFI_TRY(wino_conv(cx, 1, gy, N, H, W, co, prm->w[n], ci, nullptr, dense_view(scratch + s.o_g[n - 1], H, W, ci), null_view(), scratch + s.o_wino,
-                              s.n_wino, part_, part_n_, st, false, nullptr, nullptr, nullptr, slots ? gmax + 4 * n : nullptr, /*known=*/true, nullptr, nullptr, false,
-                              &bs, &bsums_rows));
-        } else if (n > 0) {
-            AFI_TRY(PG(conv_dgrad_desc(gy, N, H, W, co, prm->w[n], ci, dense_view(scratch + s.o_g[n - 1], H, W, ci)), 1));
-        } else if (dx && wino) {
-            AFI_TRY(wino_conv(cx, 1, gy, N, H, W, co, prm->w[n], ci, nullptr, dense_view(dx, H, W, ci), null_view(), scratch + s.o_wino, s.n_wino, part_,
-                              part_n_, st, false, nullptr, nullptr, nullptr, slots ? gmax + 4 * n : nullptr, /*known=*/true));
-        } else if (dx) {
-            AFI_TRY(PG(conv_dgrad_desc(gy, N, H, W, co, prm->w[n], ci, dense_view(dx, H, W, ci)), 1));
+                o.bsums = &bs; o.bsums_rows = &bsums_rows;
+            }
+            AFI_TRY(wino_conv(cx, kWinoDgrad, gy, N, H, W, co, prm->w[n], ci, nullptr, dense_view(gx, H, W, ci), null_view(), scratch + s.o_wino, s.n_wino, part_,
+                              part_n_, st, o));
+        } else if (gx) {
+            AFI_TRY(PG(conv_dgrad_desc(gy, N, H, W, co, prm->w[n], ci, dense_view(gx, H, W, ci)), 1));
         }
     }
     fk.join();
