@@ -121,6 +121,8 @@ SIGNATURES = {
     "afi_dual_scale_u8_ws_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
     "afi_dual_scale_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _ll, _vp]),
     "afi_normalize_pad_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "afi_resnet_stem_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "afi_nearest_nhwc": (_i, [View, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "afi_convT6s2_pack_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_unpack_wgrad": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp]),

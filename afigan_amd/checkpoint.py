@@ -6,7 +6,9 @@ Host-side restatement of the key remapping of ``AF_DetectionCheckpointer`` (afig
 stage-2 AF-extractor checkpoint hands only its ``srf_module`` tensors to the stage-3 detector.  No GPU work here.
 """
 import logging
-from typing import Dict, Tuple
+import pickle
+import re
+from typing import Dict, List, Tuple
 
 import torch
 
@@ -78,3 +80,55 @@ def load_target_detector_weights(model: torch.nn.Module, checkpoint) -> Dict[str
     matched = align_and_update(sd, kept)
     model.load_state_dict(sd, strict=True)
     return matched
+
+
+# Caffe2 / Detectron1 blob names (ImageNet R-50.pkl, Detectron1 model zoo): detectron2 loads them only through its name-matching heuristics,
+# which the reference's guide loader never runs (stage1_trainer.py:62-74 calls _load_model on the raw pickle)
+_CAFFE2_NAME = re.compile(r"^(conv1_[wb]|res_conv1_bn_[sb]|res\d+_\d+_branch\w+|fpn_inner_\w+|fpn_res\d+\w*|pred_\w+)$")
+
+
+def read_guide_checkpoint(path) -> Dict[str, torch.Tensor]:
+    """The state dict of a guide checkpoint file: a detectron2 model-zoo ``.pkl`` (``{"model": {name: numpy array}, "__author__": ...}``,
+    read with ``pickle.load(..., encoding="latin1")`` as stage1_trainer.py:66-68 does) or a ``.pth`` (``{"model": ...}`` or a bare state
+    dict).  Caffe2-named files are refused."""
+    if str(path).endswith(".pkl"):
+        with open(path, "rb") as f:
+            data = pickle.load(f, encoding="latin1")
+    else:
+        data = torch.load(path, map_location="cpu", weights_only=False)
+    if isinstance(data, dict) and "blobs" in data:
+        data = data["blobs"]
+    sd = _model_dict(data)
+    if not isinstance(sd, dict):
+        raise ValueError(f"{path}: not a state dict ({type(sd).__name__})")
+    caffe2 = sorted(k for k in sd if _CAFFE2_NAME.match(str(k)))
+    if caffe2:
+        raise ValueError(f"{path}: Caffe2-named weights ({', '.join(caffe2[:3])}, ...) are not supported; use a detectron2-format checkpoint "
+                         "(keys like backbone.bottom_up.res2.0.conv1.weight)")
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("module."):                                      # (DDP prefix, stripped as detectron2's Checkpointer does)
+            k = k[len("module."):]
+        if isinstance(v, torch.Tensor):
+            out[k] = v
+        elif hasattr(v, "dtype") and hasattr(v, "shape"):                # numpy arrays of a model-zoo pickle
+            out[k] = torch.as_tensor(v)
+    return out
+
+
+def load_guide_weights(model: torch.nn.Module, path) -> Tuple[List[str], List[str]]:
+    """``_load_model`` of the guide (stage1_trainer.py:62-74): load a guide checkpoint (a path, see read_guide_checkpoint, or an already
+    read state dict) NON-strictly into ``model`` (``RCNN_FPN_only``: keys ``backbone.*``).  Every key present on both sides must have the
+    same shape (ValueError otherwise).  Returns (missing keys: in the model, not in the file; unused keys: in the file, not in the model)."""
+    sd = model.state_dict()
+    ckpt = read_guide_checkpoint(path) if not isinstance(path, dict) else {k: torch.as_tensor(v) for k, v in _model_dict(path).items()}
+    bad = [(k, tuple(v.shape), tuple(sd[k].shape)) for k, v in ckpt.items() if k in sd and tuple(v.shape) != tuple(sd[k].shape)]
+    if bad:
+        raise ValueError("guide checkpoint shapes do not match the model: " + "; ".join(f"{k}: file {a}, model {b}" for k, a, b in bad[:5]))
+    matched = {k: v for k, v in ckpt.items() if k in sd}
+    model.load_state_dict(matched, strict=False)
+    missing = sorted(k for k in sd if k not in ckpt)
+    unused = sorted(k for k in ckpt if k not in sd)
+    if missing:
+        logger.warning("guide checkpoint: %d model keys not in the file (first: %s)", len(missing), missing[0])
+    return missing, unused

@@ -144,6 +144,11 @@ def get_cfg():
     except Exception:
         cfg = Node({"MODEL": {"DEVICE": "cuda", "PIXEL_MEAN": [103.530, 116.280, 123.675], "PIXEL_STD": [1.0, 1.0, 1.0],
                               "FPN": {"IN_FEATURES": ["res2", "res3", "res4", "res5"], "OUT_CHANNELS": 256, "NORM": "", "FUSE_TYPE": "sum"},
-                              "BACKBONE": {"NAME": "build_resnet_fpn_sr_backbone", "FREEZE_AT": 2}},
+                              "BACKBONE": {"NAME": "build_resnet_fpn_sr_backbone", "FREEZE_AT": 2},
+                              # detectron2's ResNet defaults (config/defaults.py _C.MODEL.RESNETS): what resnet_guide.py reads
+                              "RESNETS": {"DEPTH": 50, "OUT_FEATURES": ["res4"], "NUM_GROUPS": 1, "NORM": "FrozenBN", "WIDTH_PER_GROUP": 64,
+                                          "STRIDE_IN_1X1": True, "RES5_DILATION": 1, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64,
+                                          "DEFORM_ON_PER_STAGE": [False, False, False, False], "DEFORM_MODULATED": False,
+                                          "DEFORM_NUM_GROUPS": 1}},
                     "INPUT": {"FORMAT": "BGR"}, "SOLVER": {}})
         return add_afigan_config(cfg)

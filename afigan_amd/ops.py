@@ -692,6 +692,31 @@ def normalize_pad(images_chw, pixel_mean, pixel_std, size_divisibility=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ frozen ResNet-FPN guide (resnet_guide.py)
+def resnet_stem(x, w, bias):
+    """detectron2's BasicStem with its FrozenBN folded into (w [64,3,7,7], bias [64]): max_pool2d(relu(conv7x7/2(x)), 3, 2, 1) in one kernel.
+    x: the NCHW fp32 batch [N,3,H,W]; returns pixel-major [N,64,ceil(H/4),ceil(W/4)] (afi_resnet_stem_fwd)."""
+    _check_cuda(x, w, bias)
+    N, Cin, H, W = x.shape
+    if Cin != 3 or tuple(w.shape) != (64, 3, 7, 7) or tuple(bias.shape) != (64,):
+        raise _lib.AfiError(f"resnet_stem: a 3 -> 64 channel 7x7 stem only, got x {tuple(x.shape)}, w {tuple(w.shape)}")
+    x, w, bias = x.contiguous(), w.contiguous(), bias.contiguous()
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    out = new_pixel_major(N, 64, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, x.device)
+    call("afi_resnet_stem_fwd", _p(x), N, H, W, _p(w), _p(bias), _p(out), stream_ptr())
+    return out
+
+
+def nearest(x, up=2, down=1):
+    """Nearest resampling of a pixel-major tensor by up / down: F.interpolate(x, scale_factor=2, mode="nearest") (up=2), or the stride-2
+    subsampling max_pool2d(x, 1, 2) of LastLevelMaxPool (down=2).  Returns a dense pixel-major tensor (afi_nearest_nhwc)."""
+    _check_cuda(x)
+    N, C_, H, W = x.shape
+    out = new_pixel_major(N, C_, -(-H * up // down), -(-W * up // down), x.device)
+    call("afi_nearest_nhwc", view_of(x), N, H, W, C_, int(up), int(down), _p(out), stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

@@ -515,6 +515,19 @@ int afi_dual_scale_u8(const unsigned char* src, int H0, int W0, int C, unsigned 
 int afi_normalize_pad_u8(const unsigned char* img_chw, int C, int H, int W, const float* mean, const float* std_,
                          float* out, int Hp, int Wp, void* stream);
 
+/* ------------------------------------------------------------------ frozen ResNet-FPN guide (afigan_amd/resnet_guide.py)
+ * The guide network of stages 1 and 2 (RCNN_FPN_only over detectron2's build_resnet_fpn_backbone), forward only.  Its 1x1 convs are
+ * afi_conv1x1_fwd, its 3x3 convs afi_conv3x3_fwd / afi_conv3x3_wino_infer / afi_conv3x3s2_fwd; these two cover the rest.
+ * afi_resnet_stem_fwd: BasicStem in one kernel -- out = max_pool2d(relu(conv2d(x, w, bias, stride 2, pad 3)), 3, stride 2, pad 1), torch's
+ *   padding (zeros for the conv, -inf for the pool).  x dense NCHW [N][3][H][W] fp32 (the normalised, padded batch); w dense [64][3][7][7]
+ *   and bias[64] with the FrozenBN affine folded in; out dense [N][Ho][Wo][64], Ho = ceil(ceil(H/2)/2).  fp32 FMA chains; the conv map
+ *   is never written.
+ * afi_nearest_nhwc: out dense [N][Ho][Wo][C] = x[n][oy*down/up][ox*down/up][c], Ho = ceil(H*up/down): F.interpolate(scale_factor=2,
+ *   mode="nearest") with up = 2, down = 1 (the FPN top-down addend), max_pool2d(1, stride 2) with up = 1, down = 2 (LastLevelMaxPool).
+ *   C % 4 == 0, x and out 16-byte aligned, view strides multiples of 4 (AFI_ERR_UNSUPPORTED otherwise). */
+int afi_resnet_stem_fwd(const float* x, int N, int H, int W, const float* w, const float* bias, float* out, void* stream);
+int afi_nearest_nhwc(afi_view_t x, int N, int H, int W, int C, int up, int down, float* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
