@@ -9,7 +9,11 @@ two frozen R-50-FPN guide forwards (image and image_x0.5), the D step and the G 
 the RCCL gradient all-reduce (N > 1) and both fused SGD updates.  Inputs are resident in HBM before the timed region.
 Rank 0 prints ONE JSON line.  `value` = images/s of the whole job; weak scaling (2 images per GPU).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  Everything measured beside the
+headline takes runs of its own and comes with --full only: the extra objects below, `other_dtypes`, and for N > 1 the exchanges timed
+alone (`comm.allreduce_alone`), `comm.comm_exposed_ms` and the overlap_comm A/B (`comm.overlap_ab`).
+
+Extra objects on the line (--full):
   roofline      -- the dominant kernel of the timed region (by summed HIP-event time, measured on the launch stream by the
                    library's own event brackets): algorithmic FLOP / time vs the dense fp32 MFMA peak (157.3 TFLOP/s).
   cpu_baseline  -- the CPU oracle (kind "port": oracle/afigan_oracle.py, a PyTorch-CPU restatement pinned to the reference's
@@ -56,19 +60,22 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch-per-gpu", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-interp", action="store_true", help="skip the AF-interpolator micro-benchmark")
+    ap.add_argument("--full", action="store_true", help="also measure what lies beside the headline (off: the run does only what `value` and "
+                    "`ms_per_step` need): the roofline repeat and its kernel_alone steps, the other dtypes, the AF-interpolator / FPN / "
+                    "BiFPN / stage-2 / data-path legs, the CPU baseline; for N > 1 the exchanges alone, their exposure and the overlap_comm A/B")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-interp", action="store_true", help="--full: skip the AF-interpolator micro-benchmark and the legs after it")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl == RCCL; gloo only to rehearse "
                     "the multi-process path with several ranks sharing one GPU)")
     ap.add_argument("--dtype", default=None, choices=["fp32", "f16x3", "bf16x6", "bf16x3", "bf16"],
                     help="how the big convolutions' GEMMs form their fp32 products (afi_ctx_set_compute_dtype).  Default: the library's "
-                         "(f16x3: two scaled fp16 pieces per operand, three products, fp32-grade); the default run also times the other settings on the same "
-                         "engine afterwards and reports them under other_dtypes")
+                         "(f16x3: two scaled fp16 pieces per operand, three products, fp32-grade); without --dtype, --full also times the other settings on "
+                         "the same engine afterwards and reports them under other_dtypes")
     ap.add_argument("--overlap-comm", type=int, default=None, choices=[0, 1], help="N > 1: issue the two gradient all-reduces asynchronously beside independent work "
                     "(Stage1Step(overlap_comm=...)); default: the engine's (on under gloo, off under nccl until an RCCL run has exercised it)")
-    ap.add_argument("--profile-timed", action="store_true", help="record the library's per-launch HIP events INSIDE the timed region (default: over a repeat of "
-                    "the same K steps right behind it, so that the headline number carries no event records); the rocprofv3 passes use it: their traces "
-                    "then hold exactly the timed launches")
+    ap.add_argument("--profile-timed", action="store_true", help="record the library's per-launch HIP events INSIDE the timed region (default: --full records "
+                    "them over a repeat of the same K steps right behind it, so that the headline number carries no event records); the rocprofv3 passes "
+                    "use it: their traces then hold exactly the timed launches")
     ap.add_argument("--synthetic-pyramid", action="store_true",
                     help="feed seeded randn pyramids instead of running the R-50-FPN guide (debug only; not the headline config)")
     ap.add_argument("--pair-d-max-pixels", type=int, default=None, help="Stage1Step(pair_d_max_pixels=...): levels up to this many pixels run D(real) and D(fake) "
@@ -81,8 +88,8 @@ def parse():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="afi_ctx_set_option on the engine's contexts (A/B runs), "
                     "e.g. --option g_batch_growth_grads=0; names: afigan_amd._lib.OPTIONS")
     ap.add_argument("--dist-world-1", action="store_true", help="--gpus 1 only: run the distributed code path anyway, on a ONE-rank process group of "
-                    "--backend (a real RCCL communicator under nccl): broadcast, both all-reduces, the `comm` object and the overlap_comm A/B leg "
-                    "execute on a one-GPU box.  Not the headline configuration")
+                    "--backend (a real RCCL communicator under nccl): broadcast, both all-reduces, the `comm` object and (with --full) the overlap_comm "
+                    "A/B leg execute on a one-GPU box.  Not the headline configuration")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launch path only (no GPU work, no metric): spawn / rendezvous / all-reduce / invariant checks of the N-rank job with "
                          "CPU tensors; what tests/test_host_logic.py runs with --gpus 2 --backend gloo in a container without a GPU")
@@ -93,6 +100,9 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if os.environ.get("AFI_PROFILE_DUMP") and not (args.full or args.profile_timed):
+        ap.error("AFI_PROFILE_DUMP needs --full (launches of the profiled repeat) or --profile-timed (launches of the timed steps): "
+                 "a plain run records none")
     return args
 
 
@@ -179,17 +189,18 @@ def main():
         name, _, val = kv.partition("=")
         step.set_option(name, int(val))
     run_dtype = step.dtype                             # the library's default when --dtype is not given
-    # data-parallel runs: what the process group says it is, and what the two gradient exchanges of a step cost with nothing beside them
+    # data-parallel runs: what the process group says it is, and (--full) what the two gradient exchanges of a step cost with nothing beside them
     # (the engine's own flat gradient buffers: D 61.4 MB, G 31.3 MB), before any step runs -- SURVEY 8e (2), (3)
     comm = None
     if dist is not None:
         if args.overlap_comm is not None:
             step.overlap_comm = bool(args.overlap_comm)
         comm = {"backend": dist.get_backend(), "world_size_reported": dist.get_world_size(), "rank0_device": torch.cuda.get_device_name(dev),
-                "overlap_comm": bool(step.overlap_comm),
-                "allreduce_alone": allreduce_alone(dist, torch, {"D": step.d_opt.flat_grad, "G": step.g_opt.flat_grad}, dev, world)}
-        log(f"process group: backend {comm['backend']}, world {comm['world_size_reported']}; all-reduce alone: " +
-            ", ".join(f"{k} {v['ms']:.3f} ms ({v['bus_gb_per_s']} GB/s bus)" for k, v in comm["allreduce_alone"].items()))
+                "overlap_comm": bool(step.overlap_comm)}
+        log(f"process group: backend {comm['backend']}, world {comm['world_size_reported']}")
+        if args.full:
+            comm["allreduce_alone"] = allreduce_alone(dist, torch, {"D": step.d_opt.flat_grad, "G": step.g_opt.flat_grad}, dev, world)
+            log("all-reduce alone: " + ", ".join(f"{k} {v['ms']:.3f} ms ({v['bus_gb_per_s']} GB/s bus)" for k, v in comm["allreduce_alone"].items()))
     guide = None if args.synthetic_pyramid else GuideR50FPN().to(dev)
     gen = torch.Generator(device=dev).manual_seed(100 + rank)     # each rank owns a different shard of the global batch
     images = torch.rand((B, 3, 800, 1333), device=dev, generator=gen) * 255.0
@@ -283,7 +294,7 @@ def main():
         log(f"--dump-outputs: {n_files} arrays, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}")
     host_timed = {k: list(v[-args.steps:]) for k, v in host_ms.items()}      # (the profiled repeat below appends its own)
     profiled_ms_per_step = None
-    if not args.profile_timed:
+    if args.full and not args.profile_timed:
         if rank == 0:
             lib.afi_profile_enable(1)
         step.measure_comm = dist is not None               # events either side of each exchange's wait, on the stream that waits (last step's are kept)
@@ -307,11 +318,11 @@ def main():
         step.measure_comm = False
         log(f"profiled repeat done: {profiled_ms_per_step:.2f} ms/step with the event brackets on")
     def overlap_ab_leg(emit_on_timeout=None):
-        """The other setting of overlap_comm on the same engine, same inputs, same K (never the headline): the first multi-GPU run measures both.
+        """The other setting of overlap_comm on the same engine, same inputs, same K (never the headline; --full): the first multi-GPU run measures both.
         It is the one leg of an N > 1 run that issues collectives no multi-GPU box has run yet, so for world > 1 it is the LAST thing every rank does,
         behind a watchdog: if it has not finished within AFI_BENCH_AB_TIMEOUT_S (default 90) the rank leaves -- rank 0 after printing the line it
         had already completed (`emit_on_timeout`), with the time-out recorded in comm.overlap_ab -- instead of taking the measured headline down."""
-        if dist is None or os.environ.get("AFI_BENCH_OVERLAP_AB", "1") == "0":
+        if dist is None or not args.full or os.environ.get("AFI_BENCH_OVERLAP_AB", "1") == "0":
             return
         import threading
         other = not step.overlap_comm
@@ -373,96 +384,97 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the dominant kernel (HIP events recorded by the library on the launch stream)
-    kinds = []
-    for k in range(lib.afi_profile_num_kinds()):
-        out3 = (C.c_double * 3)()
-        _lib.check(lib.afi_profile_get(k, out3), "afi_profile_get")
-        if out3[0] > 0:
-            kinds.append({"kernel": lib.afi_profile_kind_name(k).decode(), "launches": int(out3[0]), "ms_total": out3[1],
-                          "avg_us": out3[1] / out3[0] * 1e3, "tflops": out3[2] / (out3[1] * 1e-3) / 1e12 if out3[1] > 0 else 0.0,
-                          "flop_total": out3[2]})
-    kinds.sort(key=lambda r: -r["ms_total"])
-    dom = kinds[0]
-    # The timed steps run the D phase (and G's backward) on two streams, so the HIP-event duration of a launch above includes the time it
-    # shares the chip with the other stream's kernels.  The same kernel with the chip to itself: two extra steps with the overlaps off.
-    kernel_alone = None
-    if world == 1 and step.overlap_d and os.environ.get("AFI_BENCH_OTHER_DTYPES", "1") != "0":     # (the profiled runs of tools/prof_r02.sh switch the extra legs off)
-        og = step.overlap_g
-        step.overlap_d = step.overlap_g = False
-        one_step(solo=True); torch.cuda.synchronize()
-        lib.afi_profile_enable(1)
-        for _ in range(2):
-            one_step(solo=True)
-        torch.cuda.synchronize()
-        lib.afi_profile_enable(0)
+    # ---- roofline of the dominant kernel (HIP events recorded by the library on the launch stream) and the other dtypes: --full only
+    roofline = other_dtypes = None
+    if args.full:
+        kinds = []
         for k in range(lib.afi_profile_num_kinds()):
-            if lib.afi_profile_kind_name(k).decode() == dom["kernel"]:
-                o3 = (C.c_double * 3)()
-                _lib.check(lib.afi_profile_get(k, o3), "afi_profile_get")
-                if o3[0] > 0:
-                    kernel_alone = {"launches": int(o3[0]), "avg_launch_us": o3[1] / o3[0] * 1e3, "achieved": o3[2] / (o3[1] * 1e-3) / 1e12}
-        step.overlap_d, step.overlap_g = True, og
-    # the opt-in bf16 arithmetic on the same engine, same inputs (N = 1 only; never the headline value): 1 warm-up + the same K steps each
-    other_dtypes = None
-    if world == 1 and args.dtype is None and os.environ.get("AFI_BENCH_OTHER_DTYPES", "1") != "0":
-        other_dtypes = {}
-        for dt in [d for d in ("fp32", "f16x3", "bf16x6", "bf16x3", "bf16") if d != run_dtype]:
-            step.set_dtype(dt)
-            one_step()
-            torch.cuda.synchronize()
+            out3 = (C.c_double * 3)()
+            _lib.check(lib.afi_profile_get(k, out3), "afi_profile_get")
+            if out3[0] > 0:
+                kinds.append({"kernel": lib.afi_profile_kind_name(k).decode(), "launches": int(out3[0]), "ms_total": out3[1],
+                              "avg_us": out3[1] / out3[0] * 1e3, "tflops": out3[2] / (out3[1] * 1e-3) / 1e12 if out3[1] > 0 else 0.0,
+                              "flop_total": out3[2]})
+        kinds.sort(key=lambda r: -r["ms_total"])
+        dom = kinds[0]
+        # The timed steps run the D phase (and G's backward) on two streams, so the HIP-event duration of a launch above includes the time it
+        # shares the chip with the other stream's kernels.  The same kernel with the chip to itself: two extra steps with the overlaps off.
+        kernel_alone = None
+        if world == 1 and step.overlap_d and os.environ.get("AFI_BENCH_OTHER_DTYPES", "1") != "0":     # (the profiled runs of tools/prof_r02.sh switch the extra legs off)
+            og = step.overlap_g
+            step.overlap_d = step.overlap_g = False
+            one_step(solo=True); torch.cuda.synchronize()
             lib.afi_profile_enable(1)
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                one_step()
+            for _ in range(2):
+                one_step(solo=True)
             torch.cuda.synchronize()
-            el = time.perf_counter() - t1
             lib.afi_profile_enable(0)
-            gk = []
             for k in range(lib.afi_profile_num_kinds()):
-                o3 = (C.c_double * 3)()
-                _lib.check(lib.afi_profile_get(k, o3), "afi_profile_get")
-                name = lib.afi_profile_kind_name(k).decode()
-                if o3[0] > 0 and ("gemm_nt" in name or "gemm_tn" in name):
-                    tf = o3[2] / (o3[1] * 1e-3) / 1e12
-                    gk.append({"kernel": name, "launches": int(o3[0]), "ms_total": round(o3[1], 3), "tflops": round(tf, 1),
-                               "frac_of_peak": round(tf / gemm_peak(dt), 4), "peak": round(gemm_peak(dt), 1)})
-            try:
-                fin = all(v == v and abs(v) != float("inf") for v in step.metrics().values())
-            except FloatingPointError:
-                fin = False
-            other_dtypes[dt] = {"ms_per_step": el / args.steps * 1e3, "images_per_s": B * args.steps / el, "losses_finite": fin, "winograd_gemm_kernels": gk}
-            log(f"dtype {dt}: {el / args.steps * 1e3:.1f} ms/step")
-        step.set_dtype(run_dtype)
+                if lib.afi_profile_kind_name(k).decode() == dom["kernel"]:
+                    o3 = (C.c_double * 3)()
+                    _lib.check(lib.afi_profile_get(k, o3), "afi_profile_get")
+                    if o3[0] > 0:
+                        kernel_alone = {"launches": int(o3[0]), "avg_launch_us": o3[1] / o3[0] * 1e3, "achieved": o3[2] / (o3[1] * 1e-3) / 1e12}
+            step.overlap_d, step.overlap_g = True, og
+        # the opt-in bf16 arithmetic on the same engine, same inputs (N = 1 only; never the headline value): 1 warm-up + the same K steps each
+        if world == 1 and args.dtype is None and os.environ.get("AFI_BENCH_OTHER_DTYPES", "1") != "0":
+            other_dtypes = {}
+            for dt in [d for d in ("fp32", "f16x3", "bf16x6", "bf16x3", "bf16") if d != run_dtype]:
+                step.set_dtype(dt)
+                one_step()
+                torch.cuda.synchronize()
+                lib.afi_profile_enable(1)
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    one_step()
+                torch.cuda.synchronize()
+                el = time.perf_counter() - t1
+                lib.afi_profile_enable(0)
+                gk = []
+                for k in range(lib.afi_profile_num_kinds()):
+                    o3 = (C.c_double * 3)()
+                    _lib.check(lib.afi_profile_get(k, o3), "afi_profile_get")
+                    name = lib.afi_profile_kind_name(k).decode()
+                    if o3[0] > 0 and ("gemm_nt" in name or "gemm_tn" in name):
+                        tf = o3[2] / (o3[1] * 1e-3) / 1e12
+                        gk.append({"kernel": name, "launches": int(o3[0]), "ms_total": round(o3[1], 3), "tflops": round(tf, 1),
+                                   "frac_of_peak": round(tf / gemm_peak(dt), 4), "peak": round(gemm_peak(dt), 1)})
+                try:
+                    fin = all(v == v and abs(v) != float("inf") for v in step.metrics().values())
+                except FloatingPointError:
+                    fin = False
+                other_dtypes[dt] = {"ms_per_step": el / args.steps * 1e3, "images_per_s": B * args.steps / el, "losses_finite": fin, "winograd_gemm_kernels": gk}
+                log(f"dtype {dt}: {el / args.steps * 1e3:.1f} ms/step")
+            step.set_dtype(run_dtype)
 
-    gemm_ms = sum(r["ms_total"] for r in kinds)
-    gemm_flop = sum(r["flop_total"] for r in kinds)
-    traffic = committed_traffic("traffic_dominant_kernel.json", dom["kernel"])
-    # the Winograd GEMMs' own roof: the dense bf16 MFMA peak over the bf16 MFMAs issued per fp32-equivalent product (6 / 3 / 1), or the
-    # fp32 MFMA peak; every other kernel multiplies on the fp32 MFMA
-    dom_peak = kind_peak(dom["kernel"], run_dtype)
-    peak_s = sum(r["flop_total"] / (kind_peak(r["kernel"], run_dtype) * 1e12) for r in kinds)        # seconds the step's products take at each kernel's own peak
-    roofline = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"], "peak": dom_peak, "unit": "TFLOP/s",
-                "frac": dom["tflops"] / dom_peak, "traffic": traffic, "launches": dom["launches"], "avg_launch_us": dom["avg_us"],
-                "share_of_step_time": dom["ms_total"] / (elapsed * 1e3),
-                # `achieved` above is over the timed region, where the D phase runs on two streams: a launch's duration includes the time it
-                # shares the chip with the other stream's kernels (sum of durations > wall time).  The kernel with the chip to itself:
-                "kernel_alone": (dict(kernel_alone, frac=kernel_alone["achieved"] / dom_peak,
-                                      note="two extra steps on ONE stream (overlap_d / overlap_g / guide prefetch off), same HIP-event "
-                                           "brackets; profiles/r06 holds both traces")
-                                 if kernel_alone else None),
-                # fp32-equivalent rate of the dominant kernel against the fp32 MFMA roof it replaces (> 1 is the point of the emulated forms)
-                "achieved_over_fp32_mfma_peak": dom["tflops"] / PEAK_FP32_MFMA_TFLOPS,
-                "peak_note": PEAK_NOTE,
-                # the whole step in EXECUTED matrix-core products (what the GEMM launches multiplied, Winograd-domain for the big convs): the time
-                # they need at each kernel's own peak over the wall time -- the one <= 1 "achieved roofline" figure of the step
-                "frac_step_executed": peak_s / elapsed,
-                "all_gemm_kernels": {"tflops": gemm_flop / (gemm_ms * 1e-3) / 1e12, "frac": peak_s / (gemm_ms * 1e-3),
-                                     "share_of_step_time": gemm_ms / (elapsed * 1e3)},
-                "per_kernel": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items() if k != "flop_total"} for r in kinds],
-                "measured_over": ("the timed region itself (--profile-timed)" if args.profile_timed else
-                                  f"a repeat of the timed region's {args.steps} steps right behind it with the library's per-launch HIP events on "
-                                  f"({profiled_ms_per_step:.2f} ms/step there): the timed region carries no event records")}
+        gemm_ms = sum(r["ms_total"] for r in kinds)
+        gemm_flop = sum(r["flop_total"] for r in kinds)
+        traffic = committed_traffic("traffic_dominant_kernel.json", dom["kernel"])
+        # the Winograd GEMMs' own roof: the dense bf16 MFMA peak over the bf16 MFMAs issued per fp32-equivalent product (6 / 3 / 1), or the
+        # fp32 MFMA peak; every other kernel multiplies on the fp32 MFMA
+        dom_peak = kind_peak(dom["kernel"], run_dtype)
+        peak_s = sum(r["flop_total"] / (kind_peak(r["kernel"], run_dtype) * 1e12) for r in kinds)        # seconds the step's products take at each kernel's own peak
+        roofline = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"], "peak": dom_peak, "unit": "TFLOP/s",
+                    "frac": dom["tflops"] / dom_peak, "traffic": traffic, "launches": dom["launches"], "avg_launch_us": dom["avg_us"],
+                    "share_of_step_time": dom["ms_total"] / (elapsed * 1e3),
+                    # `achieved` above is over the timed region, where the D phase runs on two streams: a launch's duration includes the time it
+                    # shares the chip with the other stream's kernels (sum of durations > wall time).  The kernel with the chip to itself:
+                    "kernel_alone": (dict(kernel_alone, frac=kernel_alone["achieved"] / dom_peak,
+                                          note="two extra steps on ONE stream (overlap_d / overlap_g / guide prefetch off), same HIP-event "
+                                               "brackets; profiles/r06 holds both traces")
+                                     if kernel_alone else None),
+                    # fp32-equivalent rate of the dominant kernel against the fp32 MFMA roof it replaces (> 1 is the point of the emulated forms)
+                    "achieved_over_fp32_mfma_peak": dom["tflops"] / PEAK_FP32_MFMA_TFLOPS,
+                    "peak_note": PEAK_NOTE,
+                    # the whole step in EXECUTED matrix-core products (what the GEMM launches multiplied, Winograd-domain for the big convs): the time
+                    # they need at each kernel's own peak over the wall time -- the one <= 1 "achieved roofline" figure of the step
+                    "frac_step_executed": peak_s / elapsed,
+                    "all_gemm_kernels": {"tflops": gemm_flop / (gemm_ms * 1e-3) / 1e12, "frac": peak_s / (gemm_ms * 1e-3),
+                                         "share_of_step_time": gemm_ms / (elapsed * 1e3)},
+                    "per_kernel": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items() if k != "flop_total"} for r in kinds],
+                    "measured_over": ("the timed region itself (--profile-timed)" if args.profile_timed else
+                                      f"a repeat of the timed region's {args.steps} steps right behind it with the library's per-launch HIP events on "
+                                      f"({profiled_ms_per_step:.2f} ms/step there): the timed region carries no event records")}
 
     # algorithmic work of one step per image: D fwd 4x hr px + D bwd on 2x hr px; G fwd 2x lr px + G bwd 1x lr px
     hr_px = sum(h * w for h, w in hr_shapes)
@@ -472,9 +484,10 @@ def main():
     n_img = world * B * args.steps
     # SURVEY 8(d)'s algorithmic (direct-convolution) FLOP count of the step over wall time and peak.  It can pass 1: the big 3x3 convs
     # run in Winograd form, which executes 2.25x (F(2x2,3x3)) / 4x (F(4x4,3x3)) fewer multiplies than the count assumes
-    roofline["algorithmic_over_peak"] = flop_img * B * args.steps / elapsed / 1e12 / PEAK_FP32_MFMA_TFLOPS
-    roofline["winograd_multiply_reduction"] = ("4x F(4x4,3x3): data / weight gradients, forwards without a backward, D's blocks 1 and 2; "
-                                               "2.25x F(2x2,3x3): the other forwards a backward follows")
+    if roofline is not None:
+        roofline["algorithmic_over_peak"] = flop_img * B * args.steps / elapsed / 1e12 / PEAK_FP32_MFMA_TFLOPS
+        roofline["winograd_multiply_reduction"] = ("4x F(4x4,3x3): data / weight gradients, forwards without a backward, D's blocks 1 and 2; "
+                                                   "2.25x F(2x2,3x3): the other forwards a backward follows")
     line = {
         "metric": "stage1_G+D_step_images_per_s", "value": n_img / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -501,9 +514,9 @@ def main():
         "params_identical_across_ranks": params_identical,
         "losses_last_step": {k: round(v, 5) for k, v in metrics.items()}, "losses_finite": losses_finite,
     }
-    log("AF-interpolator micro-benchmark")
-    micro = not args.no_interp and world == 1             # single-GPU metrics: reported on the N=1 line only
+    micro = args.full and not args.no_interp and world == 1      # single-GPU metrics: reported on the N=1 line only
     if micro:
+        log("AF-interpolator micro-benchmark")
         # release the stage-1 engine first: with its tens of GB of workspaces mapped, every kernel launch of the small-map
         # legs cost the host ~16 us instead of ~5 us and the (launch-bound) config-1 leg measured the host, not the GPU
         del step, G, D
@@ -545,8 +558,8 @@ def main():
         line["stage2_adversarial"] = stage2_bench(amd, torch)
         from tools import dual_scale_bench                       # the mapper's uint8 resize pair + normalise/pad
         line["dual_scale_data_path"] = dual_scale_bench.run(iters=100, warm=10, cpu_iters=3)
-    log("CPU baseline (oracle) on the host cores")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        log("CPU baseline (oracle) on the host cores")
         line["cpu_baseline"] = cpu_baseline(torch, B)
         line["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
         if "af_interpolator" in line:                      # metric 1, GPU beside CPU, in the object the driver keeps

@@ -115,7 +115,7 @@ D_GRAD_FLOATS, G_GRAD_FLOATS = 15_352_324, 7_834_624        # flat gradient buff
 def rehearse_launch(args, world, rank):
     """--rehearse-launch: everything bench.py does AROUND the GPU work for an N-rank job, on CPU tensors over gloo: rendezvous, the `comm`
     object (backend, world size as the group reports it, the two exchanges alone on buffers of the real sizes: the same
-    `allreduce_alone` the real run calls), K "steps" whose only content is the two all-reduces of a step in the engine's order (blocking,
+    `allreduce_alone` the real run calls under --full), K "steps" whose only content is the two all-reduces of a step in the engine's order (blocking,
     or asynchronous and waited for where the engine waits: `--overlap-comm`), barrier + MAX-over-ranks timing, per-rank images/s, the
     cross-rank identity check (`identical_across_ranks`, as the real run), ONE JSON line from rank 0.  Reports no metric."""
     import torch

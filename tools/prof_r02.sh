@@ -4,7 +4,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r02; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export AFI_BENCH_OTHER_DTYPES=0      # the profiled runs hold the default arithmetic only (the default run at the end reports every setting)
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 L="python3 $R/tools/cfg1_loop.py"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o step -- $B --steps 3 --warmup 0 --no-interp --no-cpu-baseline > $O/bench_trace.log 2>&1
@@ -25,6 +25,6 @@ timeout -k 10 200 rocprofv3 --pmc $SQ --output-format csv -d $O/cfg1_sq -o cfg1 
 echo cfg1 passes done
 unset AFI_BENCH_OTHER_DTYPES
 cd $R && timeout -k 10 200 $L 200 g > $O/cfg1_default.log 2>&1
-cd $R && timeout -k 10 500 python bench.py > $O/bench_default.log 2> $O/bench_default.err
+cd $R && timeout -k 10 500 python bench.py --full > $O/bench_default.log 2> $O/bench_default.err
 echo default done
 find $O -name "*.csv" | head -40

@@ -5,7 +5,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r06; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export AFI_BENCH_OTHER_DTYPES=0      # the profiled runs hold the default arithmetic only (the default run at the end reports every setting)
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 L="python3 $R/tools/cfg1_loop.py"
 S="--no-interp --no-cpu-baseline --profile-timed"   # (the library's event brackets inside the timed region: the traces hold exactly the timed launches)
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
@@ -42,6 +42,6 @@ python3 $R/tools/gflip_check.py 52 84 > $O/gflip_interpolator_forwards.txt 2>&1 
 echo widened rows done
 unset AFI_BENCH_OTHER_DTYPES
 cd $R && timeout -k 10 200 $L 200 g > $O/cfg1_default.log 2>&1
-cd $R && timeout -k 10 500 python bench.py > $O/bench_default.log 2> $O/bench_default.err
+cd $R && timeout -k 10 500 python bench.py --full > $O/bench_default.log 2> $O/bench_default.err
 echo default done
 find $O -name "*.csv" | head -40
