@@ -123,6 +123,12 @@ SIGNATURES = {
     "afi_normalize_pad_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "afi_resnet_stem_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "afi_nearest_nhwc": (_i, [View, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "afi_resnest_stem_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "afi_resnest_pool_nhwc": (_i, [View, _i, _i, _i, _i, _i, _vp, _vp]),
+    "afi_resnest_splat_ws_floats": (_ll, [_i, _i, _i, _i]),
+    "afi_resnest_splat_gap": (_i, [View, View, _i, _i, _i, _i, _vp, _ll, _vp]),
+    "afi_resnest_splat_attn": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "afi_resnest_splat_combine": (_i, [View, View, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "afi_convT6s2_pack_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_unpack_wgrad": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp]),

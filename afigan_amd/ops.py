@@ -717,6 +717,58 @@ def nearest(x, up=2, down=1):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ frozen ResNeSt bottom-up (resnest_backbone.py)
+POOL_MODES = {"max3s2p1": 0, "avg3s2p1": 1, "avg2s2_ceil": 2}          # AFI_POOL_* of include/afigan_hip.h
+
+
+def resnest_stem(x, w, bias):
+    """The deep stem's first conv with its norm folded into (w [Cout,3,3,3], bias [Cout]): relu(conv2d(x, w, bias, stride 2, padding 1)).
+    x: the NCHW fp32 batch [N,3,H,W]; returns pixel-major [N,Cout,ceil(H/2),ceil(W/2)] (afi_resnest_stem_fwd)."""
+    _check_cuda(x, w, bias)
+    N, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    if Cin != 3 or tuple(w.shape) != (Cout, 3, 3, 3) or tuple(bias.shape) != (Cout,):
+        raise _lib.AfiError(f"resnest_stem: a 3-channel 3x3 conv only, got x {tuple(x.shape)}, w {tuple(w.shape)}")
+    x, w, bias = x.contiguous(), ohwi(w), bias.contiguous()
+    out = new_pixel_major(N, Cout, (H + 1) // 2, (W + 1) // 2, x.device)
+    call("afi_resnest_stem_fwd", _p(x), N, H, W, _p(w), _p(bias), Cout, _p(out), stream_ptr())
+    return out
+
+
+def resnest_pool(x, mode):
+    """Pooling of a pixel-major tensor (afi_resnest_pool_nhwc); every mode gives [N,C,ceil(H/2),ceil(W/2)]:
+    "max3s2p1" max_pool2d(3, 2, 1); "avg3s2p1" avg_pool2d(3, 2, 1) (count_include_pad: / 9); "avg2s2_ceil" avg_pool2d(2, 2, ceil_mode=True,
+    count_include_pad=False)."""
+    _check_cuda(x)
+    N, C_, H, W = x.shape
+    out = new_pixel_major(N, C_, (H + 1) // 2, (W + 1) // 2, x.device)
+    call("afi_resnest_pool_nhwc", view_of(x), N, H, W, C_, POOL_MODES[mode], _p(out), stream_ptr())
+    return out
+
+
+def splat_attention(s0, s1, w1, b1, w2, b2, avd=False):
+    """Split attention (radix 2) over two pixel-major splits [N,C,H,W] (bn0 + ReLU already applied), in three passes: per-chunk channel sums
+    of s0 + s1, the per-image attention att = rsoftmax(fc2(relu(fc1(mean)))) with w1 [I,C] (bn1 folded) and w2 [2C,I], and the combine
+    att0 * s0 + att1 * s1 -- with avd, its avg_pool2d(3, 2, 1) in the same pass.  Returns (out, att [N, 2C])."""
+    _check_cuda(s0, s1, w1, b1, w2, b2)
+    N, C_, H, W = s0.shape
+    I = w1.shape[0]
+    if tuple(s1.shape) != tuple(s0.shape) or tuple(w1.shape[:2]) != (I, C_) or tuple(w2.shape[:2]) != (2 * C_, I):
+        raise _lib.AfiError(f"splat_attention: splits {tuple(s0.shape)} / {tuple(s1.shape)}, fc1 {tuple(w1.shape)}, fc2 {tuple(w2.shape)}")
+    w1, w2 = w1.reshape(I, C_).contiguous(), w2.reshape(2 * C_, I).contiguous()
+    n = _lib.load().afi_resnest_splat_ws_floats(N, H, W, C_)
+    if n <= 0:
+        raise _lib.AfiError(f"splat_attention: unsupported split width {C_}")
+    part = new_workspace(n, s0.device)
+    att = torch.empty((N, 2 * C_), device=s0.device, dtype=torch.float32)
+    call("afi_resnest_splat_gap", view_of(s0), view_of(s1), N, H, W, C_, _p(part), n, stream_ptr())
+    call("afi_resnest_splat_attn", _p(part), N, H, W, C_, I, _p(w1), _p(b1.contiguous()), _p(w2), _p(b2.contiguous()), _p(att), stream_ptr())
+    Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if avd else (H, W)
+    out = new_pixel_major(N, C_, Ho, Wo, s0.device)
+    call("afi_resnest_splat_combine", view_of(s0), view_of(s1), N, H, W, C_, _p(att), int(bool(avd)), _p(out), stream_ptr())
+    return out, att
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

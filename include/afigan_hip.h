@@ -528,6 +528,34 @@ int afi_normalize_pad_u8(const unsigned char* img_chw, int C, int H, int W, cons
 int afi_resnet_stem_fwd(const float* x, int N, int H, int W, const float* w, const float* bias, float* out, void* stream);
 int afi_nearest_nhwc(afi_view_t x, int N, int H, int W, int C, int up, int down, float* out, void* stream);
 
+/* ------------------------------------------------------------------ frozen ResNeSt bottom-up (afigan_amd/resnest_backbone.py)
+ * detectron2-ResNeSt (radix 2, cardinality 1, deep stem, AVD, avg_down), forward only.  Its 1x1 convs are afi_conv1x1_fwd, its stride-1 3x3
+ * convs afi_conv3x3_fwd / afi_conv3x3_wino_infer (a split-attention conv: one launch per radix group, through channel views); these cover
+ * the rest.  All outputs are dense pixel-major; channel counts are multiples of 4, views 16-byte aligned with strides multiples of 4
+ * (AFI_ERR_UNSUPPORTED otherwise).  No atomics: every sum has a fixed order.
+ * afi_resnest_stem_fwd: the deep stem's first conv, out [N][Ho][Wo][Cout] = relu(conv2d(x, w, bias, stride 2, pad 1)), Ho = ceil(H/2);
+ *   x dense NCHW [N][3][H][W] fp32, w dense [Cout][3][3][3] in (O, kh, kw, I) order with the norm folded in, Cout <= 128.
+ * afi_resnest_pool_nhwc: out [N][Ho][Wo][C] of x [N][H][W][C] by `mode`:
+ *   AFI_POOL_MAX3S2P1     max_pool2d(3, 2, 1), -inf padding; Ho = ceil(H/2)                                        (the stem)
+ *   AFI_POOL_AVG3S2P1     AvgPool2d(3, 2, padding 1), count_include_pad: always / 9; Ho = ceil(H/2)                 (AVD)
+ *   AFI_POOL_AVG2S2_CEIL  AvgPool2d(2, 2, ceil_mode, count_include_pad=False): / the pixels covered; Ho = ceil(H/2) (avg_down)
+ * Split attention over the two radix splits s0, s1 ([N][H][W][C] each, C = the group width, after bn0 + ReLU) in three passes:
+ *   afi_resnest_splat_gap      part = per-chunk channel sums of s0 + s1, [N][chunks][C]; part_floats >= afi_resnest_splat_ws_floats.
+ *   afi_resnest_splat_attn     att [N][2C]: gap = (sum of the chunks, in order) / (H*W); h = relu(w1 gap + b1) (w1 [I][C], bn1 folded);
+ *                              z = w2 h + b2 (w2 [2C][I]); (att[c], att[C+c]) = softmax(z[c], z[C+c]).  C <= 1024, I % 4 == 0.
+ *   afi_resnest_splat_combine  out = att[c] s0 + att[C+c] s1 ([N][H][W][C], avd 0), or its AvgPool2d(3, 2, padding 1) ([N][ceil(H/2)][ceil(W/2)][C],
+ *                              avd 1: the AVD layer of a stride-2 block, fused). */
+#define AFI_POOL_MAX3S2P1 0
+#define AFI_POOL_AVG3S2P1 1
+#define AFI_POOL_AVG2S2_CEIL 2
+int afi_resnest_stem_fwd(const float* x, int N, int H, int W, const float* w, const float* bias, int Cout, float* out, void* stream);
+int afi_resnest_pool_nhwc(afi_view_t x, int N, int H, int W, int C, int mode, float* out, void* stream);
+long long afi_resnest_splat_ws_floats(int N, int H, int W, int C);
+int afi_resnest_splat_gap(afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, float* part, long long part_floats, void* stream);
+int afi_resnest_splat_attn(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
+                           const float* b2, float* att, void* stream);
+int afi_resnest_splat_combine(afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, const float* att, int avd, float* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
