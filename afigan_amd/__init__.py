@@ -27,6 +27,7 @@ from .registry import BACKBONE_REGISTRY, GUIDE_ARCH_REGISTRY, build_guide_model 
 from .rcnn_only import RCNN_FPN_only  # noqa: E402
 from . import resnet_guide  # noqa: E402  (registers build_resnet_fpn_backbone when detectron2 is absent)
 from . import resnest_backbone  # noqa: E402  (registers build_resnest_fpn_backbone when detectron2 is absent)
+from . import swin_backbone  # noqa: E402  (opt-in "swint" bottom-up: swin_backbone.use_as_bottom_up)
 from .rcnn_extractor import GeneralizedRCNN_AFExtractor, META_ARCH_REGISTRY  # noqa: E402
 from .config import add_afigan_config, get_cfg  # noqa: E402
 

@@ -129,6 +129,10 @@ SIGNATURES = {
     "afi_resnest_splat_gap": (_i, [View, View, _i, _i, _i, _i, _vp, _ll, _vp]),
     "afi_resnest_splat_attn": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "afi_resnest_splat_combine": (_i, [View, View, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "afi_swin_patch_embed": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "afi_swin_layernorm": (_i, [View, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "afi_swin_gelu": (_i, [_vp, _ll, _vp]),
+    "afi_swin_window_attn": (_i, [View, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "afi_convT6s2_pack_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_unpack_wgrad": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp]),

@@ -769,6 +769,76 @@ def splat_attention(s0, s1, w1, b1, w2, b2, avd=False):
     return out, att
 
 
+# ------------------------------------------------------------------------------------------------ frozen Swin bottom-up (swin_backbone.py)
+SWIN_WINDOWS = (7, 12)                      # window sizes afi_swin_window_attn covers
+
+
+def swin_patch_embed(x, w, bias, gamma, beta, eps=1e-5):
+    """PatchEmbed: LayerNorm(conv2d(x zero-padded to multiples of 4, w [C,3,4,4], bias, stride 4)) with (gamma, beta, eps).
+    x: the NCHW fp32 batch [N,3,H,W]; returns pixel-major [N,C,ceil(H/4),ceil(W/4)] (afi_swin_patch_embed)."""
+    _check_cuda(x, w, bias, gamma, beta)
+    N, Cin, H, W = x.shape
+    C_ = w.shape[0]
+    if Cin != 3 or tuple(w.shape) != (C_, 3, 4, 4):
+        raise _lib.AfiError(f"swin_patch_embed: a 3-channel 4x4 conv only, got x {tuple(x.shape)}, w {tuple(w.shape)}")
+    out = new_pixel_major(N, C_, (H + 3) // 4, (W + 3) // 4, x.device)
+    call("afi_swin_patch_embed", _p(x.contiguous()), N, H, W, _p(w.contiguous()), _p(bias.contiguous()), _p(gamma.contiguous()),
+         _p(beta.contiguous()), float(eps), C_, _p(out), stream_ptr())
+    return out
+
+
+def swin_layernorm(x, gamma, beta, eps=1e-5, merge=False):
+    """LayerNorm over the channels of a pixel-major [N,C,H,W] -> pixel-major [N,C,H,W]; merge: PatchMerging's 2x2 gather (odd H / W
+    zero-padded, torch.cat([x0, x1, x2, x3]) order) and its LayerNorm over the 4C channels -> [N,4C,ceil(H/2),ceil(W/2)] (afi_swin_layernorm)."""
+    _check_cuda(x, gamma, beta)
+    N, C_, H, W = x.shape
+    Ct, Ho, Wo = (4 * C_, (H + 1) // 2, (W + 1) // 2) if merge else (C_, H, W)
+    if tuple(gamma.shape) != (Ct,) or tuple(beta.shape) != (Ct,):
+        raise _lib.AfiError(f"swin_layernorm: affine of {Ct} channels expected, got {tuple(gamma.shape)} / {tuple(beta.shape)}")
+    out = new_pixel_major(N, Ct, Ho, Wo, x.device)
+    call("afi_swin_layernorm", view_of(x), N, H, W, C_, _p(gamma.contiguous()), _p(beta.contiguous()), float(eps), int(bool(merge)), _p(out),
+         stream_ptr())
+    return out
+
+
+def swin_gelu_(x):
+    """Exact (erf) GELU of a dense pixel-major tensor, in place (afi_swin_gelu)."""
+    _check_cuda(x)
+    if not is_dense_pm(x):
+        raise _lib.AfiError("swin_gelu_: a dense pixel-major tensor is required")
+    call("afi_swin_gelu", _p(x), x.numel(), stream_ptr())
+    return x
+
+
+def swin_bias_image(table, index, window):
+    """The dense relative-position bias afi_swin_window_attn reads: [heads, NP, NP] with [h, i, j] = table[index[i, j], h] for i, j < window^2,
+    zero elsewhere (NP = window^2 rounded up to 16)."""
+    n = window * window
+    NP = (n + 15) // 16 * 16
+    heads = table.shape[1]
+    img = torch.zeros((heads, NP, NP), device=table.device, dtype=torch.float32)
+    img[:, :n, :n] = table.float()[index.reshape(-1).long()].reshape(n, n, heads).permute(2, 0, 1)
+    return img
+
+
+def swin_window_attn(qkv, qkv_bias, bias_img, window, shift):
+    """(Shifted) window attention of a pixel-major qkv [N,3C,H,W] (head dim 32) -> pixel-major [N,C,H,W], the reference's
+    pad / roll(-shift) / window_partition / WindowAttention (mask -100 across shift regions when shift > 0) / window_reverse / roll / crop
+    in one pass; padded tokens' q / k / v are qkv_bias.  bias_img: swin_bias_image (afi_swin_window_attn)."""
+    _check_cuda(qkv, qkv_bias, bias_img)
+    N, C3, H, W = qkv.shape
+    C_ = C3 // 3
+    if C3 % 3 or C_ % 32 or window not in SWIN_WINDOWS or not 0 <= shift < window or tuple(qkv_bias.shape) != (C3,):
+        raise _lib.AfiError(f"swin_window_attn: qkv {tuple(qkv.shape)} (head dim 32), window {window} (one of {SWIN_WINDOWS}), shift {shift}")
+    NP = (window * window + 15) // 16 * 16
+    if tuple(bias_img.shape) != (C_ // 32, NP, NP) or not bias_img.is_contiguous():
+        raise _lib.AfiError(f"swin_window_attn: bias image {tuple(bias_img.shape)}, expected dense {(C_ // 32, NP, NP)}")
+    out = new_pixel_major(N, C_, H, W, qkv.device)
+    call("afi_swin_window_attn", view_of(qkv), N, H, W, C_, _p(qkv_bias.contiguous()), _p(bias_img), int(window), int(shift), _p(out),
+         stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

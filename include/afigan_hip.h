@@ -556,6 +556,28 @@ int afi_resnest_splat_attn(const float* part, int N, int H, int W, int C, int I,
                            const float* b2, float* att, void* stream);
 int afi_resnest_splat_combine(afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, const float* att, int avd, float* out, void* stream);
 
+/* ------------------------------------------------------------------ frozen Swin Transformer bottom-up (afigan_amd/swin_backbone.py)
+ * SwinTransformer (patch 4, head dim 32, window 7 or 12, no APE), forward only.  Its linears are afi_conv1x1_fwd over pixel-major tokens;
+ * these cover the rest.  Outputs are dense pixel-major, channel counts multiples of 4, views 16-byte aligned with strides multiples of 4
+ * (AFI_ERR_UNSUPPORTED otherwise).  No atomics.
+ * afi_swin_patch_embed: out [N][ceil(H/4)][ceil(W/4)][C] = LayerNorm(conv2d(pad(x), w, bias, stride 4)) with (gamma, beta, eps); x dense NCHW
+ *   [N][3][H][W] fp32 zero-padded on the right / bottom to multiples of 4, w dense [C][3][4][4]; C <= 256.
+ * afi_swin_layernorm: merge 0: out [N][H][W][C] = LayerNorm over the channels of x [N][H][W][C] (biased variance, eps), gamma / beta [C].
+ *   merge 1 (PatchMerging): out [N][ceil(H/2)][ceil(W/2)][4C] = LayerNorm(cat(x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2])) of x
+ *   zero-padded to even H, W; gamma / beta [4C].  The normalised width (C or 4C) is at most 3072.
+ * afi_swin_gelu: x[i] = x[i] / 2 (1 + erf(x[i] / sqrt 2)) in place, n % 4 == 0.
+ * afi_swin_window_attn: out dense [N][H][W][C] of qkv [N][H][W][3C] (channel s C + 32 head + d, s = q, k, v): window multi-head attention
+ *   of window `window` (7 or 12) over the map zero-padded to multiples of it, rolled by -shift (0 <= shift < window), padded tokens' q / k /
+ *   v = qkv_bias [3C]; softmax(q k^T / sqrt 32 + bias_img[head] + mask) v, bias_img dense [C/32][NP][NP] (NP = ceil(window^2 / 16) 16;
+ *   entries past window^2 unused), mask -100 between tokens of different shift regions when shift > 0; written un-rolled and cropped. */
+int afi_swin_patch_embed(const float* x, int N, int H, int W, const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                         int C, float* out, void* stream);
+int afi_swin_layernorm(afi_view_t x, int N, int H, int W, int C, const float* gamma, const float* beta, float eps, int merge, float* out,
+                       void* stream);
+int afi_swin_gelu(float* x, long long n, void* stream);
+int afi_swin_window_attn(afi_view_t qkv, int N, int H, int W, int C, const float* qkv_bias, const float* bias_img, int window, int shift,
+                         float* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
