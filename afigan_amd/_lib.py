@@ -133,6 +133,11 @@ SIGNATURES = {
     "afi_swin_layernorm": (_i, [View, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "afi_swin_gelu": (_i, [_vp, _ll, _vp]),
     "afi_swin_window_attn": (_i, [View, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "afi_rpn_topk_ws_floats": (_ll, [_i, _i, _i, _i]),
+    "afi_rpn_topk": (_i, [View, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp, _ll, _vp]),
+    "afi_rpn_decode": (_i, [View, _i, _i, _i, _i, _vp, _i, _vp, _i, _ll, _vp, _f, _f, _f, _f, C.c_double, _f, _vp, _vp, _vp]),
+    "afi_rpn_nms": (_i, [_vp, _vp, _i, _i, _ll, _f, _vp, _vp]),
+    "afi_rpn_merge": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int), _i, _vp, _vp, _vp, _vp]),
     "afi_convT6s2_pack_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_unpack_wgrad": (_i, [_vp, _vp, _i, _i, _vp]),
     "afi_convT6s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp]),

@@ -1,0 +1,469 @@
+// The selection stages of the frozen RPN proposal generator (afigan_amd/rpn.py); its head (3x3 conv + ReLU, the two 1x1 convs as one) runs on
+// afi_conv3x3_wino_infer / afi_conv3x3_fwd and afi_conv1x1_fwd.
+//   afi_rpn_topk     per image, the k highest of the H W A objectness logits of one level, sorted by (logit descending, anchor index ascending).
+//                    A select, not a sort: every logit becomes an order-preserving 32-bit key, key and anchor index one 54-bit word
+//                    (key << 22 | ~index: distinct words, so "the k largest words" is one well-defined set), and the k-th largest word is found
+//                    by radix passes over LDS histograms (digits of 11, 11, 10 key bits, then 11, 11 index bits; the passes stop as soon as
+//                    the open digit group is taken whole -- with distinct logits after the key bits).  Maps of more than 16384 logits first
+//                    go through a histogram of the top 12 key bits over the whole grid and a filter that keeps the words of the bins down to
+//                    the one holding the cut (typically a few thousand); one block per image then selects among those.  The <= 1024 survivors
+//                    are sorted in LDS (bitonic, on the distinct words).  The integer atomics only count or hand out slots of an unordered
+//                    list: the result does not depend on their order.
+//   afi_rpn_decode   the selected anchors' deltas gathered from the pixel-major head output, the anchor formed from its index and the [A][4] cell
+//                    anchors, Box2BoxTransform.apply_deltas (evaluated in fp64 from the fp32 inputs, rounded once), the clip to the image's own
+//                    size and the MIN_SIZE test on the stored fp32 box.
+//   afi_rpn_nms      greedy NMS of <= 1024 sorted boxes per image: the suppression bit matrix (a wave's 64-bit __ballot is one word, 16 words per
+//                    row) is built in LDS by all sixteen waves; one wave then sweeps it 64 rows at a time -- the 64 x 64 diagonal block is
+//                    resolved in registers by lane reads, the kept rows' words OR-ed into the running mask by all lanes.  The overlap test
+//                    is compiled without fused multiply-adds: inter / (area_a + area_b - inter) > thresh, each operation rounded to fp32.
+//   afi_rpn_merge    the kept boxes of all levels of an image in (logit descending, level, rank) order, cut to post_k: every level's list is
+//                    already sorted, so an entry's place is its own rank plus one binary search per other level.  No sort, no atomics.
+// Nothing here synchronises with the host, and every result is bit-identical from run to run and under hipGraph replay.
+#include "../../include/afigan_hip.h"
+#include "afi_common.h"
+
+#define RPN_MAXK 1024
+#define RPN_MAX_A 16
+#define RPN_IDX_BITS 22
+#define RPN_IDX_MASK 0x3FFFFFu
+#define RPN_DIRECT_MAX 16384       // up to here the selecting block reads the logits itself
+#define RPN_BINS 4096              // grid histogram: the top 12 key bits
+#define RPN_HDR 4104               // ints per image in front of the candidate lists: the histogram, the list length, padding to 8 bytes
+#define RPN_MAX_LEVELS 8
+
+typedef unsigned long long u64;
+
+struct RpnLevels { int L; int off[RPN_MAX_LEVELS + 1]; };
+
+// Order-preserving key: a < b <=> key(a) < key(b) for numbers, -0 and +0 share one key (they compare equal), NaN is 0, below every number
+// (-inf is 0x007fffff).
+__device__ __forceinline__ unsigned rpn_key(float v) {
+    if (v != v) return 0u;
+    if (v == 0.f) return 0x80000000u;
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ const float* rpn_at(const AfiView& v, int img, int i, int W, int A) {
+    const int pix = i / A, a = i - pix * A, y = pix / W, x = pix - y * W;
+    return v.p + (long long)img * v.sN + (long long)y * v.sH + (long long)x * v.sW + a;
+}
+
+__device__ __forceinline__ u64 rpn_word(float v, int i) { return ((u64)rpn_key(v) << RPN_IDX_BITS) | (u64)((~(unsigned)i) & RPN_IDX_MASK); }
+
+// Inclusive prefix sum over the block (blockDim a multiple of 64, <= 1024); wtot: 16 ints of LDS.  Two barriers.
+__device__ __forceinline__ int rpn_block_scan(int v, int* wtot, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) wtot[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int i = 0; i < nw; ++i) {
+        const int t = wtot[i];
+        if (i < w) base += t;
+        tot += t;
+    }
+    *total = tot;
+    return inc + base;
+}
+
+// The digit d of a histogram (nbins a multiple of blockDim) that holds the need-th element counted from the top bin down, and the count of
+// the bins above it: res[0] = d, res[1] = above.  1 <= need <= sum(hist).  Ends with a barrier; hist is left as it was.
+__device__ __forceinline__ void rpn_find_digit(const int* hist, int nbins, int need, int* wtot, int* res) {
+    const int per = nbins / (int)blockDim.x, top = nbins - 1 - (int)threadIdx.x * per;
+    int own = 0;
+    for (int j = 0; j < per; ++j) own += hist[top - j];
+    if (threadIdx.x == 0) { res[0] = 0; res[1] = 0; }
+    int total;
+    const int inc = rpn_block_scan(own, wtot, &total);
+    int cum = inc - own;
+    if (cum < need && need <= inc) {
+        for (int j = 0; j < per; ++j) {
+            const int c = hist[top - j];
+            if (cum + c >= need) { res[0] = top - j; res[1] = cum; break; }
+            cum += c;
+        }
+    }
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------------ top-k: grid histogram and filter (large maps)
+__global__ __launch_bounds__(256) void afi_rpn_zero_kernel(int* __restrict__ p, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void afi_rpn_hist_kernel(const AfiView lg, int W, int A, int n, int* __restrict__ hdr) {
+    __shared__ int h[RPN_BINS];
+    const int img = blockIdx.y;
+    for (int i = threadIdx.x; i < RPN_BINS; i += 256) h[i] = 0;
+    __syncthreads();
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) atomicAdd(&h[rpn_key(*rpn_at(lg, img, i, W, A)) >> 20], 1);
+    __syncthreads();
+    int* g = hdr + (long long)img * RPN_HDR;
+    for (int i = threadIdx.x; i < RPN_BINS; i += 256)
+        if (h[i]) atomicAdd(&g[i], h[i]);
+}
+
+__global__ __launch_bounds__(256) void afi_rpn_filter_kernel(const AfiView lg, int W, int A, int n, int k, int* __restrict__ hdr,
+                                                             u64* __restrict__ cand_all) {
+    __shared__ int h[RPN_BINS];
+    __shared__ int wtot[16];
+    __shared__ int res[2];
+    const int img = blockIdx.y, lane = threadIdx.x & 63;
+    int* g = hdr + (long long)img * RPN_HDR;
+    for (int i = threadIdx.x; i < RPN_BINS; i += 256) h[i] = g[i];
+    __syncthreads();
+    rpn_find_digit(h, RPN_BINS, k, wtot, res);
+    const unsigned cut = (unsigned)res[0];
+    u64* cand = cand_all + (long long)img * n;
+    for (int i0 = blockIdx.x * 256; i0 < n; i0 += gridDim.x * 256) {
+        const int i = i0 + threadIdx.x;
+        u64 c = 0;
+        bool take = false;
+        if (i < n) {
+            c = rpn_word(*rpn_at(lg, img, i, W, A), i);
+            take = (unsigned)(c >> (RPN_IDX_BITS + 20)) >= cut;
+        }
+        const u64 m = __ballot(take);
+        if (m) {
+            const int first = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == first) base = atomicAdd(&g[RPN_BINS], __popcll(m));
+            base = __shfl(base, first, 64);
+            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (take && pos < n) cand[pos] = c;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ top-k: select k of m words, sort, write
+// DIRECT: the m = n words are formed from the logits; else they are the filter's list (hdr[RPN_BINS] of them).  One block per image.
+template <bool DIRECT>
+__global__ __launch_bounds__(1024) void afi_rpn_pick_kernel(const AfiView lg, int W, int A, int n, int k, const int* __restrict__ hdr,
+                                                            const u64* __restrict__ cand_all, float* __restrict__ vals, int* __restrict__ idx,
+                                                            long long ld) {
+    __shared__ int hist[2048];
+    __shared__ int wtot[16];
+    __shared__ int res[2];
+    __shared__ u64 sel[RPN_MAXK];
+    __shared__ int nsel;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    int m = n;
+    const u64* cand = nullptr;
+    if (!DIRECT) {
+        m = hdr[(long long)img * RPN_HDR + RPN_BINS];
+        m = m < 0 ? 0 : (m > n ? n : m);
+        cand = cand_all + (long long)img * n;
+    }
+    auto word = [&](int i) -> u64 { return DIRECT ? rpn_word(*rpn_at(lg, img, i, W, A), i) : cand[i]; };
+    int need = k < m ? k : m, group = m, shift = 32 + RPN_IDX_BITS;
+    u64 prefix = 0;
+    const int widths[5] = {11, 11, 10, 11, 11};
+    for (int p = 0; p < 5 && need < group; ++p) {
+        const int bits = widths[p], nb = 1 << bits;
+        shift -= bits;
+        for (int i = tid; i < nb; i += 1024) hist[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < m; i += 1024) {
+            const u64 c = word(i);
+            if ((c >> (shift + bits)) == prefix) atomicAdd(&hist[(int)(c >> shift) & (nb - 1)], 1);
+        }
+        __syncthreads();
+        rpn_find_digit(hist, nb, need, wtot, res);
+        need -= res[1];
+        group = hist[res[0]];
+        prefix = (prefix << bits) | (u64)res[0];
+        __syncthreads();
+    }
+    // the words above the open group and the group itself (taken whole): min(k, m) words
+    if (tid == 0) nsel = 0;
+    __syncthreads();
+    for (int i = tid; i < m; i += 1024) {
+        const u64 c = word(i);
+        if ((c >> shift) >= prefix) {
+            const int s = atomicAdd(&nsel, 1);
+            if (s < RPN_MAXK) sel[s] = c;
+        }
+    }
+    __syncthreads();
+    const int ns = nsel < RPN_MAXK ? nsel : RPN_MAXK;
+    if (tid >= ns) sel[tid] = 0;                       // below every real word (a real word's index field is never all ones: n <= RPN_IDX_MASK)
+    __syncthreads();
+    for (int ksz = 2; ksz <= RPN_MAXK; ksz <<= 1)
+        for (int j = ksz >> 1; j > 0; j >>= 1) {
+            const int o = tid ^ j;
+            if (o > tid) {
+                const u64 a = sel[tid], b = sel[o];
+                const bool desc = (tid & ksz) == 0;
+                if (desc ? a < b : a > b) { sel[tid] = b; sel[o] = a; }
+            }
+            __syncthreads();
+        }
+    if (tid < k) {
+        const u64 c = sel[tid];
+        int i = (int)((~(unsigned)c) & RPN_IDX_MASK);
+        if (c == 0 || i >= n) i = 0;                   // (never: k <= m real words)
+        idx[(long long)img * ld + tid] = i;
+        vals[(long long)img * ld + tid] = *rpn_at(lg, img, i, W, A);
+    }
+}
+
+long long afi_rpn_topk_ws_floats(int N, int H, int W, int A) {
+    if (N <= 0 || H <= 0 || W <= 0 || A <= 0 || A > RPN_MAX_A) return -1;
+    const long long n = (long long)H * W * A;
+    if (n >= RPN_IDX_MASK) return -1;
+    if (n <= RPN_DIRECT_MAX) return 0;
+    return (long long)N * RPN_HDR + 2 * (long long)N * n;
+}
+
+int afi_rpn_topk(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                 void* stream) {
+    if (!logits.p || !vals || !idx || N <= 0 || N > 65535 || H <= 0 || W <= 0 || A <= 0 || k <= 0 || ld < k) return AFI_ERR_BAD_ARG;
+    const long long nn = (long long)H * W * A;
+    if (A > RPN_MAX_A || k > RPN_MAXK || nn >= RPN_IDX_MASK) return AFI_ERR_UNSUPPORTED;
+    if (k > nn) return AFI_ERR_BAD_ARG;
+    const int n = (int)nn;
+    const AfiView lg{(float*)logits.p, logits.sN, logits.sH, logits.sW};
+    hipStream_t st = (hipStream_t)stream;
+    if (n <= RPN_DIRECT_MAX) {
+        hipLaunchKernelGGL(afi_rpn_pick_kernel<true>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)nullptr, (const u64*)nullptr, vals,
+                           idx, ld);
+        return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+    }
+    const long long need = afi_rpn_topk_ws_floats(N, H, W, A);
+    if (!ws || ws_floats < need || ((uintptr_t)ws & 7)) return AFI_ERR_WORKSPACE;
+    int* hdr = (int*)ws;
+    u64* cand = (u64*)(hdr + (long long)N * RPN_HDR);          // N * RPN_HDR ints: a multiple of 8 bytes
+    hipLaunchKernelGGL(afi_rpn_zero_kernel, dim3((N * RPN_HDR + 255) / 256), dim3(256), 0, st, hdr, N * RPN_HDR);      // histograms, list lengths
+    int gx = (n + 256 * 8 - 1) / (256 * 8);
+    if (gx > 512) gx = 512;
+    hipLaunchKernelGGL(afi_rpn_hist_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, hdr);
+    hipLaunchKernelGGL(afi_rpn_filter_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, k, hdr, cand);
+    hipLaunchKernelGGL(afi_rpn_pick_kernel<false>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)hdr, (const u64*)cand, vals, idx, ld);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ decode
+struct RpnDecode {
+    int N, H, W, A, k, stride;
+    float wx, wy, ww, wh;
+    double clamp;
+    float min_size;
+};
+
+__global__ __launch_bounds__(256) void afi_rpn_decode_kernel(const AfiView dl, const RpnDecode d, const float* __restrict__ cell,
+                                                             const int* __restrict__ idx, long long ld, const float* __restrict__ image_hw,
+                                                             float* __restrict__ boxes, int* __restrict__ valid) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= d.N * d.k) return;
+    const int img = t / d.k, j = t - img * d.k;
+    const long long o = (long long)img * ld + j;
+    const int i = idx[o];
+    float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
+    int ok = 0;
+    if (i >= 0 && i < d.H * d.W * d.A) {
+        const int pix = i / d.A, a = i - pix * d.A, y = pix / d.W, x = pix - y * d.W;
+        const float* q = dl.p + (long long)img * dl.sN + (long long)y * dl.sH + (long long)x * dl.sW + 4 * a;
+        // in fp64: pcx = dx w + cx cancels when a delta moves a far anchor back towards the origin, and the fp32 rounding of the anchor's
+        // own coordinates (up to half an ulp of x stride) would then exceed every bound stated relative to |pcx| + pw.  2000 boxes per level.
+        const double sx = (double)(x * d.stride), sy = (double)(y * d.stride);
+        const double ax1 = (double)cell[4 * a] + sx, ay1 = (double)cell[4 * a + 1] + sy, ax2 = (double)cell[4 * a + 2] + sx,
+                     ay2 = (double)cell[4 * a + 3] + sy;
+        const double w = ax2 - ax1, h = ay2 - ay1, cx = ax1 + 0.5 * w, cy = ay1 + 0.5 * h;
+        const double dx = (double)q[0] / (double)d.wx, dy = (double)q[1] / (double)d.wy;
+        const double dw = fmin((double)q[2] / (double)d.ww, d.clamp), dh = fmin((double)q[3] / (double)d.wh, d.clamp);
+        const double pcx = dx * w + cx, pcy = dy * h + cy, pw = exp(dw) * w, ph = exp(dh) * h;
+        const float ih = image_hw[2 * img], iw = image_hw[2 * img + 1];
+        x1 = fminf(fmaxf((float)(pcx - 0.5 * pw), 0.f), iw);
+        y1 = fminf(fmaxf((float)(pcy - 0.5 * ph), 0.f), ih);
+        x2 = fminf(fmaxf((float)(pcx + 0.5 * pw), 0.f), iw);
+        y2 = fminf(fmaxf((float)(pcy + 0.5 * ph), 0.f), ih);
+        ok = (x2 - x1 > d.min_size) && (y2 - y1 > d.min_size);
+    }
+    float* b = boxes + 4 * o;
+    b[0] = x1; b[1] = y1; b[2] = x2; b[3] = y2;
+    valid[o] = ok;
+}
+
+int afi_rpn_decode(afi_view_t deltas, int N, int H, int W, int A, const float* cell_anchors, int stride, const int* idx, int k, long long ld,
+                   const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, float min_size, float* boxes, int* valid,
+                   void* stream) {
+    if (!deltas.p || !cell_anchors || !idx || !image_hw || !boxes || !valid || N <= 0 || H <= 0 || W <= 0 || A <= 0 || stride <= 0 || k <= 0 ||
+        ld < k)
+        return AFI_ERR_BAD_ARG;
+    if (A > RPN_MAX_A || (long long)H * W * A >= RPN_IDX_MASK || (long long)N * k > (1ll << 30)) return AFI_ERR_UNSUPPORTED;
+    if (!(wx > 0.f) || !(wy > 0.f) || !(ww > 0.f) || !(wh > 0.f)) return AFI_ERR_BAD_ARG;
+    const AfiView dl{(float*)deltas.p, deltas.sN, deltas.sH, deltas.sW};
+    const RpnDecode d{N, H, W, A, k, stride, wx, wy, ww, wh, scale_clamp, min_size};
+    hipLaunchKernelGGL(afi_rpn_decode_kernel, dim3((N * k + 255) / 256), dim3(256), 0, (hipStream_t)stream, dl, d, cell_anchors, idx, ld, image_hw,
+                       boxes, valid);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ NMS
+__device__ __forceinline__ u64 rpn_readlane64(u64 v, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
+    return ((u64)hi << 32) | lo;
+}
+
+// One block (sixteen waves) per image.  mask[i][w] bit j: box 64 w + j (later than i in the list) overlaps box i by more than thresh.
+__global__ __launch_bounds__(1024) void afi_rpn_nms_kernel(const float* __restrict__ boxes, const int* __restrict__ valid, int k, long long ld,
+                                                           float thresh, int* __restrict__ keep) {
+#pragma clang fp contract(off)                          // the overlap test is the stated fp32 expression, operation by operation
+    __shared__ u64 mask[RPN_MAXK * 16];
+    __shared__ float4 bx[RPN_MAXK];
+    __shared__ int vd[RPN_MAXK];
+    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = (k + 63) >> 6;
+    {
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        int v = 0;
+        if (tid < k) {
+            const float* q = boxes + 4 * ((long long)img * ld + tid);
+            b = make_float4(q[0], q[1], q[2], q[3]);
+            v = valid[(long long)img * ld + tid] != 0;
+        }
+        bx[tid] = b;
+        vd[tid] = v;
+    }
+    __syncthreads();
+    for (int w = 0; w < nw; ++w) {
+        const int j = 64 * w + lane;
+        const float4 c = bx[j];
+        const float carea = (c.z - c.x) * (c.w - c.y);
+        const bool cok = j < k && vd[j];
+        const int rows = 64 * (w + 1) < k ? 64 * (w + 1) : k;
+        for (int i = wave; i < rows; i += 16) {
+            const float4 r = bx[i];
+            const float iw = fmaxf(fminf(r.z, c.z) - fmaxf(r.x, c.x), 0.f), ih = fmaxf(fminf(r.w, c.w) - fmaxf(r.y, c.y), 0.f);
+            const float inter = iw * ih, rarea = (r.z - r.x) * (r.w - r.y);
+            const bool hit = cok && j > i && (inter / (rarea + carea - inter) > thresh);
+            const u64 word = __ballot(hit);
+            if (lane == 0) mask[i * 16 + w] = word;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    u64 remv = 0;                                       // lane w < 16: word w of the boxes suppressed so far
+    const int wsel = lane & 15, sub = lane >> 4;
+    for (int c = 0; c < nw; ++c) {
+        const int row = 64 * c + lane;
+        const u64 diag = (row < k) ? mask[row * 16 + c] : 0ull;
+        const u64 V = __ballot(row < k && vd[row]);
+        u64 R = rpn_readlane64(remv, c) | ~V;           // an invalid box is neither kept nor suppresses anything
+        u64 K = 0;
+#pragma unroll
+        for (int b = 0; b < 64; ++b) {
+            if (!((R >> b) & 1ull)) {
+                K |= 1ull << b;
+                R |= rpn_readlane64(diag, b);
+            }
+        }
+        if (row < k) keep[(long long)img * ld + row] = (int)((K >> lane) & 1ull);
+        // OR the kept rows' words into remv: lane = (word wsel, rows sub, sub + 4, ...)
+        u64 acc = 0;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int b = sub + 4 * t;
+            if (wsel > c && wsel < nw && ((K >> b) & 1ull)) acc |= mask[(64 * c + b) * 16 + wsel];
+        }
+        acc |= __shfl_xor(acc, 16, 64);
+        acc |= __shfl_xor(acc, 32, 64);
+        remv |= acc;                                    // lanes >= 16 hold copies of words lane & 15: never read
+    }
+}
+
+int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld, float thresh, int* keep, void* stream) {
+    if (N <= 0 || N > 65535 || k < 0 || ld < k) return AFI_ERR_BAD_ARG;
+    if (k == 0) return AFI_OK;
+    if (!boxes || !valid || !keep) return AFI_ERR_BAD_ARG;
+    if (k > RPN_MAXK) return AFI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(afi_rpn_nms_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, valid, k, ld, thresh, keep);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ merge
+// boxes [N][Ktot][4], vals / keep [N][Ktot]: the levels side by side, level l in columns [off[l], off[l + 1]), each sorted by afi_rpn_topk.
+__global__ __launch_bounds__(1024) void afi_rpn_merge_kernel(const float* __restrict__ boxes, const float* __restrict__ vals,
+                                                             const int* __restrict__ keep, const RpnLevels lv, int post_k,
+                                                             float* __restrict__ ob, float* __restrict__ ol, int* __restrict__ counts) {
+    __shared__ unsigned ckey[RPN_MAX_LEVELS * RPN_MAXK];
+    __shared__ unsigned short cpos[RPN_MAX_LEVELS * RPN_MAXK];
+    __shared__ int cnt[RPN_MAX_LEVELS];
+    __shared__ int wtot[16];
+    const int img = blockIdx.x, tid = threadIdx.x, Ktot = lv.off[lv.L];
+    const long long row0 = (long long)img * Ktot;
+    for (int l = 0; l < lv.L; ++l) {
+        const int o = lv.off[l], kl = lv.off[l + 1] - o;
+        const int f = (tid < kl) && keep[row0 + o + tid] != 0;
+        int tot;
+        const int inc = rpn_block_scan(f, wtot, &tot);
+        if (f) {
+            ckey[o + inc - 1] = rpn_key(vals[row0 + o + tid]);
+            cpos[o + inc - 1] = (unsigned short)(o + tid);
+        }
+        if (tid == 0) cnt[l] = tot;
+    }
+    __syncthreads();
+    int total = 0;
+    for (int l = 0; l < lv.L; ++l) total += cnt[l];
+    for (int l = 0; l < lv.L; ++l) {
+        if (tid >= cnt[l]) continue;
+        const unsigned key = ckey[lv.off[l] + tid];
+        int rank = tid;
+        for (int b = 0; b < lv.L && rank < post_k; ++b) {
+            if (b == l) continue;
+            const unsigned* arr = ckey + lv.off[b];
+            int lo = 0, hi = cnt[b];
+            while (lo < hi) {                          // entries of level b in front: >= key for an earlier level, > key for a later one
+                const int mid = (lo + hi) >> 1;
+                const bool front = b < l ? arr[mid] >= key : arr[mid] > key;
+                if (front) lo = mid + 1; else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < post_k) {
+            const long long src = row0 + cpos[lv.off[l] + tid], dst = (long long)img * post_k + rank;
+            const float* q = boxes + 4 * src;
+            float* p = ob + 4 * dst;
+            p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; p[3] = q[3];
+            ol[dst] = vals[src];
+        }
+    }
+    const int c = total < post_k ? total : post_k;
+    if (tid == 0) counts[img] = c;
+    for (int r = c + tid; r < post_k; r += 1024) {
+        const long long dst = (long long)img * post_k + r;
+        float* p = ob + 4 * dst;
+        p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; p[3] = 0.f;
+        ol[dst] = 0.f;
+    }
+}
+
+int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                  float* out_logits, int* counts, void* stream) {
+    if (!boxes || !vals || !keep || !level_off || !out_boxes || !out_logits || !counts || N <= 0 || N > 65535 || L <= 0 || post_k <= 0)
+        return AFI_ERR_BAD_ARG;
+    if (L > RPN_MAX_LEVELS) return AFI_ERR_UNSUPPORTED;
+    RpnLevels lv;
+    lv.L = L;
+    if (level_off[0] != 0) return AFI_ERR_BAD_ARG;
+    for (int l = 0; l <= RPN_MAX_LEVELS; ++l) lv.off[l] = level_off[l < L ? l : L];
+    for (int l = 0; l < L; ++l) {
+        const int kl = level_off[l + 1] - level_off[l];
+        if (kl < 0) return AFI_ERR_BAD_ARG;
+        if (kl > RPN_MAXK) return AFI_ERR_UNSUPPORTED;
+    }
+    if (level_off[L] <= 0) return AFI_ERR_BAD_ARG;
+    hipLaunchKernelGGL(afi_rpn_merge_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes, out_logits,
+                       counts);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}

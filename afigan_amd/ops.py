@@ -839,6 +839,120 @@ def swin_window_attn(qkv, qkv_bias, bias_img, window, shift):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ RPN selection (rpn.py)
+RPN_MAX_TOPK = 1024                         # per-level list length the selection kernels hold in LDS
+RPN_MAX_ANCHORS = 16
+RPN_MAX_LEVELS = 8
+
+
+def _check_i32(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise _lib.AfiError("the RPN selection runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != torch.int32:
+            raise _lib.AfiError(f"int32 expected, got {t.dtype}")
+
+
+def _rpn_rows(t, k, inner=()):
+    """`t` is rows of one level's list: [N, >= k, *inner], dense inside a row; returns the row stride in list elements."""
+    per = 1
+    for s in inner:
+        per *= s
+    if t.dim() != 2 + len(inner) or t.shape[1] < k or tuple(t.shape[2:]) != tuple(inner) or not t[0].is_contiguous() or t.stride(0) % per:
+        raise _lib.AfiError(f"rpn: a list buffer [N, >= {k}{''.join(', ' + str(s) for s in inner)}] with dense rows expected, got shape "
+                            f"{tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) // per
+
+
+def rpn_topk(head, A, k, vals=None, idx=None):
+    """The k highest of channels 0..A-1 of the pixel-major head output [N, Cpad, H, W], per image: (vals [N, k] fp32, idx [N, k] int32), sorted
+    by (logit descending, anchor index (y W + x) A + a ascending); NaN below every number (afi_rpn_topk).  vals / idx may be column slices of wider
+    [N, K] buffers (the levels of an image side by side)."""
+    _check_cuda(head)
+    N, Cp, H, W = head.shape
+    if not 0 < A <= min(Cp, RPN_MAX_ANCHORS) or not 0 < k <= min(RPN_MAX_TOPK, H * W * A):
+        raise _lib.AfiError(f"rpn_topk: A {A} (1..{min(Cp, RPN_MAX_ANCHORS)}), k {k} (1..{min(RPN_MAX_TOPK, H * W * A)}) for a head of shape {tuple(head.shape)}")
+    if vals is None:
+        vals = torch.empty((N, k), device=head.device, dtype=torch.float32)
+        idx = torch.empty((N, k), device=head.device, dtype=torch.int32)
+    _check_cuda(vals)
+    _check_i32(idx)
+    ld = _rpn_rows(vals, k)
+    if vals.shape[0] != N or idx.shape[0] != N or _rpn_rows(idx, k) != ld:
+        raise _lib.AfiError("rpn_topk: vals and idx must be [N, >= k] with one row stride")
+    n = _lib.load().afi_rpn_topk_ws_floats(N, H, W, A)
+    if n < 0:
+        raise _lib.AfiError(f"rpn_topk: unsupported map {H}x{W}x{A}")
+    ws = new_workspace(n, head.device) if n else None
+    call("afi_rpn_topk", view_of(head), N, H, W, A, k, _p(vals), _p(idx), ld, _p(ws), n, stream_ptr())
+    return vals, idx
+
+
+def rpn_decode(head, c0, A, cell_anchors, stride, idx, k, image_hw, weights=(1.0, 1.0, 1.0, 1.0), scale_clamp=4.135166556742356, min_size=0.0,
+               boxes=None, valid=None):
+    """Boxes of the anchors idx [N, k] of one level: deltas = channels c0 + 4 a + c of the pixel-major head output, anchors from the index and
+    cell_anchors [A, 4], Box2BoxTransform(weights) with dw / dh clamped at scale_clamp, clipped to image_hw [N, 2] (device fp32: height, width);
+    returns (boxes [N, k, 4], valid [N, k] int32 = both sides > min_size) (afi_rpn_decode)."""
+    _check_cuda(head, cell_anchors, image_hw)
+    _check_i32(idx)
+    N, Cp, H, W = head.shape
+    if not 0 < A <= RPN_MAX_ANCHORS or c0 < 0 or c0 + 4 * A > Cp or tuple(cell_anchors.shape) != (A, 4) or tuple(image_hw.shape) != (N, 2):
+        raise _lib.AfiError(f"rpn_decode: head {tuple(head.shape)}, deltas at channel {c0}, A {A}, cell anchors {tuple(cell_anchors.shape)}, "
+                            f"image sizes {tuple(image_hw.shape)}")
+    if boxes is None:
+        boxes = torch.empty((N, k, 4), device=head.device, dtype=torch.float32)
+        valid = torch.empty((N, k), device=head.device, dtype=torch.int32)
+    _check_cuda(boxes)
+    _check_i32(valid)
+    ld = _rpn_rows(idx, k)
+    if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(valid, k) != ld or not (idx.shape[0] == boxes.shape[0] == valid.shape[0] == N):
+        raise _lib.AfiError("rpn_decode: idx, boxes and valid must be lists of one row stride")
+    v = view_of(head)
+    v.p += 4 * c0
+    call("afi_rpn_decode", v, N, H, W, A, _p(cell_anchors.contiguous()), int(stride), _p(idx), k, ld, _p(image_hw.contiguous()),
+         *[float(w) for w in weights], float(scale_clamp), float(min_size), _p(boxes), _p(valid), stream_ptr())
+    return boxes, valid
+
+
+def rpn_nms(boxes, valid, thresh, keep=None):
+    """Greedy NMS of the lists boxes [N, k, 4] (k <= 1024, in score order), valid [N, k] int32: keep [N, k] int32 (afi_rpn_nms)."""
+    _check_cuda(boxes)
+    _check_i32(valid)
+    N, k = valid.shape
+    if keep is None:
+        keep = torch.empty((N, k), device=boxes.device, dtype=torch.int32)
+    _check_i32(keep)
+    if k > RPN_MAX_TOPK:
+        raise _lib.AfiError(f"rpn_nms: lists of at most {RPN_MAX_TOPK} boxes, got {k}")
+    if k == 0:
+        return keep
+    ld = _rpn_rows(valid, k)
+    if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(keep, k) != ld or not (boxes.shape[0] == keep.shape[0] == N):
+        raise _lib.AfiError("rpn_nms: boxes, valid and keep must be lists of one row stride")
+    call("afi_rpn_nms", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), stream_ptr())
+    return keep
+
+
+def rpn_merge(boxes, vals, keep, level_off, post_k):
+    """The kept entries of every level of an image in (logit descending, level, rank) order, the first post_k: boxes [N, K, 4], vals / keep
+    [N, K] dense with level l in columns [level_off[l], level_off[l + 1]); returns (boxes [N, post_k, 4], logits [N, post_k], counts [N] int32),
+    rows past counts zero (afi_rpn_merge)."""
+    _check_cuda(boxes, vals)
+    _check_i32(keep)
+    N, K = vals.shape
+    L = len(level_off) - 1
+    if not (boxes.is_contiguous() and vals.is_contiguous() and keep.is_contiguous()) or tuple(boxes.shape) != (N, K, 4) or tuple(keep.shape) != (N, K) \
+            or level_off[0] != 0 or level_off[-1] != K or not 0 < L <= RPN_MAX_LEVELS or post_k <= 0:
+        raise _lib.AfiError(f"rpn_merge: dense boxes [N, K, 4], vals / keep [N, K] and 1..{RPN_MAX_LEVELS} levels ending at K expected, got "
+                            f"{tuple(boxes.shape)}, {tuple(vals.shape)}, {tuple(keep.shape)}, offsets {list(level_off)}")
+    ob = torch.empty((N, post_k, 4), device=boxes.device, dtype=torch.float32)
+    ol = torch.empty((N, post_k), device=boxes.device, dtype=torch.float32)
+    counts = torch.empty((N,), device=boxes.device, dtype=torch.int32)
+    off = (C.c_int * (L + 1))(*[int(o) for o in level_off])
+    call("afi_rpn_merge", _p(boxes), _p(vals), _p(keep), N, L, off, int(post_k), _p(ob), _p(ol), _p(counts), stream_ptr())
+    return ob, ol, counts
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

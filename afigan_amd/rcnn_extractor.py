@@ -1,9 +1,10 @@
 """``GeneralizedRCNN_AFExtractor`` (afigan/modeling/meta_arch/rcnn_extractor.py:21-147): the stage-2 detector, a GeneralizedRCNN that runs on
 ``image_x0.5`` and ALSO hands back its FPN features, which the stage-2 loop trains against the guide network's.
 
-The backbone is the AFI pyramid of this package (FPN_AFIGAN / PAFPN_AFIGAN through BACKBONE_REGISTRY); the proposal generator and the
-ROI heads are detectron2 components outside this package's scope: ``from_config`` builds them with detectron2 when it is importable,
-and the constructor takes any callables with their contracts otherwise (tests use small stand-ins)."""
+The backbone is the AFI pyramid of this package (FPN_AFIGAN / PAFPN_AFIGAN through BACKBONE_REGISTRY); the proposal generator is
+detectron2's when it is importable and this package's frozen, inference-only ``rpn.RPN`` otherwise; the ROI heads are detectron2
+components outside this package's scope: ``from_config`` builds them with detectron2 when it is importable, and the constructor takes any
+callables with their contracts otherwise (tests use small stand-ins)."""
 import torch
 import torch.nn as nn
 
@@ -51,12 +52,16 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
         backbone = BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg, ShapeSpec(channels=len(cfg.MODEL.PIXEL_MEAN), stride=None))
         try:
             from detectron2.modeling.proposal_generator import build_proposal_generator
+        except Exception:
+            from .rpn import build_proposal_generator                  # the frozen, inference-only RPN of this package
+        proposal_generator = build_proposal_generator(cfg, backbone.output_shape())
+        try:
             from detectron2.modeling.roi_heads import build_roi_heads
         except Exception as e:
             from ._lib import AfiError
-            raise AfiError(f"building the RPN / ROI heads from a config needs detectron2 ({type(e).__name__}: {e}); "
+            raise AfiError(f"building the ROI heads from a config needs detectron2 ({type(e).__name__}: {e}); "
                            "pass proposal_generator= and roi_heads= instead")
-        return backbone, build_proposal_generator(cfg, backbone.output_shape()), build_roi_heads(cfg, backbone.output_shape())
+        return backbone, proposal_generator, build_roi_heads(cfg, backbone.output_shape())
 
     def preprocess_image(self, batched_inputs):
         """rcnn_extractor.py:120-127: the detector sees the HALF-size image of the dual-scale mapper."""

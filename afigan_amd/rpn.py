@@ -1,0 +1,307 @@
+"""The frozen RPN proposal generator of the inference configs: detectron2 v0.1.1's ``RPN`` (``StandardRPNHead``, ``DefaultAnchorGenerator``,
+``Box2BoxTransform``, ``find_top_rpn_proposals``) at inference, forward only, on this package's HIP kernels.
+
+Per level l of ``MODEL.RPN.IN_FEATURES`` (stride s, map H x W, A anchors per cell):
+  - head: t = relu(conv3x3(x)); objectness_logits = conv1x1(t) [A channels], anchor_deltas = conv1x1(t) [4A channels, 4a + c]; one set of weights;
+  - anchors: cell anchor a = (-w/2, -h/2, w/2, h/2), w = sqrt(size^2 / ratio), h = ratio w (sizes, then ratios); anchor (y W + x) A + a is the
+    cell anchor shifted by (x s, y s).  Never materialised: the kernels form an anchor from its index and the ``cell_anchors`` buffer;
+  - the min(PRE_NMS_TOPK_TEST, H W A) highest logits per image, equal logits in ascending anchor index (detectron2's sort leaves ties open;
+    this is the rule here), NaN below every number;
+  - Box2BoxTransform(BBOX_REG_WEIGHTS).apply_deltas with dw / dh clamped at log(1000 / 16), clip to the image's own un-padded size, drop
+    boxes with a side <= PROPOSAL_GENERATOR.MIN_SIZE;
+  - greedy NMS per image and level (batched_nms with the level as the category), inter / (area_a + area_b - inter) > NMS_THRESH in fp32;
+then the survivors of all levels by logit (ties: level, then rank), the first POST_NMS_TOPK_TEST.
+
+Keys: ``rpn_head.{conv, objectness_logits, anchor_deltas}.{weight, bias}`` and the buffers ``anchor_generator.cell_anchors.{l}`` [A, 4] --
+detectron2's, so a detector checkpoint's ``proposal_generator.*`` loads with strict=True.  Every parameter has requires_grad False.
+
+Kernels: the 3x3 conv + ReLU is afi_conv3x3_wino_infer / afi_conv3x3_fwd (the regime rule of resnet_guide), the two 1x1 convs ONE
+afi_conv1x1_fwd over their concatenated weights (A + 4A channels, zero-padded to a multiple of 4; rebuilt when a parameter changes: version,
+storage, device); selection afi_rpn_topk, afi_rpn_decode, afi_rpn_nms per level and one afi_rpn_merge (csrc/rpn.hip).  No torch sort / topk /
+conv, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host read and can be captured in a hipGraph; ``forward`` reads ``counts`` once.
+
+Out of scope (AfiError): losses, label assignment and training (``gt_instances``, a training-mode call with gradients enabled), rotated
+anchors, heads other than StandardRPNHead, PRE_NMS_TOPK_TEST above 1024, more than 16 anchors per cell, more than 8 levels, CPU tensors,
+2-byte features."""
+import math
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import AfiError
+from .registry import Registry
+from .resnet_guide import _conv3x3, _get
+
+SCALE_CLAMP = math.log(1000.0 / 16)                    # Box2BoxTransform's _DEFAULT_SCALE_CLAMP
+
+
+def _d2_registry():
+    try:
+        from detectron2.modeling.proposal_generator import PROPOSAL_GENERATOR_REGISTRY as reg
+        return reg
+    except Exception:
+        return None
+
+
+_D2 = _d2_registry()
+# detectron2's own "RPN" owns the name there: its registry is used only when the name is free
+PROPOSAL_GENERATOR_REGISTRY = _D2 if _D2 is not None and "RPN" not in _D2 else Registry("PROPOSAL_GENERATOR")
+
+
+def generate_cell_anchors(sizes, aspect_ratios):
+    """DefaultAnchorGenerator.generate_cell_anchors: [len(sizes) len(ratios), 4] fp32 (x1, y1, x2, y2) around the origin, sizes then ratios."""
+    out = []
+    for size in sizes:
+        area = float(size) ** 2.0
+        for ratio in aspect_ratios:
+            w = math.sqrt(area / ratio)
+            h = ratio * w
+            out.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
+    return torch.tensor(out, dtype=torch.float32)
+
+
+class BufferList(nn.Module):
+    """detectron2's BufferList: buffers named "0", "1", ... (the state-dict keys ``cell_anchors.{l}``)."""
+
+    def __init__(self, buffers):
+        super().__init__()
+        for i, b in enumerate(buffers):
+            self.register_buffer(str(i), b)
+
+    def __len__(self):
+        return len(self._buffers)
+
+    def __iter__(self):
+        return iter(self._buffers.values())
+
+    def __getitem__(self, i):
+        return self._buffers[str(i)]
+
+
+class DefaultAnchorGenerator(nn.Module):
+    def __init__(self, sizes, aspect_ratios, strides, offset=0.0):
+        super().__init__()
+        n = len(strides)
+        sizes, aspect_ratios = [list(s) for s in sizes], [list(r) for r in aspect_ratios]
+        if len(sizes) == 1:
+            sizes = sizes * n
+        if len(aspect_ratios) == 1:
+            aspect_ratios = aspect_ratios * n
+        if len(sizes) != n or len(aspect_ratios) != n:
+            raise AfiError(f"rpn: ANCHOR_GENERATOR.SIZES / ASPECT_RATIOS need one entry, or one per input feature ({n}); got {len(sizes)} / "
+                           f"{len(aspect_ratios)}")
+        if float(offset) != 0.0:
+            raise AfiError(f"rpn: ANCHOR_GENERATOR.OFFSET {offset} is not supported (detectron2 v0.1.1 places anchors at offset 0)")
+        self.strides = [int(s) for s in strides]
+        self.cell_anchors = BufferList([generate_cell_anchors(s, r) for s, r in zip(sizes, aspect_ratios)])
+
+    @property
+    def num_cell_anchors(self):
+        return [int(c.shape[0]) for c in self.cell_anchors]
+
+
+class StandardRPNHead(nn.Module):
+    def __init__(self, in_channels, num_cell_anchors, box_dim=4):
+        super().__init__()
+        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
+        self.objectness_logits = nn.Conv2d(in_channels, num_cell_anchors, kernel_size=1, stride=1)
+        self.anchor_deltas = nn.Conv2d(in_channels, num_cell_anchors * box_dim, kernel_size=1, stride=1)
+        for layer in (self.conv, self.objectness_logits, self.anchor_deltas):      # detectron2's initialisation
+            nn.init.normal_(layer.weight, std=0.01)
+            nn.init.constant_(layer.bias, 0)
+
+
+class Boxes:
+    """The part of detectron2's Boxes the detector path reads: ``.tensor`` [n, 4]."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+    def to(self, device):
+        return Boxes(self.tensor.to(device))
+
+
+class Proposals:
+    """One image's proposals when detectron2's Instances is not importable: ``image_size``, ``proposal_boxes``, ``objectness_logits``."""
+
+    def __init__(self, image_size, proposal_boxes, objectness_logits):
+        self.image_size, self.proposal_boxes, self.objectness_logits = image_size, proposal_boxes, objectness_logits
+
+    def __len__(self):
+        return len(self.proposal_boxes)
+
+    def to(self, device):
+        return Proposals(self.image_size, self.proposal_boxes.to(device), self.objectness_logits.to(device))
+
+
+def _make_proposals(image_size, boxes, logits):
+    try:
+        from detectron2.structures import Boxes as D2Boxes, Instances
+    except Exception:
+        return Proposals(tuple(image_size), Boxes(boxes), logits)
+    r = Instances(tuple(image_size))
+    r.proposal_boxes = D2Boxes(boxes)
+    r.objectness_logits = logits
+    return r
+
+
+@PROPOSAL_GENERATOR_REGISTRY.register()
+class RPN(nn.Module):
+    def __init__(self, cfg, input_shape):
+        super().__init__()
+        m = cfg.MODEL
+        ag, r, pg = _get(m, "ANCHOR_GENERATOR", None), _get(m, "RPN", None), _get(m, "PROPOSAL_GENERATOR", None)
+        if r is None or ag is None:
+            raise AfiError("rpn: the config has no MODEL.RPN / MODEL.ANCHOR_GENERATOR section (afigan_amd.config.get_cfg declares them)")
+        if _get(ag, "NAME", "DefaultAnchorGenerator") != "DefaultAnchorGenerator":
+            raise AfiError(f"rpn: MODEL.ANCHOR_GENERATOR.NAME {ag.NAME!r} is not supported (DefaultAnchorGenerator only: rotated anchors are out of scope)")
+        if _get(r, "HEAD_NAME", "StandardRPNHead") != "StandardRPNHead":
+            raise AfiError(f"rpn: MODEL.RPN.HEAD_NAME {r.HEAD_NAME!r} is not supported (StandardRPNHead only)")
+        self.in_features = list(r.IN_FEATURES)
+        missing = [f for f in self.in_features if f not in input_shape]
+        if missing or not self.in_features:
+            raise AfiError(f"rpn: MODEL.RPN.IN_FEATURES {self.in_features} are not all outputs of the backbone ({sorted(input_shape)})")
+        if len(self.in_features) > ops.RPN_MAX_LEVELS:
+            raise AfiError(f"rpn: at most {ops.RPN_MAX_LEVELS} input features, got {len(self.in_features)}")
+        self.pre_nms_topk = int(_get(r, "PRE_NMS_TOPK_TEST", 6000))
+        if not 0 < self.pre_nms_topk <= ops.RPN_MAX_TOPK:
+            raise AfiError(f"rpn: MODEL.RPN.PRE_NMS_TOPK_TEST {self.pre_nms_topk} is outside 1..{ops.RPN_MAX_TOPK}, the per-level list the selection "
+                           f"kernels hold (detectron2's default of 6000 is above it; every reference config sets 1000)")
+        self.post_nms_topk = int(_get(r, "POST_NMS_TOPK_TEST", 1000))
+        if self.post_nms_topk <= 0:
+            raise AfiError(f"rpn: MODEL.RPN.POST_NMS_TOPK_TEST {self.post_nms_topk} must be positive")
+        self.nms_thresh = float(_get(r, "NMS_THRESH", 0.7))
+        self.min_box_side_len = float(_get(pg, "MIN_SIZE", 0))
+        self.box_weights = tuple(float(w) for w in _get(r, "BBOX_REG_WEIGHTS", (1.0, 1.0, 1.0, 1.0)))
+        if len(self.box_weights) != 4 or min(self.box_weights) <= 0:
+            raise AfiError(f"rpn: MODEL.RPN.BBOX_REG_WEIGHTS {self.box_weights} must be four positive numbers")
+        shapes = [input_shape[f] for f in self.in_features]
+        channels = {s.channels for s in shapes}
+        if len(channels) != 1:
+            raise AfiError(f"rpn: every input feature must have one channel count, got {sorted(channels)}")
+        self.anchor_generator = DefaultAnchorGenerator(_get(ag, "SIZES", [[32, 64, 128, 256, 512]]), _get(ag, "ASPECT_RATIOS", [[0.5, 1.0, 2.0]]),
+                                                       [s.stride for s in shapes], _get(ag, "OFFSET", 0.0))
+        na = set(self.anchor_generator.num_cell_anchors)
+        if len(na) != 1:
+            raise AfiError(f"rpn: every level must have the same number of cell anchors, got {self.anchor_generator.num_cell_anchors}")
+        self.num_anchors = na.pop()
+        if self.num_anchors > ops.RPN_MAX_ANCHORS:
+            raise AfiError(f"rpn: {self.num_anchors} anchors per cell; at most {ops.RPN_MAX_ANCHORS} are supported")
+        self.rpn_head = StandardRPNHead(channels.pop(), self.num_anchors)
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    # ------------------------------------------------------------------ the head
+    def _prepare(self):
+        """The two 1x1 convs as one [Cpad, C] weight (logits, then deltas, zero rows up to a multiple of 4) and the 3x3 weight in the kernels'
+        layout, rebuilt when a parameter changes."""
+        h = self.rpn_head
+        ts = [h.objectness_logits.weight, h.objectness_logits.bias, h.anchor_deltas.weight, h.anchor_deltas.bias, h.conv.weight, h.conv.bias]
+        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
+        if getattr(self, "_cat_key", None) != key:
+            A, C_ = self.num_anchors, h.conv.weight.shape[0]
+            cpad = (5 * A + 3) // 4 * 4
+            w = torch.zeros((cpad, C_), device=ts[0].device, dtype=torch.float32)
+            b = torch.zeros((cpad,), device=ts[0].device, dtype=torch.float32)
+            w[:A], w[A:5 * A] = ts[0].detach().reshape(A, C_), ts[2].detach().reshape(4 * A, C_)
+            b[:A], b[A:5 * A] = ts[1].detach(), ts[3].detach()
+            w3 = ts[4].detach().float().permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)       # [O][kh][kw][I] memory: what the conv kernels read
+            self._cat, self._cat_key = (w, b, w3, ts[5].detach().float().contiguous()), key
+        return self._cat
+
+    def _check(self, features):
+        if self.training and torch.is_grad_enabled():
+            raise AfiError("rpn: the proposal generator is inference-only (frozen): call .eval(), or run it under torch.no_grad(); RPN losses and "
+                           "training are out of scope")
+        missing = [f for f in self.in_features if f not in features]
+        if missing:
+            raise AfiError(f"rpn: features {missing} are missing (got {sorted(features)})")
+        xs = [features[f] for f in self.in_features]
+        for f, x in zip(self.in_features, xs):
+            if not x.is_cuda:
+                raise AfiError(f"rpn: feature {f} is a CPU tensor; the proposal generator runs on the GPU only, there is no CPU fallback")
+            if x.dtype != torch.float32:
+                raise AfiError(f"rpn: feature {f} is {x.dtype}; fp32 features only (2-byte activations stop at the AFI backbone's boundary)")
+            if x.dim() != 4 or x.shape[1] != self.rpn_head.conv.weight.shape[1] or x.shape[0] != xs[0].shape[0]:
+                raise AfiError(f"rpn: feature {f} has shape {tuple(x.shape)}; [N, {self.rpn_head.conv.weight.shape[1]}, H, W] expected")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise AfiError("rpn: the proposal generator is forward-only: run it under torch.no_grad() or detach its inputs")
+        return xs
+
+    def head(self, features):
+        """Per level, the pixel-major head output [N, Cpad, H, W]: channels 0..A-1 the objectness logits, A..5A-1 the anchor deltas."""
+        xs = self._check(features)
+        with torch.no_grad():
+            wcat, bcat, w3, b3 = self._prepare()
+            outs = []
+            for x in xs:
+                t = _conv3x3(ops.pixel_major(x), (w3, b3), relu=True)
+                outs.append(ops.conv1x1_fwd(t, wcat, bcat))
+        return outs
+
+    # ------------------------------------------------------------------ selection
+    def select(self, heads, image_hw):
+        """top-k, decode, NMS per level and the merge, on the head outputs; image_hw [N, 2] fp32 on the device.  Returns a dict with the padded
+        result (boxes [N, post_k, 4], logits [N, post_k], counts [N] int32) and the stages' own outputs with the levels side by side
+        (level_off, vals / idx / valid / keep [N, K], level_boxes [N, K, 4])."""
+        A, N, dev = self.num_anchors, heads[0].shape[0], heads[0].device
+        ks = [min(self.pre_nms_topk, o.shape[2] * o.shape[3] * A) for o in heads]
+        off = [0]
+        for k in ks:
+            off.append(off[-1] + k)
+        K = off[-1]
+        vals = torch.empty((N, K), device=dev, dtype=torch.float32)
+        idx = torch.empty((N, K), device=dev, dtype=torch.int32)
+        boxes = torch.empty((N, K, 4), device=dev, dtype=torch.float32)
+        valid = torch.empty((N, K), device=dev, dtype=torch.int32)
+        keep = torch.empty((N, K), device=dev, dtype=torch.int32)
+        for l, (o, k) in enumerate(zip(heads, ks)):
+            s = slice(off[l], off[l + 1])
+            ops.rpn_topk(o, A, k, vals[:, s], idx[:, s])
+            ops.rpn_decode(o, A, A, self.anchor_generator.cell_anchors[l], self.anchor_generator.strides[l], idx[:, s], k, image_hw,
+                           self.box_weights, SCALE_CLAMP, self.min_box_side_len, boxes[:, s], valid[:, s])
+            ops.rpn_nms(boxes[:, s], valid[:, s], self.nms_thresh, keep[:, s])
+        ob, ol, counts = ops.rpn_merge(boxes, vals, keep, off, self.post_nms_topk)
+        return {"boxes": ob, "logits": ol, "counts": counts, "level_off": off, "vals": vals, "idx": idx, "level_boxes": boxes, "valid": valid,
+                "keep": keep}
+
+    def forward_padded(self, image_sizes, features, intermediates=False):
+        """(boxes [N, post_k, 4], logits [N, post_k], counts [N] int32) on the device, rows past counts zero; image_sizes: [N, 2] device tensor
+        (height, width) of the un-padded images.  No host read: capturable in a hipGraph.  intermediates: the dict of ``select`` instead."""
+        heads = self.head(features)
+        if not torch.is_tensor(image_sizes) or not image_sizes.is_cuda:
+            raise AfiError("rpn: forward_padded takes the image sizes as an [N, 2] tensor on the GPU (forward() takes a list)")
+        if tuple(image_sizes.shape) != (heads[0].shape[0], 2):
+            raise AfiError(f"rpn: image sizes of shape {tuple(image_sizes.shape)} for a batch of {heads[0].shape[0]}")
+        with torch.no_grad():
+            r = self.select(heads, image_sizes.to(torch.float32).contiguous())
+        return r if intermediates else (r["boxes"], r["logits"], r["counts"])
+
+    def forward(self, images, features, gt_instances=None):
+        """detectron2's RPN.forward at inference: (one proposals object per image -- image_size, proposal_boxes, objectness_logits, sorted by
+        logit --, {}).  One device-to-host read, of the counts."""
+        if gt_instances is not None:
+            raise AfiError("rpn: gt_instances given -- RPN losses and label assignment are out of scope (inference only)")
+        xs = self._check(features)
+        sizes = [(int(h), int(w)) for h, w in images.image_sizes]
+        if len(sizes) != xs[0].shape[0] or len(images) != len(sizes):
+            raise AfiError(f"rpn: {len(sizes)} image sizes for a batch of {xs[0].shape[0]}")
+        hw = torch.tensor(sizes, dtype=torch.float32).to(xs[0].device)
+        boxes, logits, counts = self.forward_padded(hw, features)
+        return [_make_proposals(sz, boxes[n, :c], logits[n, :c]) for n, (sz, c) in enumerate(zip(sizes, counts.tolist()))], {}
+
+
+def build_proposal_generator(cfg, input_shape):
+    """detectron2's build_proposal_generator: None for precomputed proposals, else the registered class."""
+    name = _get(_get(cfg.MODEL, "PROPOSAL_GENERATOR", None), "NAME", "RPN")
+    if name == "PrecomputedProposals":
+        return None
+    try:
+        cls = PROPOSAL_GENERATOR_REGISTRY.get(name)
+    except KeyError:
+        raise AfiError(f"rpn: no proposal generator named {name!r} (this package provides 'RPN')")
+    return cls(cfg, input_shape)

@@ -578,6 +578,34 @@ int afi_swin_gelu(float* x, long long n, void* stream);
 int afi_swin_window_attn(afi_view_t qkv, int N, int H, int W, int C, const float* qkv_bias, const float* bias_img, int window, int shift,
                          float* out, void* stream);
 
+/* ------------------------------------------------------------------ frozen RPN proposal generator: selection (afigan_amd/rpn.py)
+ * detectron2 v0.1.1's RPN at inference, after its head (which runs on afi_conv3x3_wino_infer / afi_conv3x3_fwd and one afi_conv1x1_fwd): per level
+ * top-k, decode + clip + size test, greedy NMS; then the cross-level merge.  Anchor i of a level is (y W + x) A + a: cell anchor a shifted by
+ * (x, y) * stride; no anchor tensor exists.  A <= 16, k <= 1024 per level, H W A < 2^22 - 1, at most 8 levels, N <= 65535 (AFI_ERR_UNSUPPORTED /
+ * AFI_ERR_BAD_ARG otherwise).  Lists of one level are rows of `ld` elements (ld >= k), so the levels of an image can sit side by side in one
+ * [N][sum k] buffer -- the layout afi_rpn_merge reads.  No entry point synchronises with the host; all results are bit-identical between runs.
+ * afi_rpn_topk: logits = channels 0 .. A-1 of the view [N][H][W][.] (4-byte aligned is enough).  vals / idx [n][j], j < k <= H W A: the k highest
+ *   logits of image n, by (logit descending, anchor index ascending) -- equal logits, -0 and +0 included, go in index order inside the list and
+ *   at the cut; a NaN ranks below every number.  ws: afi_rpn_topk_ws_floats(N, H, W, A) floats, 8-byte aligned (0: none needed; -1: unsupported).
+ * afi_rpn_decode: deltas = the view whose channel 4 a + c is coordinate c of anchor a's delta; cell_anchors [A][4] (device), image_hw [N][2]
+ *   (device, fp32: the un-padded height, width).  boxes [n][j][4] = clip(Box2BoxTransform(wx, wy, ww, wh).apply_deltas, dw / dh clamped from
+ *   above at scale_clamp), evaluated in fp64 from the fp32 inputs and rounded once; valid [n][j] = (x2 - x1 > min_size && y2 - y1 > min_size) on
+ *   the stored fp32 box.  An index outside [0, H W A) gives a zero box, valid 0.
+ * afi_rpn_nms: boxes [n][j][4], valid [n][j] in list order; keep [n][j] = 1 for a valid box no earlier kept box of the list overlaps with
+ *   inter / (area_a + area_b - inter) > thresh (fp32, in that form).  k = 0 is accepted and launches nothing.
+ * afi_rpn_merge: boxes [N][K][4], vals / keep [N][K], K = level_off[L]; level l is columns [level_off[l], level_off[l+1]) (level_off: HOST array
+ *   of L + 1 ints, level_off[0] = 0), each level in afi_rpn_topk's order.  Output: the kept entries by (logit descending, level, rank), the first
+ *   post_k of them: out_boxes [N][post_k][4], out_logits [N][post_k], counts [N]; rows from counts[n] on are zero. */
+long long afi_rpn_topk_ws_floats(int N, int H, int W, int A);
+int afi_rpn_topk(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                 void* stream);
+int afi_rpn_decode(afi_view_t deltas, int N, int H, int W, int A, const float* cell_anchors, int stride, const int* idx, int k, long long ld,
+                   const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, float min_size, float* boxes, int* valid,
+                   void* stream);
+int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld, float thresh, int* keep, void* stream);
+int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                  float* out_logits, int* counts, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
