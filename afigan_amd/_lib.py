@@ -5,6 +5,7 @@ fallback: if the HIP library is missing or a call returns a non-zero status, an 
 """
 import ctypes as C
 import os
+import re
 
 # torch FIRST: the ROCm wheel ships its own libamdhip64.so; importing torch before dlopen()ing libafigan_hip.so makes the
 # library's HIP dependency resolve to the runtime torch already loaded.  The other order maps a second HIP runtime into the
@@ -14,12 +15,37 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AFI_LIB_PATH") or os.path.join(_HERE, "csrc", "libafigan_hip.so")   # override: A/B kernel builds
 
-AFI_MAX_RDB = 8
-ABI_VERSION = 8
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "afigan_hip.h")   # the one statement of the boundary: read at import, ships with the package
+ABI_VERSION = 8                       # what this binding (the struct mirrors below, ops.py) was written against; load() compares it with the library's
 
 
 class AfiError(RuntimeError):
     pass
+
+
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def parse_defines(text):
+    """{name: int} over the `#define AFI_NAME value` lines of a C header; a value that names another define (AFI_DTYPE_DEFAULT) is resolved."""
+    raw = dict(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(AFI_\w+)[ \t]+(\w+)[ \t]*$", _strip_comments(text), flags=re.M))
+    try:
+        return {k: int(raw.get(v, v), 0) for k, v in raw.items()}
+    except ValueError as e:
+        raise AfiError(f"{HEADER_PATH}: a #define AFI_* that is neither an integer nor the name of one ({e})") from None
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise AfiError(f"{HEADER_PATH} not found: the binding takes every signature and constant of the C-ABI from it (and the library "
+                       "cannot be built without it), so it ships with the package")
+    return open(HEADER_PATH).read()
+
+
+_HEADER = _read_header()
+DEFINES = parse_defines(_HEADER)      # AFI_OPT_*, AFI_DTYPE_*, AFI_STORE_*, AFI_POOL_*, AFI_MAX_RDB, the status codes
+AFI_MAX_RDB = DEFINES["AFI_MAX_RDB"]
 
 
 class View(C.Structure):
@@ -49,125 +75,36 @@ class SgdDesc(C.Structure):
                 ("wd", C.c_float), ("pad_", C.c_float)]
 
 
-_vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
-_GP, _DP = C.POINTER(GenParams), C.POINTER(DiscParams)
+# the C types of the header -> ctypes.  Every other POINTER (and an array parameter such as `const int F[4]`) is a c_void_p: the header
+# cannot tell a host array from a device pointer, and c_void_p takes a ctypes array, byref(...), an integer address or None alike.
+_CTYPES = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "afi_view_t": View,
+           "const afi_gen_params_t*": C.POINTER(GenParams), "const afi_disc_params_t*": C.POINTER(DiscParams), "const char*": C.c_char_p}
 
-# name -> (restype, argtypes); every symbol declared in include/afigan_hip.h
-SIGNATURES = {
-    "afi_abi_version": (_i, []),
-    "afi_build_id": (C.c_char_p, []),
-    "afi_status_string": (C.c_char_p, [_i]),
-    "afi_ctx_create": (_i, [C.POINTER(C.c_void_p)]),
-    "afi_ctx_destroy": (_i, [_vp]),
-    "afi_ctx_set_op_scratch": (_i, [_vp, _vp, _ll]),
-    "afi_ctx_set_compute_dtype": (_i, [_vp, _i]),
-    "afi_ctx_get_compute_dtype": (_i, [_vp]),
-    "afi_ctx_set_option": (_i, [_vp, _i, _ll]),
-    "afi_ctx_get_option": (_ll, [_vp, _i]),
-    "afi_gemm_nt_scratch_bytes": (_ll, [_i, _i, _i, _i]),
-    "afi_gemm_nt": (_i, [_vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _ll, _vp]),
-    "afi_gemm_tn_scratch_bytes": (_ll, [_i, _i]),
-    "afi_gemm_tn": (_i, [_vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _ll, _vp]),
-    "afi_ctx_set_wino_weight_cache": (_i, [_vp, _vp, _ll]),
-    "afi_ctx_wino_weight_cache_invalidate": (_i, [_vp]),
-    "afi_ctx_set_wino_wgrad_accum": (_i, [_vp, _vp, _ll]),
-    "afi_ctx_wino_wgrad_flush": (_i, [_vp, _vp]),
-    "afi_ctx_wino_wgrad_discard": (_i, [_vp]),
-    "afi_generator_fwd_ws_floats": (_ll, [_i] * 6),
-    "afi_generator_bwd_ws_floats": (_ll, [_i] * 6),
-    "afi_generator_fwd": (_i, [_vp, _GP, View, _i, _i, _i, View, _vp, _ll, _vp]),
-    "afi_generator_fwd_out16": (_i, [_vp, _GP, View, _i, _i, _i, View, _i, _vp, _ll, _vp]),
-    "afi_generator_bwd": (_i, [_vp, _GP, _GP, View, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
-    "afi_discriminator_fwd_ws_floats": (_ll, [C.POINTER(C.c_int), _i, _i, _i]),
-    "afi_discriminator_fwd_ws_floats_ex": (_ll, [_vp, C.POINTER(C.c_int), _i, _i, _i, _i]),
-    "afi_discriminator_bwd_ws_floats": (_ll, [C.POINTER(C.c_int), _i, _i, _i]),
-    "afi_discriminator_ws_layout": (_i, [C.POINTER(C.c_int), _i, _i, _i, C.POINTER(C.c_longlong)]),
-    "afi_discriminator_saved_activations": (_i, [_vp, C.POINTER(C.c_int), _i, _i, _i]),
-    "afi_discriminator_fwd": (_i, [_vp, _DP, View, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
-    "afi_discriminator_bwd": (_i, [_vp, _DP, _DP, View, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
-    "afi_discriminator_fwd_paired": (_i, [_vp, _DP, View, _i, _i, _i, _vp, _i, _vp, _ll, _vp]),
-    "afi_discriminator_bwd_paired": (_i, [_vp, _DP, _DP, View, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
-    "afi_conv3x3_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _f, _f, _i, _vp]),
-    "afi_conv3x3_fwd_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _f, _f, _i, _vp]),
-    "afi_conv3x3_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _f, _f, View, _vp]),
-    "afi_conv3x3_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
-    "afi_conv1x1_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _f, _f, View, _f, _i, _vp]),
-    "afi_conv1x1_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _f, _f, _vp]),
-    "afi_conv1x1_dgrad_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _i, _f, _f, _vp]),
-    "afi_conv1x1_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
-    "afi_conv3x3_wino_ws_floats": (_ll, [_i] * 5),
-    "afi_conv3x3_wino_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _vp, _ll, _vp]),
-    "afi_conv3x3_wino_fwd_out16": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp, _ll, _vp]),
-    "afi_conv3x3_wino_infer": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp, _ll, _vp]),
-    "afi_conv3x3_wino_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, View, _vp, _ll, _vp]),
-    "afi_conv3x3_wino_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp, _ll, _vp]),
-    "afi_conv3x3s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, View, _f, View, _f, _vp]),
-    "afi_conv3x3s2_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, _f, _f, _vp]),
-    "afi_conv3x3s2_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
-    "afi_relu_bwd": (_i, [_vp, _vp, _vp, _ll, _f, _vp]),
-    "afi_dwconv3x3_fwd": (_i, [View, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "afi_maxpool3s2_same_fwd": (_i, [View, _i, _i, _i, _i, _vp, _vp]),
-    "afi_fuse_swish_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _vp]),
-    "afi_fuse_swish_bwd_scratch_floats": (_ll, []),
-    "afi_fuse_swish_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp]),
-    "afi_dwconv3x3_wgrad_scratch_floats": (_ll, [_i]),
-    "afi_dwconv3x3_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "afi_maxpool3s2_same_fwd_idx": (_i, [View, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "afi_maxpool3s2_same_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "afi_bn_stats_ex": (_i, [_vp, _ll, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "afi_bn_apply_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _f, _vp]),
-    "afi_resize_bilinear_u8_ws_bytes": (_ll, [_i, _i, _i, _i, _i]),
-    "afi_resize_bilinear_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _ll, _vp]),
-    "afi_dual_scale_u8_ws_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
-    "afi_dual_scale_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _ll, _vp]),
-    "afi_normalize_pad_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    "afi_resnet_stem_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "afi_nearest_nhwc": (_i, [View, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "afi_resnest_stem_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    "afi_resnest_pool_nhwc": (_i, [View, _i, _i, _i, _i, _i, _vp, _vp]),
-    "afi_resnest_splat_ws_floats": (_ll, [_i, _i, _i, _i]),
-    "afi_resnest_splat_gap": (_i, [View, View, _i, _i, _i, _i, _vp, _ll, _vp]),
-    "afi_resnest_splat_attn": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "afi_resnest_splat_combine": (_i, [View, View, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "afi_swin_patch_embed": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
-    "afi_swin_layernorm": (_i, [View, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
-    "afi_swin_gelu": (_i, [_vp, _ll, _vp]),
-    "afi_swin_window_attn": (_i, [View, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "afi_rpn_topk_ws_floats": (_ll, [_i, _i, _i, _i]),
-    "afi_rpn_topk": (_i, [View, _i, _i, _i, _i, _i, _vp, _vp, _ll, _vp, _ll, _vp]),
-    "afi_rpn_decode": (_i, [View, _i, _i, _i, _i, _vp, _i, _vp, _i, _ll, _vp, _f, _f, _f, _f, C.c_double, _f, _vp, _vp, _vp]),
-    "afi_rpn_nms": (_i, [_vp, _vp, _i, _i, _ll, _f, _vp, _vp]),
-    "afi_rpn_merge": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int), _i, _vp, _vp, _vp, _vp]),
-    "afi_convT6s2_pack_weight": (_i, [_vp, _vp, _i, _i, _vp]),
-    "afi_convT6s2_unpack_wgrad": (_i, [_vp, _vp, _i, _i, _vp]),
-    "afi_convT6s2_fwd": (_i, [_vp, View, _i, _i, _i, _i, _vp, _vp, _i, View, _i, _vp]),
-    "afi_convT6s2_dgrad": (_i, [_vp, View, _i, _i, _i, _i, _vp, _i, View, View, _vp]),
-    "afi_convT6s2_wgrad": (_i, [_vp, View, View, _i, _i, _i, _i, _i, _vp, _f, _vp]),
-    "afi_bilinear2x_add_fwd": (_i, [View, _i, _i, _i, _i, _f, _vp, _vp]),
-    "afi_bilinear2x_add_bwd": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
-    "afi_reduce_scratch_floats": (_ll, [_i]),
-    "afi_bn_stats": (_i, [_vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "afi_bn_apply_lrelu_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp]),
-    "afi_bn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp]),
-    "afi_bn_bwd_sums": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp]),
-    "afi_bn_bwd_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp]),
-    "afi_colsum_accum": (_i, [_vp, _ll, _i, _ll, _f, _vp, _vp, _vp]),
-    "afi_bce_logits_fwd_bwd": (_i, [_vp, _ll, _f, _f, _vp, _f, _vp, _vp]),
-    "afi_l1_fwd_bwd": (_i, [View, View, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _vp, _vp]),
-    "afi_sgd_momentum_step": (_i, [_vp, _i, _ll, _f, _f, _f, _vp]),
-    "afi_scale_inplace": (_i, [_vp, _ll, _f, _vp]),
-    "afi_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "afi_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "afi_cast_to_f32_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp]),
-    "afi_cast_from_f32_nhwc": (_i, [View, _i, _i, _i, _i, _vp, _i, _vp]),
-    "afi_profile_enable": (_i, [_i]),
-    "afi_profile_num_kinds": (_i, []),
-    "afi_profile_kind_name": (C.c_char_p, [_i]),
-    "afi_profile_get": (_i, [_i, C.POINTER(C.c_double)]),
-    "afi_profile_dump": (_i, [C.c_char_p]),
-    "afi_debug_wk6_convT_images": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
-    "afi_debug_wgrad_sk_plan": (_i, [C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-}
+
+def _ctype(decl, where):
+    t = " ".join(decl.replace("*", " * ").split()).replace(" *", "*")
+    if t in _CTYPES:
+        return _CTYPES[t]
+    if t.endswith("*"):
+        return C.c_void_p
+    raise AfiError(f"{HEADER_PATH}: {where}: no ctypes type for {t!r} (the binding knows {sorted(_CTYPES)} and pointers)")   # never a default to int
+
+
+def parse_prototypes(text):
+    """{name: (restype, argtypes)} over the prototypes `ret afi_name(args);` of a C header: comments (inside argument lists too), preprocessor
+    lines and typedefs are dropped, a prototype may span lines, parameters are named.  A type _ctype does not know raises AfiError."""
+    text = re.sub(r"^[ \t]*#.*$", " ", _strip_comments(text), flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w*\s*\{[^}]*\}\s*\w+\s*;|typedef[^;{]*;|extern\s+\"C\"\s*\{", " ", text)
+    sigs = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(afi_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [a.strip() for a in args.split(",")] if args.strip() not in ("", "void") else []
+        sigs[name] = (_ctype(ret, name), [C.c_void_p if "[" in a else _ctype(re.sub(r"\w+$", "", a), f"{name}({a})") for a in args])
+    return sigs
+
+
+# name -> (restype, argtypes) of every entry point, derived from the prototypes of include/afigan_hip.h.  A new entry point needs a prototype
+# there, a definition in csrc/ and a wrapper in ops.py; nothing here.
+SIGNATURES = parse_prototypes(_HEADER)
 
 _lib = None
 
@@ -233,10 +170,9 @@ CTX_FIRST = frozenset(n for n, (_, a) in SIGNATURES.items() if n.startswith(("af
                       and not n.endswith(("_ws_floats", "_ws_layout", "pack_weight", "unpack_wgrad")))
 
 
-DTYPES = {"fp32": 0, "bf16": 1, "f16x3": 2, "bf16x3": 3, "bf16x6": 6}             # AFI_DTYPE_* of include/afigan_hip.h
-OPTIONS = {"winograd": 0, "winograd_f4_backward": 1, "winograd_f4_forward": 2, "bn_stats_fp64": 3, "d_winograd_min_pixels": 4,
-           "g_winograd_min_pixels": 5, "g_smallmap_max_pixels": 6, "g_grouped_wgrad_max_pixels": 7, "g_batch_growth_grads": 8,
-           "g_smallmap6_max_pixels": 9, "g_rdb_chain": 10, "d_fold_bn_apply": 11, "deterministic": 12, "f16_presplit": 13, "f16_nt256_min_tiles": 14, "f16_local_sums": 15, "d_fuse_tail": 16, "d_fuse_bwd_sums": 17}      # AFI_OPT_*
+# the Python-side names of the header's AFI_DTYPE_* / AFI_OPT_* (an option is its define without the prefix, lower-cased)
+DTYPES = {k: DEFINES["AFI_DTYPE_" + n] for k, n in (("fp32", "F32"), ("bf16", "BF16"), ("f16x3", "F16X3"), ("bf16x3", "BF16X3"), ("bf16x6", "BF16X6"))}
+OPTIONS = {k[len("AFI_OPT_"):].lower(): v for k, v in DEFINES.items() if k.startswith("AFI_OPT_") and k != "AFI_OPT_COUNT"}
 
 
 class Ctx:

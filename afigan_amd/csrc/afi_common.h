@@ -2,22 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/afigan_hip.h"      // the status codes (AFI_OK, AFI_ERR_*: no exceptions cross the C-ABI) and AFI_STORE_*, defined there only
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define AFI_LRELU_SLOPE 0.2f
 
-// status codes returned across the C-ABI (no exceptions cross it)
-#define AFI_OK 0
-#define AFI_ERR_BAD_ARG 1
-#define AFI_ERR_UNSUPPORTED 2
-#define AFI_ERR_LAUNCH 3
-
-// storage dtype of a tensor at the module boundary (include/afigan_hip.h: AFI_STORE_*); the kernels compute in fp32 whatever it is
-#define AFI_STORE_F32 0
-#define AFI_STORE_BF16 1
-#define AFI_STORE_F16 2
 #ifndef AFI_TRY
 #define AFI_TRY(expr) do { int _s = (expr); if (_s != AFI_OK) return _s; } while (0)
 #endif

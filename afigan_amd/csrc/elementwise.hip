@@ -4,6 +4,7 @@
 // All of them are float4-vectorised along the contiguous channel dimension of the pixel-major layout;
 // reductions use wavefront shuffles (64 lanes) + one LDS hop per block.
 #include "afi_common.h"
+#include "afi_launch.h"
 #include "afi_bilinear.h"
 #include "afi_convt_pack.h"
 #include "afi_bn.h"

@@ -3,6 +3,7 @@
 //   narrow: fp32 pixel-major view  ->  dense 2-byte [N][H][W][C] (channels_last), rounded once to nearest even       (csrc/afi_half.h)
 // The fp32 NCHW -> NHWC transpose of the detectron2 boundary (afi_nchw_to_nhwc) is the fp32 instance of the widening transpose.
 #include "afi_common.h"
+#include "afi_launch.h"
 #include "afi_half.h"
 
 template <int DT> struct AfiStoreT { typedef unsigned short T; };

@@ -25,6 +25,7 @@
 //     store (conv-transpose), LeakyReLU-derivative mask (dgrad), channel-slice in/out of wider buffers
 //     (the RDB dense buffer replaces every torch.cat of generator_rdb.py:66-68).
 #include "afi_common.h"
+#include "afi_launch.h"
 
 #define AFI_BK 32
 #define AFI_LDK (AFI_BK + 4)
@@ -841,7 +842,6 @@ int afi_launch_absmax_planes(const float* X, long long per_plane, int planes, fl
 // wkind = 5 / 6 (F(2x2) / F(4x4) weight planes): the header's slot [64] already holds the largest magnitude of the weight tensor the planes were
 // transformed from -- the caller zero-filled the header (afi_f16_image_begin) and the weight transform raised it -- one launch.
 long long afi_f16_image_bytes(int planes, int N, int K) { return AFI_F16_HDR_BYTES + (long long)planes * N * K * 4; }
-AfiF16Bound afi_f16_bound(const float* amax, int kind);
 int afi_f16_image_begin(void* out, hipStream_t st) { return hipMemsetAsync(out, 0, AFI_F16_HDR_BYTES, st) == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH; }
 float* afi_f16_image_wmax(void* out) { return (float*)out + 64; }
 int afi_launch_split_f16_tiles(const float* B, void* out, int planes, int N, int K, hipStream_t st, int wkind) {
@@ -983,10 +983,6 @@ int afi_launch_gemm_tn_f16x3(const float* Q, const float* V, float* dU, int plan
     else hipLaunchKernelGGL(afi_gemm_tn_f16x3_kernel, dim3((unsigned)tiles, splitK), dim3(256), 2u * 4u * 4096u, st, g, qb, vb, ntm, ntn, kper);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
-int afi_launch_pix_gemm_sk(const AfiPixGemm& p, int b_rc, hipStream_t st);   // smallmap.hip
-int afi_launch_pix_gemm_wk_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st);
-int afi_launch_wgrad_group(const AfiWgradGemm* probs, int n, int wide, hipStream_t st);
-int afi_launch_wgrad6_group(const AfiWgradGemm* probs, int n, hipStream_t st);
 // grouped small-map launches, bracketed for the live roofline like every other GEMM launch
 int afi_launch_pix_gemm_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st) {
     double fl = 0.0; long long m = 0; int nn = 0;

@@ -16,6 +16,7 @@
 //                            atomics, no zero-fills, and the grid fills the chip (the per-layer launches were 7 .. 36 tiles each).
 //   afi_colsum_group_kernel  the bias gradients of the same pass in one launch.
 #include "afi_common.h"
+#include "afi_launch.h"
 
 #define AFI_BK 32
 // zero page of the branch-free gathers.  EXTERNAL linkage and non-const on purpose: with internal linkage hipcc proves the array is
@@ -1088,7 +1089,7 @@ __global__ __launch_bounds__(256) void afi_wk6_image_kernel(const AfiWk6ImgJobs 
 long long afi_wk6_image_bytes(int Ncols, int Ck, int ntaps, int nKphase) {
     return (long long)afi_cdiv(Ncols, 32) * afi_cdiv(Ck, AFI_BK) * ntaps * nKphase * AFI_WK6_STAGE_BYTES;
 }
-int afi_launch_wk6_images(const AfiWk6ImgJob* jobs, int n, hipStream_t st, const AfiWk6Side* side = nullptr, const AfiWk6ConvT* ct = nullptr) {
+int afi_launch_wk6_images(const AfiWk6ImgJob* jobs, int n, hipStream_t st, const AfiWk6Side* side, const AfiWk6ConvT* ct) {
     static_assert(AFI_WK6_CT_LDS >= 16 * (8 * 36 + 1) && AFI_WK6_CT_LDS >= AFI_CT_CI * AFI_CT_LD, "one LDS tile for the three conv-transpose bodies");
     if (ct) {
         if (!ct->W || !ct->dst || ct->Cin <= 0 || ct->Cout <= 0 || (ct->mode != 0 && ct->mode != 1)) return AFI_ERR_BAD_ARG;

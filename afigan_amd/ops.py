@@ -58,7 +58,7 @@ def new_pixel_major(N, C_, H, W, device, zero=False, dtype=torch.float32) -> tor
 # The interpolator and the AFI FPN / PAFPN accept bf16 / fp16 activations (torch.autocast): they are widened to fp32 on the way in, every
 # kernel computes in fp32 under the context's compute dtype, and the module's outputs (and its inputs' gradients) are rounded back ONCE, by
 # the epilogue that stores them.  Only the helpers below let a 2-byte tensor in; _check_cuda keeps refusing it everywhere else.
-STORE_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # AFI_STORE_* of include/afigan_hip.h
+STORE_DTYPES = {torch.float32: _lib.DEFINES["AFI_STORE_F32"], torch.bfloat16: _lib.DEFINES["AFI_STORE_BF16"], torch.float16: _lib.DEFINES["AFI_STORE_F16"]}
 
 
 def boundary_dtype(*ts) -> torch.dtype:
@@ -718,7 +718,7 @@ def nearest(x, up=2, down=1):
 
 
 # ------------------------------------------------------------------------------------------------ frozen ResNeSt bottom-up (resnest_backbone.py)
-POOL_MODES = {"max3s2p1": 0, "avg3s2p1": 1, "avg2s2_ceil": 2}          # AFI_POOL_* of include/afigan_hip.h
+POOL_MODES = {m: _lib.DEFINES["AFI_POOL_" + m.upper()] for m in ("max3s2p1", "avg3s2p1", "avg2s2_ceil")}
 
 
 def resnest_stem(x, w, bias):

@@ -8,7 +8,11 @@
  * so this header defines the boundary a binding for that path needs: plain pointers, sizes and a HIP stream;
  * no torch types; every function returns an int status (AFI_OK == 0) and never throws or allocates.
  * The Python binding a maintainer would add (ctypes) is shown in INTEGRATION.md and shipped in
- * afigan_amd/_lib.py.
+ * afigan_amd/_lib.py.  That binding READS this file at import: argument and return types come from the
+ * prototypes below, option / dtype / pool numbers from the #defines.  A new entry point needs a prototype
+ * here, a definition under afigan_amd/csrc and a wrapper in afigan_amd/ops.py -- no table anywhere else.
+ * Keep to the types the binding knows (int, long long, float, double, afi_view_t by value, pointers, named
+ * parameters): anything else is refused at import, never guessed.
  *
  * Conventions
  *   - Activations are PIXEL-MAJOR ("NHWC"): element (n, y, x, c) of a view lives at

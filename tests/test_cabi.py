@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI boundary: the library loads without a GPU and exports every symbol include/afigan_hip.h
-declares; the binding table covers the header; workspace queries (host-only functions) answer."""
+declares; the binding table is derived from the header, all of it, and the hand-written struct mirrors have the header's layout; workspace
+queries (host-only functions) answer."""
 import ctypes
 import os
 import re
@@ -23,6 +24,71 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in afigan_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
+
+
+def test_header_parser_on_literal_prototypes():
+    """The rules _lib.parse_prototypes derives SIGNATURES by, one literal case each."""
+    import pytest
+    from afigan_amd import _lib
+    vp, i, ll, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+    P = _lib.parse_prototypes
+    assert P("int afi_a(const float* A, float* C, int planes, long long rows,\n          void* scratch,\n          void* stream);") == {"afi_a": (i, [vp, vp, i, ll, vp, vp])}
+    assert P("int afi_b(afi_ctx_t* ctx, afi_view_t dy /*[N,Ho,Wo,Cout]*/, int N, // batch\n float alpha);") == {"afi_b": (i, [vp, _lib.View, i, f])}
+    assert P("long long afi_c(const int F[4], int N);") == {"afi_c": (ll, [vp, i])}
+    assert P("long long afi_d(void);\nint afi_e();") == {"afi_d": (ll, []), "afi_e": (i, [])}
+    assert P("const char* afi_f(int status);\nint afi_g(const char* path);") == {"afi_f": (ctypes.c_char_p, [i]), "afi_g": (i, [ctypes.c_char_p])}
+    assert P("int afi_h(afi_view_t a, afi_view_t b, double c);") == {"afi_h": (i, [_lib.View, _lib.View, ctypes.c_double])}
+    got = P("int afi_i(const afi_gen_params_t* prm, const afi_disc_params_t* grads, const afi_sgd_desc_t* d, afi_ctx_t** out, unsigned char* idx);")
+    assert got == {"afi_i": (i, [ctypes.POINTER(_lib.GenParams), ctypes.POINTER(_lib.DiscParams), vp, vp, vp])}
+    # what surrounds the prototypes in the header: defines with long trailing comments, typedefs with and without a body, extern "C"
+    hdr = ('#ifdef __cplusplus\nextern "C" {\n#endif\n#define AFI_OPT_X 3   /* a comment that goes on\n * over afi_not_a_call(int) lines */\n'
+           "typedef struct afi_s { float* p; long long n; } afi_s_t;\ntypedef struct afi_ctx afi_ctx_t;\n#define AFI_Y AFI_OPT_X\nint afi_j(int a);\n#ifdef __cplusplus\n}\n#endif\n")
+    assert P(hdr) == {"afi_j": (i, [i])} and _lib.parse_defines(hdr) == {"AFI_OPT_X": 3, "AFI_Y": 3}
+    for bad in ("int afi_k(size_t n);", "unsigned afi_k(int n);", "int afi_k(afi_sgd_desc_t d);", "void afi_k(int n);", "int afi_k(int);"):
+        with pytest.raises(_lib.AfiError, match="afi_k"):       # an unknown type names the entry point; it is never taken for an int
+            P(bad)
+
+
+def test_binding_is_derived_from_the_whole_header(tmp_path, monkeypatch):
+    """Nothing in the header is silently skipped: as many signatures as a plain regex finds prototypes, and the options are numbered 0 .. AFI_OPT_COUNT - 1."""
+    import pytest
+    from afigan_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    assert len(re.findall(r"\bafi_\w+\s*\(", hdr)) == len(_lib.SIGNATURES) >= 100
+    count = int(re.search(r"#define\s+AFI_OPT_COUNT\s+(\d+)", hdr).group(1))
+    assert len(_lib.OPTIONS) == count and sorted(_lib.OPTIONS.values()) == list(range(count))
+    assert _lib.AFI_MAX_RDB == int(re.search(r"#define\s+AFI_MAX_RDB\s+(\d+)", hdr).group(1))
+    assert set(_lib.DTYPES.values()) == {v for k, v in _lib.DEFINES.items() if k.startswith("AFI_DTYPE_")}       # every dtype has its Python name
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "afigan_hip.h"))
+    with pytest.raises(_lib.AfiError, match=re.escape(str(tmp_path / "afigan_hip.h"))):                          # a missing header is named, not worked around
+        _lib._read_header()
+
+
+def test_struct_mirrors_match_the_header_layout(tmp_path):
+    """View, GenParams, DiscParams, SgdDesc are written by hand: their size and every field offset equal what the host compiler gives
+    the header's structs (a field the header does not have fails to compile)."""
+    import shutil
+    import subprocess
+    if not shutil.which("make") or not os.path.exists("/opt/rocm/bin/hipcc"):
+        import pytest
+        pytest.skip("needs make and hipcc")
+    from afigan_amd import _lib
+    mirrors = {"afi_view_t": _lib.View, "afi_gen_params_t": _lib.GenParams, "afi_disc_params_t": _lib.DiscParams, "afi_sgd_desc_t": _lib.SgdDesc}
+    lines = ["#include <cstdio>", "#include <cstddef>", '#include "afigan_hip.h"', "int main() {"]
+    for cname, st in mirrors.items():
+        lines.append(f'    std::printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    std::printf("{cname}.{fld} %zu\\n", offsetof({cname}, {fld}));' for fld, _ in st._fields_]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-x", "c++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.cpp"), "-o", str(tmp_path / "layout")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
+    want = {}
+    for cname, st in mirrors.items():
+        want[cname] = str(ctypes.sizeof(st))
+        want.update({f"{cname}.{fld}": str(getattr(st, fld).offset) for fld, _ in st._fields_})
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+    assert len(want) == 4 + 4 + 13 + 10 + 6
 
 
 def test_host_only_queries():
