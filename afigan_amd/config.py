@@ -159,6 +159,18 @@ def get_cfg():
                                       "IOU_LABELS": [0, -1, 1], "BATCH_SIZE_PER_IMAGE": 256, "POSITIVE_FRACTION": 0.5,
                                       "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0), "SMOOTH_L1_BETA": 0.0, "LOSS_WEIGHT": 1.0,
                                       "PRE_NMS_TOPK_TRAIN": 12000, "PRE_NMS_TOPK_TEST": 6000, "POST_NMS_TOPK_TRAIN": 2000,
-                                      "POST_NMS_TOPK_TEST": 1000, "NMS_THRESH": 0.7}},
-                    "INPUT": {"FORMAT": "BGR"}, "SOLVER": {}})
+                                      "POST_NMS_TOPK_TEST": 1000, "NMS_THRESH": 0.7},
+                              # detectron2 v0.1.1's ROI-head defaults (_C.MODEL.ROI_HEADS / ROI_BOX_HEAD / ROI_MASK_HEAD, MASK_ON, KEYPOINT_ON): what
+                              # roi_heads.py reads, and every key the reference yamls set there (the mask head's are declared only)
+                              "MASK_ON": False, "KEYPOINT_ON": False,
+                              "ROI_HEADS": {"NAME": "Res5ROIHeads", "NUM_CLASSES": 80, "IN_FEATURES": ["res4"], "IOU_THRESHOLDS": [0.5],
+                                            "IOU_LABELS": [0, 1], "BATCH_SIZE_PER_IMAGE": 512, "POSITIVE_FRACTION": 0.25,
+                                            "SCORE_THRESH_TEST": 0.05, "NMS_THRESH_TEST": 0.5, "PROPOSAL_APPEND_GT": True},
+                              "ROI_BOX_HEAD": {"NAME": "", "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0), "SMOOTH_L1_BETA": 0.0,
+                                               "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2", "NUM_FC": 0,
+                                               "FC_DIM": 1024, "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_BBOX_REG": False},
+                              "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0,
+                                                "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False,
+                                                "POOLER_TYPE": "ROIAlignV2"}},
+                    "INPUT": {"FORMAT": "BGR"}, "SOLVER": {}, "TEST": {"DETECTIONS_PER_IMAGE": 100}})
         return add_afigan_config(cfg)

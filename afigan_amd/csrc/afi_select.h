@@ -1,0 +1,109 @@
+// What the selection stages of the RPN (rpn.hip) and of the ROI heads' box branch (roi.hip) share: the block prefix sum and the greedy NMS of
+// a sorted list of <= 1024 boxes, with or without classes.
+#pragma once
+#include "afi_common.h"
+
+#define RPN_MAXK 1024
+
+typedef unsigned long long u64;
+
+// Inclusive prefix sum over the block (blockDim a multiple of 64, <= 1024); wtot: 16 ints of LDS.  Two barriers.
+__device__ __forceinline__ int rpn_block_scan(int v, int* wtot, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) wtot[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int i = 0; i < nw; ++i) {
+        const int t = wtot[i];
+        if (i < w) base += t;
+        tot += t;
+    }
+    *total = tot;
+    return inc + base;
+}
+
+// ------------------------------------------------------------------------------------------------ NMS
+__device__ __forceinline__ u64 rpn_readlane64(u64 v, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
+    return ((u64)hi << 32) | lo;
+}
+
+// One block (sixteen waves) per image.  mask[i][w] bit j: box 64 w + j (later than i in the list) overlaps box i by more than thresh.
+// CLS: a pair suppresses only when its classes are equal (afi_roi_nms): one more LDS array and one more term of the test; !CLS is afi_rpn_nms as it was.
+template <bool CLS>
+__global__ __launch_bounds__(1024) void afi_nms_kernel(const float* __restrict__ boxes, const int* __restrict__ cls, const int* __restrict__ valid,
+                                                       int k, long long ld, float thresh, int* __restrict__ keep) {
+#pragma clang fp contract(off)                          // the overlap test is the stated fp32 expression, operation by operation
+    __shared__ u64 mask[RPN_MAXK * 16];
+    __shared__ float4 bx[RPN_MAXK];
+    __shared__ int vd[RPN_MAXK];
+    __shared__ int cl[CLS ? RPN_MAXK : 1];
+    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = (k + 63) >> 6;
+    {
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        int v = 0;
+        if (tid < k) {
+            const float* q = boxes + 4 * ((long long)img * ld + tid);
+            b = make_float4(q[0], q[1], q[2], q[3]);
+            v = valid[(long long)img * ld + tid] != 0;
+        }
+        bx[tid] = b;
+        vd[tid] = v;
+        if (CLS) cl[tid] = tid < k ? cls[(long long)img * ld + tid] : -1;
+    }
+    __syncthreads();
+    for (int w = 0; w < nw; ++w) {
+        const int j = 64 * w + lane;
+        const float4 c = bx[j];
+        const float carea = (c.z - c.x) * (c.w - c.y);
+        const bool cok = j < k && vd[j];
+        const int ccls = CLS ? cl[j] : 0;
+        const int rows = 64 * (w + 1) < k ? 64 * (w + 1) : k;
+        for (int i = wave; i < rows; i += 16) {
+            const float4 r = bx[i];
+            const float iw = fmaxf(fminf(r.z, c.z) - fmaxf(r.x, c.x), 0.f), ih = fmaxf(fminf(r.w, c.w) - fmaxf(r.y, c.y), 0.f);
+            const float inter = iw * ih, rarea = (r.z - r.x) * (r.w - r.y);
+            const bool hit = cok && j > i && (!CLS || cl[i] == ccls) && (inter / (rarea + carea - inter) > thresh);
+            const u64 word = __ballot(hit);
+            if (lane == 0) mask[i * 16 + w] = word;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    u64 remv = 0;                                       // lane w < 16: word w of the boxes suppressed so far
+    const int wsel = lane & 15, sub = lane >> 4;
+    for (int c = 0; c < nw; ++c) {
+        const int row = 64 * c + lane;
+        const u64 diag = (row < k) ? mask[row * 16 + c] : 0ull;
+        const u64 V = __ballot(row < k && vd[row]);
+        u64 R = rpn_readlane64(remv, c) | ~V;           // an invalid box is neither kept nor suppresses anything
+        u64 K = 0;
+#pragma unroll
+        for (int b = 0; b < 64; ++b) {
+            if (!((R >> b) & 1ull)) {
+                K |= 1ull << b;
+                R |= rpn_readlane64(diag, b);
+            }
+        }
+        if (row < k) keep[(long long)img * ld + row] = (int)((K >> lane) & 1ull);
+        // OR the kept rows' words into remv: lane = (word wsel, rows sub, sub + 4, ...)
+        u64 acc = 0;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int b = sub + 4 * t;
+            if (wsel > c && wsel < nw && ((K >> b) & 1ull)) acc |= mask[(64 * c + b) * 16 + wsel];
+        }
+        acc |= __shfl_xor(acc, 16, 64);
+        acc |= __shfl_xor(acc, 32, 64);
+        remv |= acc;                                    // lanes >= 16 hold copies of words lane & 15: never read
+    }
+}

@@ -21,8 +21,8 @@
 // Nothing here synchronises with the host, and every result is bit-identical from run to run and under hipGraph replay.
 #include "../../include/afigan_hip.h"
 #include "afi_common.h"
+#include "afi_select.h"
 
-#define RPN_MAXK 1024
 #define RPN_MAX_A 16
 #define RPN_IDX_BITS 22
 #define RPN_IDX_MASK 0x3FFFFFu
@@ -30,8 +30,6 @@
 #define RPN_BINS 4096              // grid histogram: the top 12 key bits
 #define RPN_HDR 4104               // ints per image in front of the candidate lists: the histogram, the list length, padding to 8 bytes
 #define RPN_MAX_LEVELS 8
-
-typedef unsigned long long u64;
 
 struct RpnLevels { int L; int off[RPN_MAX_LEVELS + 1]; };
 
@@ -50,28 +48,6 @@ __device__ __forceinline__ const float* rpn_at(const AfiView& v, int img, int i,
 }
 
 __device__ __forceinline__ u64 rpn_word(float v, int i) { return ((u64)rpn_key(v) << RPN_IDX_BITS) | (u64)((~(unsigned)i) & RPN_IDX_MASK); }
-
-// Inclusive prefix sum over the block (blockDim a multiple of 64, <= 1024); wtot: 16 ints of LDS.  Two barriers.
-__device__ __forceinline__ int rpn_block_scan(int v, int* wtot, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int t = wtot[i];
-        if (i < w) base += t;
-        tot += t;
-    }
-    *total = tot;
-    return inc + base;
-}
 
 // The digit d of a histogram (nbins a multiple of blockDim) that holds the need-th element counted from the top bin down, and the count of
 // the bins above it: res[0] = d, res[1] = above.  1 <= need <= sum(hist).  Ends with a barrier; hist is left as it was.
@@ -308,85 +284,13 @@ int afi_rpn_decode(afi_view_t deltas, int N, int H, int W, int A, const float* c
 }
 
 // ------------------------------------------------------------------------------------------------ NMS
-__device__ __forceinline__ u64 rpn_readlane64(u64 v, int lane) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
-    return ((u64)hi << 32) | lo;
-}
-
-// One block (sixteen waves) per image.  mask[i][w] bit j: box 64 w + j (later than i in the list) overlaps box i by more than thresh.
-__global__ __launch_bounds__(1024) void afi_rpn_nms_kernel(const float* __restrict__ boxes, const int* __restrict__ valid, int k, long long ld,
-                                                           float thresh, int* __restrict__ keep) {
-#pragma clang fp contract(off)                          // the overlap test is the stated fp32 expression, operation by operation
-    __shared__ u64 mask[RPN_MAXK * 16];
-    __shared__ float4 bx[RPN_MAXK];
-    __shared__ int vd[RPN_MAXK];
-    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nw = (k + 63) >> 6;
-    {
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        int v = 0;
-        if (tid < k) {
-            const float* q = boxes + 4 * ((long long)img * ld + tid);
-            b = make_float4(q[0], q[1], q[2], q[3]);
-            v = valid[(long long)img * ld + tid] != 0;
-        }
-        bx[tid] = b;
-        vd[tid] = v;
-    }
-    __syncthreads();
-    for (int w = 0; w < nw; ++w) {
-        const int j = 64 * w + lane;
-        const float4 c = bx[j];
-        const float carea = (c.z - c.x) * (c.w - c.y);
-        const bool cok = j < k && vd[j];
-        const int rows = 64 * (w + 1) < k ? 64 * (w + 1) : k;
-        for (int i = wave; i < rows; i += 16) {
-            const float4 r = bx[i];
-            const float iw = fmaxf(fminf(r.z, c.z) - fmaxf(r.x, c.x), 0.f), ih = fmaxf(fminf(r.w, c.w) - fmaxf(r.y, c.y), 0.f);
-            const float inter = iw * ih, rarea = (r.z - r.x) * (r.w - r.y);
-            const bool hit = cok && j > i && (inter / (rarea + carea - inter) > thresh);
-            const u64 word = __ballot(hit);
-            if (lane == 0) mask[i * 16 + w] = word;
-        }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    u64 remv = 0;                                       // lane w < 16: word w of the boxes suppressed so far
-    const int wsel = lane & 15, sub = lane >> 4;
-    for (int c = 0; c < nw; ++c) {
-        const int row = 64 * c + lane;
-        const u64 diag = (row < k) ? mask[row * 16 + c] : 0ull;
-        const u64 V = __ballot(row < k && vd[row]);
-        u64 R = rpn_readlane64(remv, c) | ~V;           // an invalid box is neither kept nor suppresses anything
-        u64 K = 0;
-#pragma unroll
-        for (int b = 0; b < 64; ++b) {
-            if (!((R >> b) & 1ull)) {
-                K |= 1ull << b;
-                R |= rpn_readlane64(diag, b);
-            }
-        }
-        if (row < k) keep[(long long)img * ld + row] = (int)((K >> lane) & 1ull);
-        // OR the kept rows' words into remv: lane = (word wsel, rows sub, sub + 4, ...)
-        u64 acc = 0;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int b = sub + 4 * t;
-            if (wsel > c && wsel < nw && ((K >> b) & 1ull)) acc |= mask[(64 * c + b) * 16 + wsel];
-        }
-        acc |= __shfl_xor(acc, 16, 64);
-        acc |= __shfl_xor(acc, 32, 64);
-        remv |= acc;                                    // lanes >= 16 hold copies of words lane & 15: never read
-    }
-}
-
 int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld, float thresh, int* keep, void* stream) {
     if (N <= 0 || N > 65535 || k < 0 || ld < k) return AFI_ERR_BAD_ARG;
     if (k == 0) return AFI_OK;
     if (!boxes || !valid || !keep) return AFI_ERR_BAD_ARG;
     if (k > RPN_MAXK) return AFI_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(afi_rpn_nms_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, valid, k, ld, thresh, keep);
+    hipLaunchKernelGGL(afi_nms_kernel<false>, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, (const int*)nullptr, valid, k, ld, thresh,
+                       keep);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 

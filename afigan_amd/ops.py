@@ -953,6 +953,123 @@ def rpn_merge(boxes, vals, keep, level_off, post_k):
     return ob, ol, counts
 
 
+# ------------------------------------------------------------------------------------------------ ROI heads, box branch (roi_heads.py)
+ROI_MAX_CANDIDATES = 1024                   # M: the per-image candidate list afi_roi_nms holds in LDS
+ROI_MAX_POOLED = 14
+ROI_MAX_CLASSES = 1024
+
+
+def roi_align(levels, min_level, boxes, counts, S, sampling_ratio=0, out=None):
+    """Multi-level ROIAlignV2 (aligned): levels = pixel-major [N, C, H_l, W_l] views with strides 2^(min_level + l), boxes [N, P, 4] with
+    counts [N] int32 (RPN.forward_padded's layout); returns the pixel-major [N P, C, S, S] pooled features, rows past counts zero
+    (afi_roi_align)."""
+    _check_cuda(boxes, out, *levels)
+    _check_i32(counts)
+    L = len(levels)
+    if not 0 < L <= RPN_MAX_LEVELS:
+        raise _lib.AfiError(f"roi_align: 1..{RPN_MAX_LEVELS} levels, got {L}")
+    N, C_ = levels[0].shape[:2]
+    if boxes.dim() != 3 or boxes.shape[0] != N or boxes.shape[2] != 4 or not boxes.is_contiguous() or tuple(counts.shape) != (N,) \
+            or not counts.is_contiguous():
+        raise _lib.AfiError(f"roi_align: dense boxes [{N}, P, 4] and counts [{N}] expected, got {tuple(boxes.shape)} and {tuple(counts.shape)}")
+    if any(x.dim() != 4 or x.shape[0] != N or x.shape[1] != C_ for x in levels) or C_ % 4:
+        raise _lib.AfiError(f"roi_align: every level must be [N, C, H, W] with one N and one C % 4 == 0, got {[tuple(x.shape) for x in levels]}")
+    if not 0 < S <= ROI_MAX_POOLED or sampling_ratio < 0:
+        raise _lib.AfiError(f"roi_align: pooled size {S} (1..{ROI_MAX_POOLED}), sampling_ratio {sampling_ratio} (>= 0)")
+    P = boxes.shape[1]
+    if out is None:
+        out = new_pixel_major(N * P, C_, S, S, boxes.device)
+    elif tuple(out.shape) != (N * P, C_, S, S) or not is_dense_pm(out):
+        raise _lib.AfiError(f"roi_align: out must be a dense pixel-major [{N * P}, {C_}, {S}, {S}] tensor")
+    views = (View * L)(*[view_of(x) for x in levels])
+    hw = (C.c_int * (2 * L))(*[int(s) for x in levels for s in x.shape[2:]])
+    call("afi_roi_align", views, hw, L, int(min_level), N, C_, _p(boxes), _p(counts), P, int(S), int(sampling_ratio), _p(out), stream_ptr())
+    return out
+
+
+def roi_scores_boxes(pred, K, agnostic, proposals, counts, image_hw, weights, scale_clamp=4.135166556742356):
+    """pred: the predictor's output, pixel-major [N P, Cpad, 1, 1] (or [N P, Cpad]): K + 1 class logits (background last), then 4 K (or 4,
+    agnostic) deltas.  Returns (scores [N, P, K] fp32 = softmax without the background column, -inf past counts; boxes [N, P, K or 1, 4] decoded
+    from proposals [N, P, 4] and clipped to image_hw [N, 2]) (afi_roi_scores_boxes)."""
+    _check_cuda(pred, proposals, image_hw)
+    _check_i32(counts)
+    N, P = proposals.shape[:2]
+    Kb = 1 if agnostic else K
+    p2 = pred.reshape(pred.shape[0], -1) if pred.dim() == 4 and pred.shape[2:] == (1, 1) and pred.stride(1) == 1 else pred
+    if p2.dim() != 2 or p2.shape[0] != N * P or p2.shape[1] < K + 1 + 4 * Kb or p2.stride(1) != 1 or not 0 < K <= ROI_MAX_CLASSES \
+            or tuple(proposals.shape) != (N, P, 4) or tuple(image_hw.shape) != (N, 2) or tuple(counts.shape) != (N,):
+        raise _lib.AfiError(f"roi_scores_boxes: pred [{N * P}, >= {K + 1 + 4 * Kb}] with dense rows, proposals [N, P, 4], image sizes [N, 2], "
+                            f"counts [N] and 1 <= K <= {ROI_MAX_CLASSES} expected, got {tuple(pred.shape)}, {tuple(proposals.shape)}, "
+                            f"{tuple(image_hw.shape)}, {tuple(counts.shape)}, K {K}")
+    scores = torch.empty((N, P, K), device=pred.device, dtype=torch.float32)
+    boxes = torch.empty((N, P, Kb, 4), device=pred.device, dtype=torch.float32)
+    call("afi_roi_scores_boxes", _p(p2), p2.stride(0), N, P, int(K), int(bool(agnostic)), _p(proposals.contiguous()), _p(counts.contiguous()),
+         _p(image_hw.contiguous()), *[float(w) for w in weights], float(scale_clamp), _p(scores), _p(boxes), stream_ptr())
+    return scores, boxes
+
+
+def roi_candidates(scores, boxes, score_thresh, M=ROI_MAX_CANDIDATES):
+    """The min(M, P K) highest of scores [N, P, K] per image by (score descending, index r K + c ascending), NaN last; boxes [N, P, K or 1, 4].
+    Returns a dict: scores / idx / cls / valid [N, M], boxes [N, M, 4], n_over [N] (all scores above score_thresh) (afi_roi_candidates)."""
+    _check_cuda(scores, boxes)
+    N, P, K = scores.shape
+    if boxes.dim() != 4 or boxes.shape[:2] != (N, P) or boxes.shape[2] not in (1, K) or boxes.shape[3] != 4 or not scores.is_contiguous() \
+            or not boxes.is_contiguous() or not 0 < M <= ROI_MAX_CANDIDATES:
+        raise _lib.AfiError(f"roi_candidates: dense scores [N, P, K] and boxes [N, P, K or 1, 4], 1 <= M <= {ROI_MAX_CANDIDATES} expected, got "
+                            f"{tuple(scores.shape)}, {tuple(boxes.shape)}, M {M}")
+    # (K == 1: a [N, P, 1, 4] box list reads the same either way)
+    agnostic = int(boxes.shape[2] == 1)
+    n = _lib.load().afi_roi_candidates_ws_floats(N, P, K)
+    if n < 0:
+        raise _lib.AfiError(f"roi_candidates: unsupported score list {P} x {K}")
+    ws = new_workspace(n, scores.device) if n else None
+    dev = scores.device
+    r = {"scores": torch.empty((N, M), device=dev, dtype=torch.float32), "idx": torch.empty((N, M), device=dev, dtype=torch.int32),
+         "boxes": torch.empty((N, M, 4), device=dev, dtype=torch.float32), "cls": torch.empty((N, M), device=dev, dtype=torch.int32),
+         "valid": torch.empty((N, M), device=dev, dtype=torch.int32), "n_over": torch.empty((N,), device=dev, dtype=torch.int32)}
+    call("afi_roi_candidates", _p(scores), _p(boxes), N, P, K, agnostic, float(score_thresh), int(M), _p(r["scores"]), _p(r["idx"]), _p(r["boxes"]),
+         _p(r["cls"]), _p(r["valid"]), _p(r["n_over"]), _p(ws), n, stream_ptr())
+    return r
+
+
+def roi_nms(boxes, cls, valid, thresh, keep=None):
+    """Class-aware greedy NMS of the lists boxes [N, k, 4] (k <= 1024, in score order), cls / valid [N, k] int32: keep [N, k] int32.  The IoU is
+    taken on the boxes as they are, not on torchvision's class-offset copies (afi_roi_nms)."""
+    _check_cuda(boxes)
+    _check_i32(cls, valid)
+    N, k = valid.shape
+    if keep is None:
+        keep = torch.empty((N, k), device=boxes.device, dtype=torch.int32)
+    _check_i32(keep)
+    if k > RPN_MAX_TOPK:
+        raise _lib.AfiError(f"roi_nms: lists of at most {RPN_MAX_TOPK} boxes, got {k}")
+    if k == 0:
+        return keep
+    ld = _rpn_rows(valid, k)
+    if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(keep, k) != ld or _rpn_rows(cls, k) != ld or not (boxes.shape[0] == keep.shape[0] == cls.shape[0] == N):
+        raise _lib.AfiError("roi_nms: boxes, cls, valid and keep must be lists of one row stride")
+    call("afi_roi_nms", _p(boxes), _p(cls), _p(valid), N, k, ld, float(thresh), _p(keep), stream_ptr())
+    return keep
+
+
+def roi_pick(cand, keep, D):
+    """The first D kept candidates of roi_candidates' dict in list order: (boxes [N, D, 4], scores [N, D], classes [N, D] int32, counts [N],
+    truncated [N] = (n_over > M and kept < D)), zero past counts (afi_roi_pick)."""
+    _check_i32(keep, cand["cls"], cand["n_over"])
+    N, M = cand["scores"].shape
+    if tuple(keep.shape) != (N, M) or not keep.is_contiguous() or not 0 < D <= ROI_MAX_CANDIDATES:
+        raise _lib.AfiError(f"roi_pick: dense keep [{N}, {M}] and 1 <= D <= {ROI_MAX_CANDIDATES} expected, got {tuple(keep.shape)}, D {D}")
+    dev = keep.device
+    ob = torch.empty((N, D, 4), device=dev, dtype=torch.float32)
+    os_ = torch.empty((N, D), device=dev, dtype=torch.float32)
+    oc = torch.empty((N, D), device=dev, dtype=torch.int32)
+    counts = torch.empty((N,), device=dev, dtype=torch.int32)
+    trunc = torch.empty((N,), device=dev, dtype=torch.int32)
+    call("afi_roi_pick", _p(cand["boxes"]), _p(cand["scores"]), _p(cand["cls"]), _p(keep), _p(cand["n_over"]), N, M, int(D), _p(ob), _p(os_), _p(oc),
+         _p(counts), _p(trunc), stream_ptr())
+    return ob, os_, oc, counts, trunc
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

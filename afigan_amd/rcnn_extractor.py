@@ -2,9 +2,9 @@
 ``image_x0.5`` and ALSO hands back its FPN features, which the stage-2 loop trains against the guide network's.
 
 The backbone is the AFI pyramid of this package (FPN_AFIGAN / PAFPN_AFIGAN through BACKBONE_REGISTRY); the proposal generator is
-detectron2's when it is importable and this package's frozen, inference-only ``rpn.RPN`` otherwise; the ROI heads are detectron2
-components outside this package's scope: ``from_config`` builds them with detectron2 when it is importable, and the constructor takes any
-callables with their contracts otherwise (tests use small stand-ins)."""
+detectron2's when it is importable and this package's frozen, inference-only ``rpn.RPN`` otherwise; the ROI heads are built from a config
+by detectron2 when it is importable, and the constructor takes any callables with their contracts otherwise: ``roi_heads=`` this package's
+frozen box branch (``afigan_amd.build_roi_heads(cfg, backbone.output_shape())``, roi_heads.py), or a stand-in."""
 import torch
 import torch.nn as nn
 

@@ -1,0 +1,356 @@
+"""The frozen box branch of the inference configs' ROI heads: detectron2 v0.1.1's ``StandardROIHeads`` (``ROIPooler`` with ROIAlignV2,
+``FastRCNNConvFCHead`` with FCs only, ``FastRCNNOutputLayers``, ``fast_rcnn_inference``) at inference, forward only, fp32, on this package's
+HIP kernels.  The mask / keypoint branches and CascadeROIHeads are out of scope.
+
+Per image, on the padded proposal list boxes [N, P, 4] with counts [N] (``RPN.forward_padded``'s layout):
+  - ROIPooler: box -> level clamp(floor(4 + log2(sqrt(area) / 224)), min, max) of ``MODEL.ROI_HEADS.IN_FEATURES`` (zero / negative area: min),
+    ROIAlignV2 (aligned: start = x1 / stride - 0.5) to POOLER_RESOLUTION^2 bins, POOLER_SAMPLING_RATIO samples per bin and axis or
+    ceil(roi / S) when it is 0; a box with a non-positive side pools to zeros.  Rows past counts are zero.
+  - box head: x = relu(fc_i(x)), fc1 on the flattened [C, S, S] features; predictor: K + 1 class logits (background last) and 4 K (or 4,
+    CLS_AGNOSTIC_BBOX_REG) deltas.
+  - scores = softmax without the background column; boxes = Box2BoxTransform(BBOX_REG_WEIGHTS).apply_deltas with dw / dh clamped at
+    log(1000 / 16), clipped to the image; both in fp64 from the fp32 values, rounded once.
+  - the M = 1024 highest scores of the image (score descending, index r K + c ascending -- detectron2 leaves ties open; this is the rule
+    here; NaN below every number), valid = score > SCORE_THRESH_TEST; class-aware greedy NMS at NMS_THRESH_TEST on the boxes as they are
+    (torchvision's batched_nms adds a per-class coordinate offset first, which rounds the boxes: not done); the first
+    TEST.DETECTIONS_PER_IMAGE kept candidates.
+  - ``truncated`` = more than M scores above the threshold AND fewer than DETECTIONS_PER_IMAGE kept: the one case in which the cut at M can
+    change the result (greedy NMS in score order is decided by the list's prefix up to the last kept box).  ``forward`` raises then.
+
+Keys: ``box_head.fc{i}.{weight, bias}``, ``box_predictor.{cls_score, bbox_pred}.{weight, bias}`` -- detectron2's, so a detector checkpoint's
+``roi_heads.box_*`` keys load with strict=True.  Every parameter has requires_grad False.
+
+Kernels: afi_roi_align; the FCs and the predictor are afi_conv1x1_fwd over the R = N P rows as pixels (fc1 reads the pooled [R][S][S][C]
+memory in place, its weight permuted once from [out][C][S][S] to [out][S][S][C]; cls_score and bbox_pred are ONE weight, zero-padded to a
+multiple of 4; both rebuilt when a parameter changes: version, storage, device); afi_roi_scores_boxes, afi_roi_candidates, afi_roi_nms,
+afi_roi_pick (csrc/roi.hip).  No torch mm / addmm / softmax / sort / topk, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host
+read and can be captured in a hipGraph; ``forward`` reads ``counts`` and ``truncated`` once."""
+import math
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import AfiError
+from .registry import Registry
+from .resnet_guide import _get
+from .rpn import SCALE_CLAMP, Boxes
+
+ROI_MAX_CANDIDATES = ops.ROI_MAX_CANDIDATES
+
+
+def _d2_registry():
+    try:
+        from detectron2.modeling.roi_heads import ROI_HEADS_REGISTRY as reg
+        return reg
+    except Exception:
+        return None
+
+
+_D2 = _d2_registry()
+# detectron2's own "StandardROIHeads" owns the name there: its registry is used only when the name is free
+ROI_HEADS_REGISTRY = _D2 if _D2 is not None and "StandardROIHeads" not in _D2 else Registry("ROI_HEADS")
+
+
+def _check_feature(where, name, x):
+    if not getattr(x, "is_cuda", False):
+        raise AfiError(f"{where}: {name} is a CPU tensor; the ROI heads run on the GPU only, there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise AfiError(f"{where}: {name} is {x.dtype}; fp32 only (2-byte activations stop at the AFI backbone's boundary)")
+
+
+class ROIPooler(nn.Module):
+    """detectron2's ROIPooler for ``pooler_type`` ROIAlignV2 on a padded box list: one afi_roi_align over all levels."""
+
+    def __init__(self, output_size, scales, sampling_ratio, pooler_type="ROIAlignV2", canonical_box_size=224, canonical_level=4):
+        super().__init__()
+        if pooler_type != "ROIAlignV2":
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_TYPE {pooler_type!r} is not supported (ROIAlignV2 only)")
+        if isinstance(output_size, (tuple, list)):
+            if len(output_size) != 2 or output_size[0] != output_size[1]:
+                raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {output_size} must be square")
+            output_size = output_size[0]
+        self.output_size, self.sampling_ratio = int(output_size), int(sampling_ratio)
+        if not 0 < self.output_size <= ops.ROI_MAX_POOLED:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {output_size} is outside 1..{ops.ROI_MAX_POOLED}")
+        if self.sampling_ratio < 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO {sampling_ratio} must be >= 0")
+        if canonical_box_size != 224 or canonical_level != 4:
+            raise AfiError("roi_heads: the canonical box size / level are fixed at 224 / 4 (detectron2's defaults)")
+        levels = [-math.log2(s) for s in scales]
+        if not levels or len(levels) > ops.RPN_MAX_LEVELS or any(abs(l - round(l)) > 1e-9 for l in levels) \
+                or any(round(b) - round(a) != 1 for a, b in zip(levels, levels[1:])) or round(levels[0]) < 0:
+            raise AfiError(f"roi_heads: the strides of MODEL.ROI_HEADS.IN_FEATURES must be 1..{ops.RPN_MAX_LEVELS} consecutive powers of two, "
+                           f"got scales {list(scales)}")
+        self.min_level, self.max_level = int(round(levels[0])), int(round(levels[-1]))
+
+    def forward(self, x, boxes, counts):
+        """x: the levels [N, C, H_l, W_l]; boxes [N, P, 4], counts [N] int32 -> pixel-major [N P, C, S, S]."""
+        if len(x) != self.max_level - self.min_level + 1:
+            raise AfiError(f"roi_heads: {len(x)} feature levels for a pooler of {self.max_level - self.min_level + 1}")
+        return ops.roi_align([ops.pixel_major(t) for t in x], self.min_level, boxes, counts, self.output_size, self.sampling_ratio)
+
+
+class FastRCNNConvFCHead(nn.Module):
+    """detectron2's FastRCNNConvFCHead with NUM_CONV 0: ``fc1`` .. ``fc{NUM_FC}`` with ReLU."""
+
+    def __init__(self, input_shape, num_fc, fc_dim, num_conv=0, norm=""):
+        super().__init__()
+        if num_conv != 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NUM_CONV {num_conv} is not supported (FC-only box head; the conv head is CascadeROIHeads' "
+                           "and out of scope)")
+        if norm:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NORM {norm!r} is not supported (the FC-only box head has no norm)")
+        if num_fc < 1:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NUM_FC {num_fc} must be >= 1")
+        if fc_dim <= 0 or fc_dim % 4:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.FC_DIM {fc_dim} must be a positive multiple of 4")
+        self.input_shape = tuple(int(s) for s in input_shape)          # (C, S, S)
+        self.fcs = []
+        dim = self.input_shape[0] * self.input_shape[1] * self.input_shape[2]
+        for k in range(num_fc):
+            fc = nn.Linear(dim, fc_dim)
+            nn.init.kaiming_uniform_(fc.weight, a=1)                   # detectron2's c2_xavier_fill
+            nn.init.constant_(fc.bias, 0)
+            self.add_module(f"fc{k + 1}", fc)
+            self.fcs.append(fc)
+            dim = fc_dim
+        self.output_size = dim
+
+
+class FastRCNNOutputLayers(nn.Module):
+    def __init__(self, input_size, num_classes, cls_agnostic_bbox_reg, box_dim=4):
+        super().__init__()
+        self.num_classes, self.cls_agnostic_bbox_reg = int(num_classes), bool(cls_agnostic_bbox_reg)
+        self.cls_score = nn.Linear(input_size, num_classes + 1)
+        self.bbox_pred = nn.Linear(input_size, (1 if cls_agnostic_bbox_reg else num_classes) * box_dim)
+        nn.init.normal_(self.cls_score.weight, std=0.01)               # detectron2's initialisation
+        nn.init.normal_(self.bbox_pred.weight, std=0.001)
+        for l in (self.cls_score, self.bbox_pred):
+            nn.init.constant_(l.bias, 0)
+
+
+class Detections:
+    """One image's detections when detectron2's Instances is not importable: ``image_size``, ``pred_boxes``, ``scores``, ``pred_classes``."""
+
+    def __init__(self, image_size, pred_boxes, scores, pred_classes):
+        self.image_size, self.pred_boxes, self.scores, self.pred_classes = image_size, pred_boxes, scores, pred_classes
+
+    def __len__(self):
+        return len(self.pred_boxes)
+
+    def to(self, device):
+        return Detections(self.image_size, self.pred_boxes.to(device), self.scores.to(device), self.pred_classes.to(device))
+
+
+def _make_detections(image_size, boxes, scores, classes):
+    try:
+        from detectron2.structures import Boxes as D2Boxes, Instances
+    except Exception:
+        return Detections(tuple(image_size), Boxes(boxes), scores, classes)
+    r = Instances(tuple(image_size))
+    r.pred_boxes = D2Boxes(boxes)
+    r.scores = scores
+    r.pred_classes = classes
+    return r
+
+
+def _rows_as_pixels(t2d):
+    """A dense [R, C] matrix as the pixel-major [1, C, 1, R] tensor afi_conv1x1_fwd reads: one row per pixel, no copy."""
+    R, C_ = t2d.shape
+    return t2d.view(1, 1, R, C_).permute(0, 3, 1, 2)
+
+
+def _pixels_as_rows(t):
+    """The dense pixel-major [1, C, 1, R] output of afi_conv1x1_fwd as its [R, C] matrix, no copy."""
+    return t.permute(0, 2, 3, 1).reshape(t.shape[3], t.shape[1])
+
+
+@ROI_HEADS_REGISTRY.register()
+class StandardROIHeads(nn.Module):
+    def __init__(self, cfg, input_shape):
+        super().__init__()
+        m = cfg.MODEL
+        rh, bh = _get(m, "ROI_HEADS", None), _get(m, "ROI_BOX_HEAD", None)
+        if rh is None or bh is None:
+            raise AfiError("roi_heads: the config has no MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD section (afigan_amd.config.get_cfg declares them)")
+        if _get(rh, "NAME", "StandardROIHeads") != "StandardROIHeads":
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {rh.NAME!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
+        if _get(m, "MASK_ON", False):
+            raise AfiError("roi_heads: MODEL.MASK_ON is set -- box branch only; set MODEL.MASK_ON False")
+        if _get(m, "KEYPOINT_ON", False):
+            raise AfiError("roi_heads: MODEL.KEYPOINT_ON is set -- box branch only; set MODEL.KEYPOINT_ON False")
+        if _get(bh, "NAME", "FastRCNNConvFCHead") != "FastRCNNConvFCHead":
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NAME {bh.NAME!r} is not supported (FastRCNNConvFCHead only)")
+        self.in_features = list(rh.IN_FEATURES)
+        missing = [f for f in self.in_features if f not in input_shape]
+        if missing or not self.in_features:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.IN_FEATURES {self.in_features} are not all outputs of the backbone ({sorted(input_shape)})")
+        shapes = [input_shape[f] for f in self.in_features]
+        channels = {s.channels for s in shapes}
+        if len(channels) != 1:
+            raise AfiError(f"roi_heads: every feature of MODEL.ROI_HEADS.IN_FEATURES must have one channel count, got {sorted(channels)}")
+        C_ = channels.pop()
+        if C_ % 4:
+            raise AfiError(f"roi_heads: {C_} feature channels; a multiple of 4 is needed")
+        self.num_classes = int(_get(rh, "NUM_CLASSES", 80))
+        if not 0 < self.num_classes <= ops.ROI_MAX_CLASSES:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NUM_CLASSES {self.num_classes} is outside 1..{ops.ROI_MAX_CLASSES}")
+        self.test_score_thresh = float(_get(rh, "SCORE_THRESH_TEST", 0.05))
+        self.test_nms_thresh = float(_get(rh, "NMS_THRESH_TEST", 0.5))
+        self.test_detections_per_img = int(_get(_get(cfg, "TEST", None), "DETECTIONS_PER_IMAGE", 100))
+        if not 0 < self.test_detections_per_img <= ROI_MAX_CANDIDATES:
+            raise AfiError(f"roi_heads: TEST.DETECTIONS_PER_IMAGE {self.test_detections_per_img} is outside 1..{ROI_MAX_CANDIDATES}, the candidate "
+                           "list the selection kernels hold")
+        self.box_weights = tuple(float(w) for w in _get(bh, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0)))
+        if len(self.box_weights) != 4 or min(self.box_weights) <= 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS {self.box_weights} must be four positive numbers")
+        res = _get(bh, "POOLER_RESOLUTION", 14)
+        self.box_pooler = ROIPooler(res, [1.0 / s.stride for s in shapes], _get(bh, "POOLER_SAMPLING_RATIO", 0), _get(bh, "POOLER_TYPE", "ROIAlignV2"))
+        S = self.box_pooler.output_size
+        self.box_head = FastRCNNConvFCHead((C_, S, S), int(_get(bh, "NUM_FC", 0)), int(_get(bh, "FC_DIM", 1024)), int(_get(bh, "NUM_CONV", 0)),
+                                           _get(bh, "NORM", ""))
+        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes, bool(_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
+        self.mask_on = self.keypoint_on = False
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    # ------------------------------------------------------------------ weights in the kernels' layout
+    def _prepare(self):
+        """(fc1's weight in [out][S][S][C] order, the predictor's two layers as one [Cpad, D] weight and [Cpad] bias), rebuilt when a parameter
+        changes."""
+        fc1, pr = self.box_head.fcs[0], self.box_predictor
+        ts = [fc1.weight, pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias]
+        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
+        if getattr(self, "_prep_key", None) != key:
+            C_, S, _ = self.box_head.input_shape
+            out = fc1.weight.shape[0]
+            w1 = fc1.weight.detach().float().view(out, C_, S, S).permute(0, 2, 3, 1).reshape(out, S * S * C_).contiguous()
+            nc, nb = pr.cls_score.weight.shape[0], pr.bbox_pred.weight.shape[0]
+            cpad = (nc + nb + 3) // 4 * 4
+            w = torch.zeros((cpad, pr.cls_score.weight.shape[1]), device=ts[0].device, dtype=torch.float32)
+            b = torch.zeros((cpad,), device=ts[0].device, dtype=torch.float32)
+            w[:nc], w[nc:nc + nb] = ts[1].detach(), ts[3].detach()
+            b[:nc], b[nc:nc + nb] = ts[2].detach(), ts[4].detach()
+            self._prep, self._prep_key = (w1, w, b), key
+        return self._prep
+
+    # ------------------------------------------------------------------ checks
+    def _check(self, features, boxes=None, counts=None):
+        if self.training and torch.is_grad_enabled():
+            raise AfiError("roi_heads: the ROI heads are inference-only (frozen): call .eval(), or run them under torch.no_grad(); the detection "
+                           "losses and training are out of scope")
+        missing = [f for f in self.in_features if f not in features]
+        if missing:
+            raise AfiError(f"roi_heads: features {missing} are missing (got {sorted(features)})")
+        xs = [features[f] for f in self.in_features]
+        C_ = self.box_head.input_shape[0]
+        for f, x in zip(self.in_features, xs):
+            _check_feature("roi_heads", f"feature {f}", x)
+            if x.dim() != 4 or x.shape[1] != C_ or x.shape[0] != xs[0].shape[0]:
+                raise AfiError(f"roi_heads: feature {f} has shape {tuple(x.shape)}; [N, {C_}, H, W] expected")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise AfiError("roi_heads: the ROI heads are forward-only: run them under torch.no_grad() or detach their inputs")
+        if boxes is not None:
+            _check_feature("roi_heads", "boxes", boxes)
+            N = xs[0].shape[0]
+            if boxes.dim() != 3 or boxes.shape[0] != N or boxes.shape[2] != 4 or boxes.shape[1] == 0:
+                raise AfiError(f"roi_heads: boxes of shape {tuple(boxes.shape)}; [{N}, P >= 1, 4] expected")
+            if not torch.is_tensor(counts) or not counts.is_cuda or counts.dtype != torch.int32 or tuple(counts.shape) != (N,):
+                raise AfiError(f"roi_heads: counts must be an int32 tensor [{N}] on the GPU")
+        return xs
+
+    # ------------------------------------------------------------------ stages
+    def box_features(self, features, boxes, counts):
+        """The pooled features of the padded box list: pixel-major [N P, C, S, S], rows past counts zero."""
+        xs = self._check(features, boxes, counts)
+        with torch.no_grad():
+            return self.box_pooler(xs, boxes.contiguous(), counts.contiguous())
+
+    def box_head_forward(self, pooled, intermediates=False):
+        """pooled [R, C, S, S] pixel-major -> the predictor's output [R, Cpad] (K + 1 logits, the deltas, zero padding); intermediates: the list
+        of every FC's output [R, FC_DIM] as well."""
+        w1, wp, bp = self._prepare()
+        R = pooled.shape[0]
+        x = _rows_as_pixels(pooled.permute(0, 2, 3, 1).reshape(R, -1))
+        acts = []
+        for k, fc in enumerate(self.box_head.fcs):
+            x = ops.conv1x1_fwd(x, w1 if k == 0 else fc.weight.detach(), fc.bias.detach(), act=2)
+            acts.append(_pixels_as_rows(x))
+        pred = _pixels_as_rows(ops.conv1x1_fwd(x, wp, bp))
+        return (pred, acts) if intermediates else pred
+
+    def select(self, pred, boxes, counts, image_hw):
+        """scores and boxes, candidates, NMS, pick on the predictor's output; returns every stage's output in a dict."""
+        pr = self.box_predictor
+        scores, cboxes = ops.roi_scores_boxes(pred, pr.num_classes, pr.cls_agnostic_bbox_reg, boxes, counts, image_hw, self.box_weights, SCALE_CLAMP)
+        cand = ops.roi_candidates(scores, cboxes, self.test_score_thresh, ROI_MAX_CANDIDATES)
+        keep = ops.roi_nms(cand["boxes"], cand["cls"], cand["valid"], self.test_nms_thresh)
+        ob, os_, oc, oc_n, trunc = ops.roi_pick(cand, keep, self.test_detections_per_img)
+        return {"boxes": ob, "scores": os_, "classes": oc, "counts": oc_n, "truncated": trunc, "class_scores": scores, "class_boxes": cboxes,
+                "cand": cand, "keep": keep}
+
+    def forward_padded(self, image_sizes, features, boxes, counts, intermediates=False):
+        """(boxes [N, D, 4], scores [N, D], classes [N, D] int32, counts [N] int32, truncated [N] int32) on the device, D =
+        TEST.DETECTIONS_PER_IMAGE, rows past counts zero; image_sizes: [N, 2] device tensor (height, width) of the un-padded images; boxes
+        [N, P, 4] / counts [N]: the proposals as ``RPN.forward_padded`` returns them.  No host read: capturable in a hipGraph.  intermediates:
+        the dict of ``select`` plus ``pooled``, ``fc`` and ``pred`` instead."""
+        xs = self._check(features, boxes, counts)
+        if not torch.is_tensor(image_sizes) or not image_sizes.is_cuda:
+            raise AfiError("roi_heads: forward_padded takes the image sizes as an [N, 2] tensor on the GPU (forward() takes a list)")
+        if tuple(image_sizes.shape) != (xs[0].shape[0], 2):
+            raise AfiError(f"roi_heads: image sizes of shape {tuple(image_sizes.shape)} for a batch of {xs[0].shape[0]}")
+        with torch.no_grad():
+            boxes, counts = boxes.contiguous(), counts.contiguous()
+            pooled = self.box_pooler(xs, boxes, counts)
+            pred, acts = self.box_head_forward(pooled, intermediates=True)
+            r = self.select(pred, boxes, counts, image_sizes.to(torch.float32).contiguous())
+        if intermediates:
+            r.update(pooled=pooled, fc=acts, pred=pred)
+            return r
+        return r["boxes"], r["scores"], r["classes"], r["counts"], r["truncated"]
+
+    def forward(self, images, features, proposals, targets=None):
+        """detectron2's StandardROIHeads.forward at inference: (one result per image -- image_size, pred_boxes, scores, pred_classes (int64),
+        sorted by score --, {}).  One device-to-host read, of counts and truncated."""
+        if targets is not None:
+            raise AfiError("roi_heads: targets given -- the detection losses and label assignment are out of scope (inference only)")
+        xs = self._check(features)
+        sizes = [(int(h), int(w)) for h, w in images.image_sizes]
+        N, dev = xs[0].shape[0], xs[0].device
+        if len(sizes) != N or len(proposals) != N:
+            raise AfiError(f"roi_heads: {len(sizes)} image sizes and {len(proposals)} proposal lists for a batch of {N}")
+        pbs = []
+        for p in proposals:
+            b = p.proposal_boxes
+            b = b.tensor if hasattr(b, "tensor") else b
+            _check_feature("roi_heads", "proposal boxes", b)
+            pbs.append(b.reshape(-1, 4))
+        P = max(1, max(int(b.shape[0]) for b in pbs))
+        boxes = torch.zeros((N, P, 4), device=dev, dtype=torch.float32)
+        for n, b in enumerate(pbs):
+            boxes[n, :b.shape[0]] = b
+        counts = torch.tensor([int(b.shape[0]) for b in pbs], dtype=torch.int32).to(dev)
+        hw = torch.tensor(sizes, dtype=torch.float32).to(dev)
+        ob, os_, oc, cn, trunc = self.forward_padded(hw, features, boxes, counts)
+        host = torch.stack([cn, trunc]).tolist()
+        if any(host[1]):
+            raise AfiError(f"roi_heads: image(s) {[n for n, t in enumerate(host[1]) if t]} have more than {ROI_MAX_CANDIDATES} class scores above "
+                           f"MODEL.ROI_HEADS.SCORE_THRESH_TEST {self.test_score_thresh} and fewer than TEST.DETECTIONS_PER_IMAGE "
+                           f"{self.test_detections_per_img} survive NMS among the {ROI_MAX_CANDIDATES} highest (the candidate cap): the result "
+                           "could differ from the uncapped one; raise SCORE_THRESH_TEST")
+        return [_make_detections(sz, ob[n, :c], os_[n, :c], oc[n, :c].to(torch.int64)) for n, (sz, c) in enumerate(zip(sizes, host[0]))], {}
+
+    def forward_with_given_boxes(self, features, instances):
+        """detectron2's StandardROIHeads.forward_with_given_boxes with the mask and keypoint branches off: the instances unchanged."""
+        if self.training and torch.is_grad_enabled():
+            raise AfiError("roi_heads: the ROI heads are inference-only (frozen): call .eval(), or run them under torch.no_grad()")
+        return instances
+
+
+def build_roi_heads(cfg, input_shape):
+    """detectron2's build_roi_heads: the class registered under MODEL.ROI_HEADS.NAME."""
+    name = _get(_get(cfg.MODEL, "ROI_HEADS", None), "NAME", "StandardROIHeads")
+    if name != "StandardROIHeads":
+        raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (this package provides the box branch of 'StandardROIHeads')")
+    return ROI_HEADS_REGISTRY.get(name)(cfg, input_shape)

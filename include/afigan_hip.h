@@ -610,6 +610,46 @@ int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld
 int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
                   float* out_logits, int* counts, void* stream);
 
+/* ------------------------------------------------------------------ frozen box branch of StandardROIHeads (afigan_amd/roi_heads.py)
+ * detectron2 v0.1.1's ROIPooler (ROIAlignV2, aligned = True) and fast_rcnn_inference; the box head's FCs and the predictor between them run on
+ * afi_conv1x1_fwd over the R = N P rows as pixels.  Boxes of an image are rows of a padded [N][P][4] list with counts[N] (device int32): the
+ * layout afi_rpn_merge writes.  No entry point synchronises with the host or uses atomics of its own (afi_roi_candidates runs afi_rpn_topk, whose
+ * integer atomics only count); every result is bit-identical between runs.  N <= 65535 (AFI_ERR_BAD_ARG / AFI_ERR_UNSUPPORTED otherwise).
+ * afi_roi_align: levels = HOST array of L <= 8 pixel-major views [N][H_l][W_l][C], level_hw = HOST array {H_0, W_0, H_1, ...}; level l has
+ *   stride 2^(min_level + l).  C % 4 == 0, views 16-byte aligned with strides multiples of 4, 1 <= S <= 14, sampling_ratio >= 0.  out
+ *   [N P][S][S][C] dense (pixel-major [R, C, S, S]); rows j >= counts[n] are zero.  Per box, in fp64 from the fp32 box, nothing stored:
+ *   level = clamp(floor(4 + log2(sqrt(area) / 224)), min_level, min_level + L - 1), a zero or negative area (NaN too) at min_level;
+ *   scale = 2^-level, start = x1 scale - 0.5, roi_w = (x2 - x1) scale, bin = roi_w / S, grid = sampling_ratio if > 0 else ceil(roi / S) per axis;
+ *   sample (iy, ix) of bin (ph, pw) at start + p bin + (i + 0.5) bin / grid; bilinear as detectron2's bilinear_interpolate (zero outside
+ *   [-1, H] x [-1, W], clamped at 0, y_low >= H - 1 collapses onto the last row); output = sum / max(grid_h grid_w, 1).  The four weights are
+ *   rounded to fp32 and the sum is accumulated in fp32.  A box with a non-positive side gives zeros under either grid rule: with the adaptive grid
+ *   that is detectron2's own result (no samples, count max(0, 1)), and the same reading is applied to a fixed sampling_ratio.
+ * afi_roi_scores_boxes: pred [N P][ld_pred]: columns 0..K the class logits (background = column K), then 4 K (agnostic 0) or 4 (agnostic 1) box
+ *   deltas.  scores [N][P][K] = softmax over the K + 1 logits without the background column, boxes [N][P][Kb][4] (Kb = K, or 1 when agnostic) =
+ *   clip(Box2BoxTransform(wx, wy, ww, wh).apply_deltas(proposal), dw / dh clamped from above at scale_clamp), both evaluated in fp64 from the
+ *   fp32 inputs and rounded once; no size test.  Rows j >= counts[n]: scores -inf, boxes zero.  A row with a NaN logit scores NaN.  K <= 1024.
+ * afi_roi_candidates: the m = min(M, P K) highest scores of image n by (score descending, index r K + c ascending), NaN below every number:
+ *   cand_scores / cand_idx / cand_cls / cand_valid [N][M], cand_boxes [N][M][4]; valid = score > score_thresh; entries m.. are (-inf, -1, -1, 0,
+ *   zero box).  n_over[n] = the count of ALL scores of image n above score_thresh.  M <= 1024, P K < 2^22 - 1.  ws:
+ *   afi_roi_candidates_ws_floats(N, P, K) floats, 8-byte aligned (0: none needed; -1: unsupported).
+ * afi_roi_nms: afi_rpn_nms with classes: an earlier kept box suppresses a later one only when cls is equal and inter / (area_a + area_b - inter)
+ *   > thresh, in fp32 in that form on the boxes as they are (torchvision's batched_nms shifts every class by a coordinate offset instead, which
+ *   rounds the boxes; not done here).  k <= 1024, k = 0 launches nothing.
+ * afi_roi_pick: the first D <= 1024 kept candidates in list order: out_boxes [N][D][4], out_scores [N][D], out_classes [N][D] (int32), counts [N],
+ *   zero past the count; truncated[n] = (n_over[n] > M && kept < D), the one case in which cutting the list at M can change the result. */
+int afi_roi_align(const afi_view_t* levels, const int* level_hw, int L, int min_level, int N, int C, const float* boxes, const int* counts, int P,
+                  int S, int sampling_ratio, float* out, void* stream);
+int afi_roi_scores_boxes(const float* pred, long long ld_pred, int N, int P, int K, int agnostic, const float* proposals, const int* counts,
+                         const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, float* scores, float* boxes,
+                         void* stream);
+long long afi_roi_candidates_ws_floats(int N, int P, int K);
+int afi_roi_candidates(const float* scores, const float* boxes, int N, int P, int K, int agnostic, float score_thresh, int M, float* cand_scores,
+                       int* cand_idx, float* cand_boxes, int* cand_cls, int* cand_valid, int* n_over, float* ws, long long ws_floats,
+                       void* stream);
+int afi_roi_nms(const float* boxes, const int* cls, const int* valid, int N, int k, long long ld, float thresh, int* keep, void* stream);
+int afi_roi_pick(const float* cand_boxes, const float* cand_scores, const int* cand_cls, const int* keep, const int* n_over, int N, int M, int D,
+                 float* out_boxes, float* out_scores, int* out_classes, int* counts, int* truncated, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
