@@ -33,6 +33,7 @@ import torch.nn as nn
 from . import _lib, ops
 from .fpn_sr import ShapeSpec, _dense_pm, _LateralMergeFn
 from .config import afi_freeze
+from .frozen import prepared
 from .generator_rdb import Generator
 
 __all__ = ["BiFPN_AFIGAN", "LastLevelP6P7"]
@@ -359,7 +360,6 @@ class BiFPN_AFIGAN(nn.Module):
         self._out_feature_channels = {k: out_channels for k in self._out_features}
         self._size_divisibility = self._out_feature_strides[self._out_features[-1]]
         self._fuse_type = fuse_type
-        self._folded, self._folded_key = None, None
 
     @property
     def size_divisibility(self):
@@ -369,15 +369,12 @@ class BiFPN_AFIGAN(nn.Module):
         return {n: ShapeSpec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
 
     # ------------------------------------------------------------------------------------------------ folded inference weights
-    def _fingerprint(self):
-        return tuple(t._version for t in self.state_dict(keep_vars=True).values()) + (str(next(self.parameters()).device),)
-
     def _prepare(self):
-        """Eval-mode constants, rebuilt only when a parameter / buffer changed: BatchNorm folded into the 1x1 convs, depthwise
-        weights repacked tap-major."""
-        key = self._fingerprint()
-        if self._folded is not None and self._folded_key == key:
-            return self._folded
+        """Eval-mode constants, rebuilt only when a parameter / buffer changed (frozen.prepared): BatchNorm folded into the 1x1 convs,
+        depthwise weights repacked tap-major."""
+        return prepared(self, "folded", self.state_dict(keep_vars=True).values(), self._fold_all)
+
+    def _fold_all(self):
         f = {}
         bb = self.before_bifpn
         for name in ("lateral3", "lateral4", "lateral5", "p4_skip", "p5_skip"):
@@ -391,7 +388,6 @@ class BiFPN_AFIGAN(nn.Module):
                 cdw = m.depthwise.weight.shape[0]
                 dw = m.depthwise.weight.detach().reshape(cdw, 9).t().contiguous()
                 f[(l, tag)] = (dw,) + _fold(m.pointwise, m.norm)
-        self._folded, self._folded_key = f, key
         return f
 
     def set_process_group(self, group):

@@ -153,11 +153,16 @@ def is_dense_pm(t: torch.Tensor) -> bool:
     return t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()
 
 
+def to_ohwi(w: torch.Tensor) -> torch.Tensor:
+    """[O,I,kh,kw] weight with its memory made [O][kh][kw][I] (what the conv kernels read)."""
+    return w.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
 def ohwi(w: torch.Tensor) -> torch.Tensor:
-    """[O,I,kh,kw] weight whose memory is [O][kh][kw][I] (what the kernels read); copies only if it is not already."""
+    """[O,I,kh,kw] weight whose memory is [O][kh][kw][I]; copies only if it is not already."""
     if w.permute(0, 2, 3, 1).is_contiguous():
         return w
-    return keep_alive(w.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2))
+    return keep_alive(to_ohwi(w))
 
 
 def new_ohwi(O, I, kh, kw, device, zero=True) -> torch.Tensor:

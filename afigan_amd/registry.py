@@ -6,6 +6,7 @@ names are registered with detectron2's registry when detectron2 is importable an
 so ``BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg, input_shape)`` resolves either way.  The bottom-up networks (ResNet, ResNeSt,
 Swin) are NOT part of this package: a builder looks its bottom-up builder up when it is CALLED -- detectron2's / the reference's if
 importable, or one installed with ``set_bottom_up_builder`` -- and fails with a clear message when there is none."""
+import importlib
 from typing import Callable, Dict
 
 from . import _lib
@@ -53,6 +54,26 @@ _D2 = _detectron2_backbone_registry()
 BACKBONE_REGISTRY = _D2 if _D2 is not None else Registry("BACKBONE")
 USING_DETECTRON2_REGISTRY = _D2 is not None
 GUIDE_ARCH_REGISTRY = Registry("GUIDE_ARCH")          # meta_arch/build.py:5
+
+
+def detectron2_or_local(module: str, attr: str, own: str, local: str):
+    """detectron2's registry ``module.attr`` when it is importable and the name `own` is free in it (detectron2's own class owns the name
+    otherwise), else a local ``Registry(local)``."""
+    try:
+        reg = getattr(importlib.import_module(module), attr)
+    except Exception:
+        return Registry(local)
+    return reg if own not in reg else Registry(local)
+
+
+def register_local_backbone(builder) -> bool:
+    """`builder` in the LOCAL backbone registry only: with detectron2 installed its name is detectron2's.  True when it is registered."""
+    if USING_DETECTRON2_REGISTRY:
+        return False
+    if builder.__name__ not in BACKBONE_REGISTRY:
+        BACKBONE_REGISTRY.register(builder)
+    return True
+
 
 _BOTTOM_UP: Dict[str, Callable] = {}
 

@@ -16,26 +16,22 @@ The parameter tree and key names are detectron2-ResNeSt's (``stem.conv1_{1,2,3}.
 ``conv2.conv.weight``, ``conv2.bn0.*``, ``conv2.fc1.{weight,bias}``, ``conv2.bn1.*``, ``conv2.fc2.*``, ``conv3.*``, ``shortcut.*``), and so is
 the freezing: with ``BACKBONE.FREEZE_AT`` = k the stem (k >= 1) and the stages res2..res{k} carry FrozenBatchNorm2d, later norms the
 config's type (BN / SyncBN, with ``num_batches_tracked``), so a trained checkpoint's key set matches exactly.  Every norm is folded into its
-conv (fp64, resnet_guide._Frozen), whatever its type: the module only runs in inference.
+conv (fp64, frozen.fold_conv), whatever its type: the module only runs in inference.
 
 Kernels: the stem's first conv afi_resnest_stem_fwd; the other 3x3 convs afi_conv3x3_fwd / afi_conv3x3_wino_infer, chosen as
-resnet_guide._conv3x3 chooses (a split-attention conv: one launch per radix group, through channel views of its input, each writing its
+frozen.conv3x3 chooses (a split-attention conv: one launch per radix group, through channel views of its input, each writing its
 own split); every 1x1 conv afi_conv1x1_fwd (conv3 with the shortcut add and the ReLU in its epilogue); the stem pool and the avg_down pool
 afi_resnest_pool_nhwc; split attention afi_resnest_splat_gap / _attn / _combine (AVD fused into the combine).  No MIOpen, hipBLASLt or
 torch conv / pool kernel runs, and no atomics: the forward is bit-identical from run to run and under hipGraph replay.
 
 Out of scope (AfiError at build time): radix != 2, NUM_GROUPS > 1, dilation, deformable convs, norms other than FrozenBN / BN / SyncBN,
 STRIDE_IN_1X1 = True; at call time, a CPU tensor and a forward that autograd could differentiate."""
-import types
-
-import torch
 import torch.nn as nn
 
-from . import ops, registry
+from . import frozen, ops, registry
 from ._lib import AfiError
-from .fpn_sr import ShapeSpec
-from .resnet_guide import FPN, FrozenBatchNorm2d, _Frozen, _conv1x1, _conv3x3, _get
-from .resnet_guide import Conv2d as _GuideConv2d
+from .frozen import FrozenBatchNorm2d, cfg_get, conv1x1, conv3x3, fold_conv
+from .resnet_guide import FPN, ResNetBase
 
 _BLOCKS = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}
 _STEM_WIDTH = {50: 32, 101: 64}
@@ -52,17 +48,12 @@ def _norm(kind, channels):
     return m
 
 
-class Conv2d(_GuideConv2d):
-    """resnet_guide.Conv2d with the norm of the given kind ("" / None: no norm)."""
+class Conv2d(frozen.Conv2d):
+    """frozen.Conv2d with the norm of the given kind ("" / None: no norm)."""
 
     def __init__(self, cin, cout, k, stride=1, bias=False, norm="FrozenBN"):
         super().__init__(cin, cout, k, stride=stride, bias=bias, norm=False)
         self.norm = _norm(norm, cout) if norm else None
-
-
-def _fold(conv, norm):
-    """resnet_guide.Conv2d.fold of `conv` through a norm that is not its own child (SplAtConv2d keeps bn0 / bn1 beside its convs)."""
-    return _GuideConv2d.fold(types.SimpleNamespace(weight=conv.weight, bias=conv.bias, norm=norm, kernel_size=conv.kernel_size))
 
 
 class SplAtConv2d(nn.Module):
@@ -79,13 +70,13 @@ class SplAtConv2d(nn.Module):
         self.fc2 = Conv2d(inter, channels * self.radix, 1, bias=True, norm=None)
 
     def fold(self):
-        return _fold(self.conv, self.bn0), _fold(self.fc1, self.bn1), self.fc2.fold()
+        return fold_conv(self.conv, self.bn0), fold_conv(self.fc1, self.bn1), self.fc2.fold()      # (bn0 / bn1 stand beside their convs)
 
     def run(self, y, f, avd):
         (wc, bc), (w1, b1), (w2, b2) = f[id(self)]
         g = self.channels
-        s0 = _conv3x3(y[:, :g // 2], (wc[:g], bc[:g]), relu=True)
-        s1 = _conv3x3(y[:, g // 2:], (wc[g:], bc[g:]), relu=True)
+        s0 = conv3x3(y[:, :g // 2], (wc[:g], bc[:g]), relu=True)
+        s1 = conv3x3(y[:, g // 2:], (wc[g:], bc[g:]), relu=True)
         return ops.splat_attention(s0, s1, w1, b1, w2, b2, avd=avd)[0]
 
 
@@ -98,8 +89,8 @@ class DeepStem(nn.Module):
 
     def run(self, x, f):
         y = ops.resnest_stem(x, *f[id(self.conv1_1)])
-        y = _conv3x3(y, f[id(self.conv1_2)], relu=True)
-        y = _conv3x3(y, f[id(self.conv1_3)], relu=True)
+        y = conv3x3(y, f[id(self.conv1_2)], relu=True)
+        y = conv3x3(y, f[id(self.conv1_3)], relu=True)
         return ops.resnest_pool(y, "max3s2p1")
 
 
@@ -119,14 +110,15 @@ class BottleneckBlock(nn.Module):
             s = x
         else:
             xs = ops.resnest_pool(x, "avg2s2_ceil") if self.stride == 2 else x           # (AvgPool2d(1, 1) is the identity)
-            s = _conv1x1(xs, f[id(self.shortcut)])
-        y = _conv1x1(x, f[id(self.conv1)], relu=True)
+            s = conv1x1(xs, f[id(self.shortcut)])
+        y = conv1x1(x, f[id(self.conv1)], relu=True)
         y = self.conv2.run(y, f, self.avd)
-        return _conv1x1(y, f[id(self.conv3)], add=s, relu=True)
+        return conv1x1(y, f[id(self.conv3)], add=s, relu=True)
 
 
-class ResNeSt(_Frozen):
-    """The bottom-up: ``forward(x [N,3,H,W]) -> {name: pixel-major fp32 features}`` for ``out_features`` (subset of stem, res2..res5)."""
+class ResNeSt(ResNetBase):
+    """The bottom-up of detectron2-ResNeSt's ResNeSt-50 / -101 (see ResNetBase for the forward)."""
+    what = "the ResNeSt bottom-up"
 
     def __init__(self, depth=50, out_features=("res2", "res3", "res4", "res5"), norm="FrozenBN", freeze_at=2, width_per_group=64,
                  bottleneck_width=64, res2_out_channels=256):
@@ -135,36 +127,15 @@ class ResNeSt(_Frozen):
             raise AfiError(f"resnest_backbone: RESNETS.DEPTH {depth} is not supported (50 or 101)")
         if norm not in NORMS:
             raise AfiError(f"resnest_backbone: RESNETS.NORM {norm!r} is not supported (one of {', '.join(NORMS)}: folded into the convs)")
-        names = ["stem", "res2", "res3", "res4", "res5"]
-        bad = [f for f in out_features if f not in names]
-        if bad or not out_features:
-            raise AfiError(f"resnest_backbone: unknown RESNETS.OUT_FEATURES {list(out_features)}")
+        n_stages = self._num_stages("resnest_backbone", out_features)
         group_width = int(width_per_group * (bottleneck_width / 64.0))
-        n_stages = max(names.index(f) for f in out_features)
         if group_width % 8 or group_width * 2 ** (n_stages - 1) > 1024 or res2_out_channels % 4:
             raise AfiError(f"resnest_backbone: group width {group_width} (a multiple of 8, at most 1024 in res5) and RES2_OUT_CHANNELS "
                            f"{res2_out_channels} (a multiple of 4) are required")
-        self._out_features = list(out_features)
         sw = _STEM_WIDTH[depth]
-        self.stem = DeepStem(sw, "FrozenBN" if freeze_at >= 1 else norm)
-        self._out_feature_channels, self._out_feature_strides = {"stem": 2 * sw}, {"stem": 4}
-        cin, cout, gw = 2 * sw, res2_out_channels, group_width
-        self.stage_names = []
-        for i, n in enumerate(_BLOCKS[depth][:n_stages]):
-            name, first = f"res{i + 2}", (1 if i == 0 else 2)
-            stage_norm = "FrozenBN" if freeze_at >= i + 2 else norm
-            blocks = [BottleneckBlock(cin if j == 0 else cout, cout, gw, first if j == 0 else 1, stage_norm) for j in range(n)]
-            self.add_module(name, nn.Sequential(*blocks))
-            self.stage_names.append(name)
-            self._out_feature_channels[name], self._out_feature_strides[name] = cout, 4 * 2 ** i
-            cin, cout, gw = cout, 2 * cout, 2 * gw
-
-    @property
-    def size_divisibility(self):
-        return 0
-
-    def output_shape(self):
-        return {n: ShapeSpec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
+        norm_of = lambda stage: "FrozenBN" if freeze_at >= stage else norm          # noqa: E731  (the stem is stage 1)
+        self._build(out_features, DeepStem(sw, norm_of(1)), 2 * sw, _BLOCKS[depth][:n_stages], res2_out_channels, group_width,
+                    lambda stage, cin, cout, gw, stride: BottleneckBlock(cin, cout, gw, stride, norm_of(stage)))
 
     def _own_convs(self):
         convs = [self.stem.conv1_1, self.stem.conv1_2, self.stem.conv1_3]
@@ -173,49 +144,28 @@ class ResNeSt(_Frozen):
                 convs += [m for m in (blk.shortcut, blk.conv1, blk.conv2, blk.conv3) if m is not None]
         return convs
 
-    def _check_frozen(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise AfiError("the ResNeSt bottom-up is forward-only (frozen): run it under torch.no_grad() with no parameter or input requiring grad")
-        if not x.is_cuda:
-            raise AfiError("the ResNeSt bottom-up runs on the GPU only (got a CPU tensor); there is no CPU fallback")
-
-    def forward(self, x):
-        self._check_frozen(x)
-        with torch.no_grad():
-            f = self._prepare()
-            out = {}
-            y = self.stem.run(x.float(), f)
-            if "stem" in self._out_features:
-                out["stem"] = y
-            for name in self.stage_names:
-                for blk in getattr(self, name):
-                    y = blk.run(y, f)
-                if name in self._out_features:
-                    out[name] = y
-        return out
-
 
 def _resnest_from_cfg(cfg, input_shape=None):
     """build_resnest_backbone (resnest.py:482-620) restricted to the frozen, forward-only module: refuses every option it does not implement."""
-    r = _get(cfg.MODEL, "RESNETS", None)
+    r = cfg_get(cfg.MODEL, "RESNETS", None)
     if input_shape is not None and getattr(input_shape, "channels", 3) not in (None, 3):
         raise AfiError(f"resnest_backbone: 3 input channels only, got {input_shape.channels}")
-    radix = _get(r, "RADIX", 1)
+    radix = cfg_get(r, "RADIX", 1)
     if radix != 2:
         raise AfiError(f"resnest_backbone: RESNETS.RADIX {radix} is not supported (2 only; radix 1 is the plain ResNet of resnet_guide)")
-    if _get(r, "NUM_GROUPS", 1) != 1:
-        raise AfiError(f"resnest_backbone: RESNETS.NUM_GROUPS {_get(r, 'NUM_GROUPS', 1)} is not supported (cardinality 1 only)")
-    if _get(r, "RES5_DILATION", 1) != 1:
-        raise AfiError(f"resnest_backbone: RESNETS.RES5_DILATION {_get(r, 'RES5_DILATION', 1)} is not supported (no dilation)")
-    if any(_get(r, "DEFORM_ON_PER_STAGE", [False] * 4)):
+    if cfg_get(r, "NUM_GROUPS", 1) != 1:
+        raise AfiError(f"resnest_backbone: RESNETS.NUM_GROUPS {cfg_get(r, 'NUM_GROUPS', 1)} is not supported (cardinality 1 only)")
+    if cfg_get(r, "RES5_DILATION", 1) != 1:
+        raise AfiError(f"resnest_backbone: RESNETS.RES5_DILATION {cfg_get(r, 'RES5_DILATION', 1)} is not supported (no dilation)")
+    if any(cfg_get(r, "DEFORM_ON_PER_STAGE", [False] * 4)):
         raise AfiError("resnest_backbone: deformable convolutions (RESNETS.DEFORM_ON_PER_STAGE) are not supported")
-    if _get(r, "STRIDE_IN_1X1", True):
+    if cfg_get(r, "STRIDE_IN_1X1", True):
         raise AfiError("resnest_backbone: RESNETS.STRIDE_IN_1X1 True is not supported: with radix 2 the AVD pool already down-samples a "
                        "stride-2 block, so a strided conv1 would down-sample it twice and its residual add would not match the shortcut "
                        "(the published ResNeSt configs set STRIDE_IN_1X1: False)")
-    return ResNeSt(depth=_get(r, "DEPTH", 50), out_features=list(_get(r, "OUT_FEATURES", ["res4"])), norm=_get(r, "NORM", "FrozenBN"),
-                   freeze_at=int(_get(_get(cfg.MODEL, "BACKBONE", None), "FREEZE_AT", 2)), width_per_group=_get(r, "WIDTH_PER_GROUP", 64),
-                   bottleneck_width=_get(r, "BOTTLENECK_WIDTH", 64), res2_out_channels=_get(r, "RES2_OUT_CHANNELS", 256))
+    return ResNeSt(depth=cfg_get(r, "DEPTH", 50), out_features=list(cfg_get(r, "OUT_FEATURES", ["res4"])), norm=cfg_get(r, "NORM", "FrozenBN"),
+                   freeze_at=int(cfg_get(cfg_get(cfg.MODEL, "BACKBONE", None), "FREEZE_AT", 2)), width_per_group=cfg_get(r, "WIDTH_PER_GROUP", 64),
+                   bottleneck_width=cfg_get(r, "BOTTLENECK_WIDTH", 64), res2_out_channels=cfg_get(r, "RES2_OUT_CHANNELS", 256))
 
 
 def build_resnest_backbone(cfg, input_shape=None):
@@ -225,11 +175,11 @@ def build_resnest_backbone(cfg, input_shape=None):
 
 def build_resnest_fpn_backbone(cfg, input_shape=None):
     """detectron2-ResNeSt's build_resnest_fpn_backbone (ResNeSt + FPN + LastLevelMaxPool) as the frozen guide of stages 1 and 2."""
-    fpn = _get(cfg.MODEL, "FPN", None)
-    if _get(fpn, "NORM", "") != "":
-        raise AfiError(f"resnest_backbone: FPN.NORM {_get(fpn, 'NORM', '')!r} is not supported (the guide's FPN has biased convs, no norm)")
-    return FPN(_resnest_from_cfg(cfg, input_shape), list(_get(fpn, "IN_FEATURES", ["res2", "res3", "res4", "res5"])),
-               _get(fpn, "OUT_CHANNELS", 256), _get(fpn, "FUSE_TYPE", "sum"))
+    fpn = cfg_get(cfg.MODEL, "FPN", None)
+    if cfg_get(fpn, "NORM", "") != "":
+        raise AfiError(f"resnest_backbone: FPN.NORM {cfg_get(fpn, 'NORM', '')!r} is not supported (the guide's FPN has biased convs, no norm)")
+    return FPN(_resnest_from_cfg(cfg, input_shape), list(cfg_get(fpn, "IN_FEATURES", ["res2", "res3", "res4", "res5"])),
+               cfg_get(fpn, "OUT_CHANNELS", 256), cfg_get(fpn, "FUSE_TYPE", "sum"))
 
 
 def use_as_bottom_up():
@@ -238,13 +188,4 @@ def use_as_bottom_up():
     registry.set_bottom_up_builder("resnest", build_resnest_backbone)
 
 
-def _register():
-    """``build_resnest_fpn_backbone`` in the LOCAL registry only: with detectron2 installed the name is detectron2-ResNeSt's."""
-    if registry.USING_DETECTRON2_REGISTRY:
-        return False
-    if "build_resnest_fpn_backbone" not in registry.BACKBONE_REGISTRY:
-        registry.BACKBONE_REGISTRY.register(build_resnest_fpn_backbone)
-    return True
-
-
-REGISTERED = _register()
+REGISTERED = registry.register_local_backbone(build_resnest_fpn_backbone)    # (with detectron2 installed the name is detectron2-ResNeSt's)

@@ -20,96 +20,34 @@ import torch.nn as nn
 from . import ops, registry
 from ._lib import AfiError
 from .fpn_sr import ShapeSpec
+from .frozen import FROZEN_BN_EPS, Conv2d, FrozenBatchNorm2d, cfg_get, check_forward_only, conv1x1, conv3x3, prepared  # noqa: F401
 
-FROZEN_BN_EPS = 1e-5
 _BLOCKS = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}
 
 
-class FrozenBatchNorm2d(nn.Module):
-    """detectron2.layers.FrozenBatchNorm2d: y = (x - running_mean) / sqrt(running_var + eps) * weight + bias, all four buffers."""
-
-    def __init__(self, num_features, eps=FROZEN_BN_EPS):
-        super().__init__()
-        self.num_features, self.eps = num_features, eps
-        self.register_buffer("weight", torch.ones(num_features))
-        self.register_buffer("bias", torch.zeros(num_features))
-        self.register_buffer("running_mean", torch.zeros(num_features))
-        self.register_buffer("running_var", torch.ones(num_features) - eps)
-
-
-class Conv2d(nn.Module):
-    """detectron2.layers.Conv2d's parameter tree (weight, optional bias, optional norm child); frozen: requires_grad is off."""
-
-    def __init__(self, cin, cout, k, stride=1, bias=False, norm=True):
-        super().__init__()
-        self.kernel_size, self.stride = k, stride
-        w = torch.randn(cout, cin, k, k) * (2.0 / (cout * k * k)) ** 0.5          # c2_msra_fill's scale (fan_out); a checkpoint replaces it
-        self.weight = nn.Parameter(w, requires_grad=False)
-        self.bias = nn.Parameter(torch.zeros(cout), requires_grad=False) if bias else None
-        self.norm = FrozenBatchNorm2d(cout) if norm else None
-
-    def fold(self, scale=1.0):
-        """(weight, bias) with the norm folded in, computed in fp64 and rounded once; 3x3 weights in the kernels' [O][kh][kw][I] memory,
-        1x1 weights as [Cout, Cin].  `scale` multiplies the bias (the FPN's "avg" fuse halves it)."""
-        w = self.weight.detach().double()
-        b = self.bias.detach().double() if self.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
-        n = self.norm
-        if n is not None:
-            s = n.weight.double() * torch.rsqrt(n.running_var.double() + n.eps)
-            w = w * s.view(-1, 1, 1, 1)
-            b = (b - n.running_mean.double()) * s + n.bias.double()
-        w, b = w.float(), (b * scale).float().contiguous()
-        if self.kernel_size == 1:
-            return w.reshape(w.shape[0], w.shape[1]).contiguous(), b
-        if self.kernel_size == 3:
-            return w.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2), b
-        return w.contiguous(), b
-
-
-def _conv1x1(x, wb, stride=1, add=None, relu=False, alpha=1.0, add_scale=1.0):
-    if stride != 1:
-        x = x[:, :, ::stride, ::stride]                                 # (a view: the kernel walks the strides)
-    if add is not None and add.shape[-2:] != x.shape[-2:]:
-        raise AfiError(f"resnet_guide: addend {tuple(add.shape)} does not match the conv output {tuple(x.shape[-2:])}")
-    return ops.conv1x1_fwd(x, wb[0], wb[1], add=add, add_scale=add_scale, alpha=alpha, act=2 if relu else 0)
-
-
-def _conv3x3(x, wb, stride=1, relu=False):
-    act = 2 if relu else 0
-    if stride == 2:
-        return ops.conv3x3s2_fwd(x, wb[0], wb[1], act=act)
-    N, C, H, W = x.shape
-    if C >= 128 and wb[0].shape[0] >= 128 and N * H * W >= 1024:      # the Winograd form (F(4x4) tiles on maps of >= 8192 pixels)
-        return ops.conv3x3_wino_infer(x, wb[0], wb[1], act=act)
-    return ops.conv3x3_fwd(x, wb[0], wb[1], lrelu=act)
-
-
 class _Frozen(nn.Module):
-    """Folded weights of the convs this module runs itself, rebuilt when a parameter / buffer of them changes (version, storage, device)."""
+    """Folded weights of the convs this module runs itself, rebuilt when a parameter / buffer of them changes (frozen.prepared)."""
+    what = "the ResNet-FPN guide"
 
     def _own_convs(self):
         raise NotImplementedError
 
+    def _fold_own(self, convs):
+        return {id(m): m.fold() for m in convs}
+
     def _prepare(self):
         convs = self._own_convs()
         ts = [t for m in convs for t in list(m.parameters()) + list(m.buffers())]
-        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
-        if getattr(self, "_folded_key", None) != key:
-            self._folded = {id(m): m.fold() for m in convs}
-            self._folded_key = key
-        return self._folded
-
-    def _check_frozen(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise AfiError("the ResNet-FPN guide is forward-only (frozen): run it under torch.no_grad() with no parameter or input requiring grad")
-        if not x.is_cuda:
-            raise AfiError("the ResNet-FPN guide runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+        return prepared(self, "folded", ts, lambda: self._fold_own(convs))
 
 
 class BasicStem(nn.Module):
     def __init__(self, in_channels=3, out_channels=64):
         super().__init__()
         self.conv1 = Conv2d(in_channels, out_channels, 7, stride=2)
+
+    def run(self, x, f):
+        return ops.resnet_stem(x, *f[id(self.conv1)])
 
 
 class BottleneckBlock(nn.Module):
@@ -124,40 +62,37 @@ class BottleneckBlock(nn.Module):
         self.conv3 = Conv2d(bottleneck, cout, 1)
 
     def run(self, x, f):
-        s = x if self.shortcut is None else _conv1x1(x, f[id(self.shortcut)], self.shortcut.stride)
-        y = _conv1x1(x, f[id(self.conv1)], self.conv1.stride, relu=True)
-        y = _conv3x3(y, f[id(self.conv2)], self.conv2.stride, relu=True)
-        return _conv1x1(y, f[id(self.conv3)], add=s, relu=True)
+        s = x if self.shortcut is None else conv1x1(x, f[id(self.shortcut)], self.shortcut.stride)
+        y = conv1x1(x, f[id(self.conv1)], self.conv1.stride, relu=True)
+        y = conv3x3(y, f[id(self.conv2)], self.conv2.stride, relu=True)
+        return conv1x1(y, f[id(self.conv3)], add=s, relu=True)
 
 
-class ResNet(_Frozen):
-    """The bottom-up: ``forward(x [N,3,H,W]) -> {name: pixel-major features}`` for ``out_features`` (subset of stem, res2..res5)."""
+class ResNetBase(_Frozen):
+    """What the ResNet and ResNeSt bottom-ups share: a stem (4x down) and the stages res2.. of bottleneck blocks, each twice as wide and, from
+    res3 on, half the size; ``forward(x [N,3,H,W]) -> {name: pixel-major fp32 features}`` for ``out_features`` (subset of stem, res2..res5)."""
+    STAGES = ["stem", "res2", "res3", "res4", "res5"]
 
-    def __init__(self, depth=50, out_features=("res2", "res3", "res4", "res5"), stride_in_1x1=True, width_per_group=64,
-                 res2_out_channels=256, stem_out_channels=64):
-        super().__init__()
-        if depth not in _BLOCKS:
-            raise AfiError(f"resnet_guide: RESNETS.DEPTH {depth} is not supported (50 or 101)")
-        if stem_out_channels != 64:
-            raise AfiError(f"resnet_guide: RESNETS.STEM_OUT_CHANNELS {stem_out_channels} is not supported (the stem kernel makes 64)")
-        names = ["stem", "res2", "res3", "res4", "res5"]
-        bad = [f for f in out_features if f not in names]
-        if bad or not out_features:
-            raise AfiError(f"resnet_guide: unknown RESNETS.OUT_FEATURES {list(out_features)}")
-        if (width_per_group % 4) or (res2_out_channels % 4):
-            raise AfiError("resnet_guide: channel counts must be multiples of 4")
+    @classmethod
+    def _num_stages(cls, prefix, out_features):
+        if not out_features or any(f not in cls.STAGES for f in out_features):
+            raise AfiError(f"{prefix}: unknown RESNETS.OUT_FEATURES {list(out_features)}")
+        return max(cls.STAGES.index(f) for f in out_features)
+
+    def _build(self, out_features, stem, stem_channels, counts, res2_out_channels, width, block):
+        """`counts` blocks per stage, each ``block(stage, cin, cout, width, stride)``; `width` (the bottleneck's) doubles per stage."""
         self._out_features = list(out_features)
-        self.stem = BasicStem(3, 64)
-        self._out_feature_channels, self._out_feature_strides = {"stem": 64}, {"stem": 4}
-        cin, cout, mid = 64, res2_out_channels, width_per_group
+        self.stem = stem
+        self._out_feature_channels, self._out_feature_strides = {"stem": stem_channels}, {"stem": 4}
+        cin, cout = stem_channels, res2_out_channels
         self.stage_names = []
-        for i, n in enumerate(_BLOCKS[depth][:max(names.index(f) for f in out_features)]):
+        for i, n in enumerate(counts):
             name, first = f"res{i + 2}", (1 if i == 0 else 2)
-            blocks = [BottleneckBlock(cin if j == 0 else cout, cout, mid, first if j == 0 else 1, stride_in_1x1) for j in range(n)]
+            blocks = [block(i + 2, cin if j == 0 else cout, cout, width, first if j == 0 else 1) for j in range(n)]
             self.add_module(name, nn.Sequential(*blocks))
             self.stage_names.append(name)
             self._out_feature_channels[name], self._out_feature_strides[name] = cout, 4 * 2 ** i
-            cin, cout, mid = cout, 2 * cout, 2 * mid
+            cin, cout, width = cout, 2 * cout, 2 * width
 
     @property
     def size_divisibility(self):
@@ -166,15 +101,12 @@ class ResNet(_Frozen):
     def output_shape(self):
         return {n: ShapeSpec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
 
-    def _own_convs(self):
-        return [m for m in self.modules() if isinstance(m, Conv2d)]
-
     def forward(self, x):
-        self._check_frozen(x)
+        check_forward_only(self, x, self.what)
         with torch.no_grad():
             f = self._prepare()
             out = {}
-            y = ops.resnet_stem(x.float(), *f[id(self.stem.conv1)])
+            y = self.stem.run(x.float(), f)
             if "stem" in self._out_features:
                 out["stem"] = y
             for name in self.stage_names:
@@ -183,6 +115,26 @@ class ResNet(_Frozen):
                 if name in self._out_features:
                     out[name] = y
         return out
+
+
+class ResNet(ResNetBase):
+    """The bottom-up of detectron2's ResNet-50 / -101 (see ResNetBase for the forward)."""
+
+    def __init__(self, depth=50, out_features=("res2", "res3", "res4", "res5"), stride_in_1x1=True, width_per_group=64,
+                 res2_out_channels=256, stem_out_channels=64):
+        super().__init__()
+        if depth not in _BLOCKS:
+            raise AfiError(f"resnet_guide: RESNETS.DEPTH {depth} is not supported (50 or 101)")
+        if stem_out_channels != 64:
+            raise AfiError(f"resnet_guide: RESNETS.STEM_OUT_CHANNELS {stem_out_channels} is not supported (the stem kernel makes 64)")
+        n_stages = self._num_stages("resnet_guide", out_features)
+        if (width_per_group % 4) or (res2_out_channels % 4):
+            raise AfiError("resnet_guide: channel counts must be multiples of 4")
+        self._build(out_features, BasicStem(3, 64), 64, _BLOCKS[depth][:n_stages], res2_out_channels, width_per_group,
+                    lambda stage, cin, cout, width, stride: BottleneckBlock(cin, cout, width, stride, stride_in_1x1))
+
+    def _own_convs(self):
+        return [m for m in self.modules() if isinstance(m, Conv2d)]
 
 
 class LastLevelMaxPool(nn.Module):
@@ -234,56 +186,51 @@ class FPN(_Frozen):
     def _own_convs(self):
         return self.lateral_convs + self.output_convs
 
-    def _prepare(self):
-        f = super()._prepare()
-        if self._fuse_type == "avg" and getattr(self, "_avg_key", None) != self._folded_key:
+    def _fold_own(self, convs):
+        f = super()._fold_own(convs)
+        if self._fuse_type == "avg":
             for m in self.lateral_convs[1:]:                               # (lat + top-down) / 2 = 0.5 conv + 0.5 bias + 0.5 top-down
                 f[("avg", id(m))] = m.fold(scale=0.5)
-            self._avg_key = self._folded_key
         return f
 
     def forward(self, x):
-        self._check_frozen(x)
+        check_forward_only(self, x, self.what)
         feats = self.bottom_up(x)
         with torch.no_grad():
             f = self._prepare()
             xs = [feats[k] for k in self.in_features[::-1]]
-            prev = _conv1x1(xs[0], f[id(self.lateral_convs[0])])
-            results = [_conv3x3(prev, f[id(self.output_convs[0])])]
+            prev = conv1x1(xs[0], f[id(self.lateral_convs[0])])
+            results = [conv3x3(prev, f[id(self.output_convs[0])])]
             for feat, lat, out in zip(xs[1:], self.lateral_convs[1:], self.output_convs[1:]):
                 td = ops.nearest(prev, up=2)
                 if self._fuse_type == "avg":
-                    prev = _conv1x1(feat, f[("avg", id(lat))], add=td, alpha=0.5, add_scale=0.5)
+                    prev = conv1x1(feat, f[("avg", id(lat))], add=td, alpha=0.5, add_scale=0.5)
                 else:
-                    prev = _conv1x1(feat, f[id(lat)], add=td)
-                results.insert(0, _conv3x3(prev, f[id(out)]))
+                    prev = conv1x1(feat, f[id(lat)], add=td)
+                results.insert(0, conv3x3(prev, f[id(out)]))
             results.append(ops.nearest(results[-1], up=1, down=2))          # LastLevelMaxPool on the coarsest output
         return dict(zip(self._out_features, results))
 
 
-def _get(node, key, default):
-    return getattr(node, key, default) if node is not None else default
-
-
 def _resnet_from_cfg(cfg, input_shape=None):
     """detectron2's build_resnet_backbone restricted to the frozen, forward-only guide: refuses every option it does not implement."""
-    r = _get(cfg.MODEL, "RESNETS", None)
+    r = cfg_get(cfg.MODEL, "RESNETS", None)
     if input_shape is not None and getattr(input_shape, "channels", 3) not in (None, 3):
         raise AfiError(f"resnet_guide: 3 input channels only, got {input_shape.channels}")
-    norm = _get(r, "NORM", "FrozenBN")
+    norm = cfg_get(r, "NORM", "FrozenBN")
     if norm != "FrozenBN":
         raise AfiError(f"resnet_guide: RESNETS.NORM {norm!r} is not supported (the frozen guide folds FrozenBN)")
-    if _get(r, "NUM_GROUPS", 1) != 1:
-        raise AfiError(f"resnet_guide: RESNETS.NUM_GROUPS {_get(r, 'NUM_GROUPS', 1)} is not supported (groups = 1 only)")
-    if _get(r, "RES5_DILATION", 1) != 1:
-        raise AfiError(f"resnet_guide: RESNETS.RES5_DILATION {_get(r, 'RES5_DILATION', 1)} is not supported (no dilation)")
-    if any(_get(r, "DEFORM_ON_PER_STAGE", [False] * 4)):
+    if cfg_get(r, "NUM_GROUPS", 1) != 1:
+        raise AfiError(f"resnet_guide: RESNETS.NUM_GROUPS {cfg_get(r, 'NUM_GROUPS', 1)} is not supported (groups = 1 only)")
+    if cfg_get(r, "RES5_DILATION", 1) != 1:
+        raise AfiError(f"resnet_guide: RESNETS.RES5_DILATION {cfg_get(r, 'RES5_DILATION', 1)} is not supported (no dilation)")
+    if any(cfg_get(r, "DEFORM_ON_PER_STAGE", [False] * 4)):
         raise AfiError("resnet_guide: deformable convolutions (RESNETS.DEFORM_ON_PER_STAGE) are not supported")
-    if _get(r, "RADIX", 1) != 1 or _get(r, "DEEP_STEM", False) or _get(r, "AVD", False) or _get(r, "AVG_DOWN", False):
+    if cfg_get(r, "RADIX", 1) != 1 or cfg_get(r, "DEEP_STEM", False) or cfg_get(r, "AVD", False) or cfg_get(r, "AVG_DOWN", False):
         raise AfiError("resnet_guide: the ResNeSt options (RESNETS.RADIX / DEEP_STEM / AVD / AVG_DOWN) are not supported")
-    return ResNet(depth=_get(r, "DEPTH", 50), out_features=list(_get(r, "OUT_FEATURES", ["res4"])),
-                  stride_in_1x1=bool(_get(r, "STRIDE_IN_1X1", True)), width_per_group=_get(r, "WIDTH_PER_GROUP", 64),
-                  res2_out_channels=_get(r, "RES2_OUT_CHANNELS", 256), stem_out_channels=_get(r, "STEM_OUT_CHANNELS", 64))
+    return ResNet(depth=cfg_get(r, "DEPTH", 50), out_features=list(cfg_get(r, "OUT_FEATURES", ["res4"])),
+                  stride_in_1x1=bool(cfg_get(r, "STRIDE_IN_1X1", True)), width_per_group=cfg_get(r, "WIDTH_PER_GROUP", 64),
+                  res2_out_channels=cfg_get(r, "RES2_OUT_CHANNELS", 256), stem_out_channels=cfg_get(r, "STEM_OUT_CHANNELS", 64))
 
 
 def build_resnet_backbone(cfg, input_shape=None):
@@ -293,11 +240,11 @@ def build_resnet_backbone(cfg, input_shape=None):
 
 def build_resnet_fpn_backbone(cfg, input_shape=None):
     """detectron2's build_resnet_fpn_backbone (ResNet + FPN + LastLevelMaxPool) as the frozen guide of stages 1 and 2."""
-    fpn = _get(cfg.MODEL, "FPN", None)
-    if _get(fpn, "NORM", "") != "":
-        raise AfiError(f"resnet_guide: FPN.NORM {_get(fpn, 'NORM', '')!r} is not supported (the guide's FPN has biased convs, no norm)")
-    return FPN(_resnet_from_cfg(cfg, input_shape), list(_get(fpn, "IN_FEATURES", ["res2", "res3", "res4", "res5"])),
-               _get(fpn, "OUT_CHANNELS", 256), _get(fpn, "FUSE_TYPE", "sum"))
+    fpn = cfg_get(cfg.MODEL, "FPN", None)
+    if cfg_get(fpn, "NORM", "") != "":
+        raise AfiError(f"resnet_guide: FPN.NORM {cfg_get(fpn, 'NORM', '')!r} is not supported (the guide's FPN has biased convs, no norm)")
+    return FPN(_resnet_from_cfg(cfg, input_shape), list(cfg_get(fpn, "IN_FEATURES", ["res2", "res3", "res4", "res5"])),
+               cfg_get(fpn, "OUT_CHANNELS", 256), cfg_get(fpn, "FUSE_TYPE", "sum"))
 
 
 def use_as_bottom_up():
@@ -305,13 +252,4 @@ def use_as_bottom_up():
     registry.set_bottom_up_builder("resnet", build_resnet_backbone)
 
 
-def _register():
-    """``build_resnet_fpn_backbone`` in the LOCAL registry only: with detectron2 installed the name is detectron2's."""
-    if registry.USING_DETECTRON2_REGISTRY:
-        return False
-    if "build_resnet_fpn_backbone" not in registry.BACKBONE_REGISTRY:
-        registry.BACKBONE_REGISTRY.register(build_resnet_fpn_backbone)
-    return True
-
-
-REGISTERED = _register()
+REGISTERED = registry.register_local_backbone(build_resnet_fpn_backbone)        # (with detectron2 installed the name is detectron2's)

@@ -22,7 +22,7 @@ Keys: ``box_head.fc{i}.{weight, bias}``, ``box_predictor.{cls_score, bbox_pred}.
 
 Kernels: afi_roi_align; the FCs and the predictor are afi_conv1x1_fwd over the R = N P rows as pixels (fc1 reads the pooled [R][S][S][C]
 memory in place, its weight permuted once from [out][C][S][S] to [out][S][S][C]; cls_score and bbox_pred are ONE weight, zero-padded to a
-multiple of 4; both rebuilt when a parameter changes: version, storage, device); afi_roi_scores_boxes, afi_roi_candidates, afi_roi_nms,
+multiple of 4; both rebuilt when a parameter changes: frozen.prepared); afi_roi_scores_boxes, afi_roi_candidates, afi_roi_nms,
 afi_roi_pick (csrc/roi.hip).  No torch mm / addmm / softmax / sort / topk, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host
 read and can be captured in a hipGraph; ``forward`` reads ``counts`` and ``truncated`` once."""
 import math
@@ -32,31 +32,18 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import AfiError
-from .registry import Registry
-from .resnet_guide import _get
+from .frozen import cfg_get, check_feature, prepared
+from .registry import detectron2_or_local
 from .rpn import SCALE_CLAMP, Boxes
 
 ROI_MAX_CANDIDATES = ops.ROI_MAX_CANDIDATES
 
 
-def _d2_registry():
-    try:
-        from detectron2.modeling.roi_heads import ROI_HEADS_REGISTRY as reg
-        return reg
-    except Exception:
-        return None
-
-
-_D2 = _d2_registry()
-# detectron2's own "StandardROIHeads" owns the name there: its registry is used only when the name is free
-ROI_HEADS_REGISTRY = _D2 if _D2 is not None and "StandardROIHeads" not in _D2 else Registry("ROI_HEADS")
+ROI_HEADS_REGISTRY = detectron2_or_local("detectron2.modeling.roi_heads", "ROI_HEADS_REGISTRY", "StandardROIHeads", "ROI_HEADS")
 
 
 def _check_feature(where, name, x):
-    if not getattr(x, "is_cuda", False):
-        raise AfiError(f"{where}: {name} is a CPU tensor; the ROI heads run on the GPU only, there is no CPU fallback")
-    if x.dtype != torch.float32:
-        raise AfiError(f"{where}: {name} is {x.dtype}; fp32 only (2-byte activations stop at the AFI backbone's boundary)")
+    check_feature(where, name, x, "the ROI heads run")
 
 
 class ROIPooler(nn.Module):
@@ -171,16 +158,16 @@ class StandardROIHeads(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
         m = cfg.MODEL
-        rh, bh = _get(m, "ROI_HEADS", None), _get(m, "ROI_BOX_HEAD", None)
+        rh, bh = cfg_get(m, "ROI_HEADS", None), cfg_get(m, "ROI_BOX_HEAD", None)
         if rh is None or bh is None:
             raise AfiError("roi_heads: the config has no MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD section (afigan_amd.config.get_cfg declares them)")
-        if _get(rh, "NAME", "StandardROIHeads") != "StandardROIHeads":
+        if cfg_get(rh, "NAME", "StandardROIHeads") != "StandardROIHeads":
             raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {rh.NAME!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
-        if _get(m, "MASK_ON", False):
+        if cfg_get(m, "MASK_ON", False):
             raise AfiError("roi_heads: MODEL.MASK_ON is set -- box branch only; set MODEL.MASK_ON False")
-        if _get(m, "KEYPOINT_ON", False):
+        if cfg_get(m, "KEYPOINT_ON", False):
             raise AfiError("roi_heads: MODEL.KEYPOINT_ON is set -- box branch only; set MODEL.KEYPOINT_ON False")
-        if _get(bh, "NAME", "FastRCNNConvFCHead") != "FastRCNNConvFCHead":
+        if cfg_get(bh, "NAME", "FastRCNNConvFCHead") != "FastRCNNConvFCHead":
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NAME {bh.NAME!r} is not supported (FastRCNNConvFCHead only)")
         self.in_features = list(rh.IN_FEATURES)
         missing = [f for f in self.in_features if f not in input_shape]
@@ -193,24 +180,24 @@ class StandardROIHeads(nn.Module):
         C_ = channels.pop()
         if C_ % 4:
             raise AfiError(f"roi_heads: {C_} feature channels; a multiple of 4 is needed")
-        self.num_classes = int(_get(rh, "NUM_CLASSES", 80))
+        self.num_classes = int(cfg_get(rh, "NUM_CLASSES", 80))
         if not 0 < self.num_classes <= ops.ROI_MAX_CLASSES:
             raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NUM_CLASSES {self.num_classes} is outside 1..{ops.ROI_MAX_CLASSES}")
-        self.test_score_thresh = float(_get(rh, "SCORE_THRESH_TEST", 0.05))
-        self.test_nms_thresh = float(_get(rh, "NMS_THRESH_TEST", 0.5))
-        self.test_detections_per_img = int(_get(_get(cfg, "TEST", None), "DETECTIONS_PER_IMAGE", 100))
+        self.test_score_thresh = float(cfg_get(rh, "SCORE_THRESH_TEST", 0.05))
+        self.test_nms_thresh = float(cfg_get(rh, "NMS_THRESH_TEST", 0.5))
+        self.test_detections_per_img = int(cfg_get(cfg_get(cfg, "TEST", None), "DETECTIONS_PER_IMAGE", 100))
         if not 0 < self.test_detections_per_img <= ROI_MAX_CANDIDATES:
             raise AfiError(f"roi_heads: TEST.DETECTIONS_PER_IMAGE {self.test_detections_per_img} is outside 1..{ROI_MAX_CANDIDATES}, the candidate "
                            "list the selection kernels hold")
-        self.box_weights = tuple(float(w) for w in _get(bh, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0)))
+        self.box_weights = tuple(float(w) for w in cfg_get(bh, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0)))
         if len(self.box_weights) != 4 or min(self.box_weights) <= 0:
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS {self.box_weights} must be four positive numbers")
-        res = _get(bh, "POOLER_RESOLUTION", 14)
-        self.box_pooler = ROIPooler(res, [1.0 / s.stride for s in shapes], _get(bh, "POOLER_SAMPLING_RATIO", 0), _get(bh, "POOLER_TYPE", "ROIAlignV2"))
+        res = cfg_get(bh, "POOLER_RESOLUTION", 14)
+        self.box_pooler = ROIPooler(res, [1.0 / s.stride for s in shapes], cfg_get(bh, "POOLER_SAMPLING_RATIO", 0), cfg_get(bh, "POOLER_TYPE", "ROIAlignV2"))
         S = self.box_pooler.output_size
-        self.box_head = FastRCNNConvFCHead((C_, S, S), int(_get(bh, "NUM_FC", 0)), int(_get(bh, "FC_DIM", 1024)), int(_get(bh, "NUM_CONV", 0)),
-                                           _get(bh, "NORM", ""))
-        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes, bool(_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
+        self.box_head = FastRCNNConvFCHead((C_, S, S), int(cfg_get(bh, "NUM_FC", 0)), int(cfg_get(bh, "FC_DIM", 1024)), int(cfg_get(bh, "NUM_CONV", 0)),
+                                           cfg_get(bh, "NORM", ""))
+        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes, bool(cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
         self.mask_on = self.keypoint_on = False
         for p in self.parameters():
             p.requires_grad_(False)
@@ -221,8 +208,8 @@ class StandardROIHeads(nn.Module):
         changes."""
         fc1, pr = self.box_head.fcs[0], self.box_predictor
         ts = [fc1.weight, pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias]
-        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
-        if getattr(self, "_prep_key", None) != key:
+
+        def build():
             C_, S, _ = self.box_head.input_shape
             out = fc1.weight.shape[0]
             w1 = fc1.weight.detach().float().view(out, C_, S, S).permute(0, 2, 3, 1).reshape(out, S * S * C_).contiguous()
@@ -232,8 +219,8 @@ class StandardROIHeads(nn.Module):
             b = torch.zeros((cpad,), device=ts[0].device, dtype=torch.float32)
             w[:nc], w[nc:nc + nb] = ts[1].detach(), ts[3].detach()
             b[:nc], b[nc:nc + nb] = ts[2].detach(), ts[4].detach()
-            self._prep, self._prep_key = (w1, w, b), key
-        return self._prep
+            return w1, w, b
+        return prepared(self, "prep", ts, build)
 
     # ------------------------------------------------------------------ checks
     def _check(self, features, boxes=None, counts=None):
@@ -350,7 +337,7 @@ class StandardROIHeads(nn.Module):
 
 def build_roi_heads(cfg, input_shape):
     """detectron2's build_roi_heads: the class registered under MODEL.ROI_HEADS.NAME."""
-    name = _get(_get(cfg.MODEL, "ROI_HEADS", None), "NAME", "StandardROIHeads")
+    name = cfg_get(cfg_get(cfg.MODEL, "ROI_HEADS", None), "NAME", "StandardROIHeads")
     if name != "StandardROIHeads":
         raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (this package provides the box branch of 'StandardROIHeads')")
     return ROI_HEADS_REGISTRY.get(name)(cfg, input_shape)

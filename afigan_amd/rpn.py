@@ -15,9 +15,9 @@ then the survivors of all levels by logit (ties: level, then rank), the first PO
 Keys: ``rpn_head.{conv, objectness_logits, anchor_deltas}.{weight, bias}`` and the buffers ``anchor_generator.cell_anchors.{l}`` [A, 4] --
 detectron2's, so a detector checkpoint's ``proposal_generator.*`` loads with strict=True.  Every parameter has requires_grad False.
 
-Kernels: the 3x3 conv + ReLU is afi_conv3x3_wino_infer / afi_conv3x3_fwd (the regime rule of resnet_guide), the two 1x1 convs ONE
-afi_conv1x1_fwd over their concatenated weights (A + 4A channels, zero-padded to a multiple of 4; rebuilt when a parameter changes: version,
-storage, device); selection afi_rpn_topk, afi_rpn_decode, afi_rpn_nms per level and one afi_rpn_merge (csrc/rpn.hip).  No torch sort / topk /
+Kernels: the 3x3 conv + ReLU is afi_conv3x3_wino_infer / afi_conv3x3_fwd (the regime rule of frozen.conv3x3), the two 1x1 convs ONE
+afi_conv1x1_fwd over their concatenated weights (A + 4A channels, zero-padded to a multiple of 4; rebuilt when a parameter changes:
+frozen.prepared); selection afi_rpn_topk, afi_rpn_decode, afi_rpn_nms per level and one afi_rpn_merge (csrc/rpn.hip).  No torch sort / topk /
 conv, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host read and can be captured in a hipGraph; ``forward`` reads ``counts`` once.
 
 Out of scope (AfiError): losses, label assignment and training (``gt_instances``, a training-mode call with gradients enabled), rotated
@@ -30,23 +30,14 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import AfiError
-from .registry import Registry
-from .resnet_guide import _conv3x3, _get
+from .frozen import cfg_get, check_feature, conv3x3, prepared
+from .registry import detectron2_or_local
 
 SCALE_CLAMP = math.log(1000.0 / 16)                    # Box2BoxTransform's _DEFAULT_SCALE_CLAMP
 
 
-def _d2_registry():
-    try:
-        from detectron2.modeling.proposal_generator import PROPOSAL_GENERATOR_REGISTRY as reg
-        return reg
-    except Exception:
-        return None
-
-
-_D2 = _d2_registry()
-# detectron2's own "RPN" owns the name there: its registry is used only when the name is free
-PROPOSAL_GENERATOR_REGISTRY = _D2 if _D2 is not None and "RPN" not in _D2 else Registry("PROPOSAL_GENERATOR")
+PROPOSAL_GENERATOR_REGISTRY = detectron2_or_local("detectron2.modeling.proposal_generator", "PROPOSAL_GENERATOR_REGISTRY", "RPN",
+                                                  "PROPOSAL_GENERATOR")
 
 
 def generate_cell_anchors(sizes, aspect_ratios):
@@ -154,12 +145,12 @@ class RPN(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
         m = cfg.MODEL
-        ag, r, pg = _get(m, "ANCHOR_GENERATOR", None), _get(m, "RPN", None), _get(m, "PROPOSAL_GENERATOR", None)
+        ag, r, pg = cfg_get(m, "ANCHOR_GENERATOR", None), cfg_get(m, "RPN", None), cfg_get(m, "PROPOSAL_GENERATOR", None)
         if r is None or ag is None:
             raise AfiError("rpn: the config has no MODEL.RPN / MODEL.ANCHOR_GENERATOR section (afigan_amd.config.get_cfg declares them)")
-        if _get(ag, "NAME", "DefaultAnchorGenerator") != "DefaultAnchorGenerator":
+        if cfg_get(ag, "NAME", "DefaultAnchorGenerator") != "DefaultAnchorGenerator":
             raise AfiError(f"rpn: MODEL.ANCHOR_GENERATOR.NAME {ag.NAME!r} is not supported (DefaultAnchorGenerator only: rotated anchors are out of scope)")
-        if _get(r, "HEAD_NAME", "StandardRPNHead") != "StandardRPNHead":
+        if cfg_get(r, "HEAD_NAME", "StandardRPNHead") != "StandardRPNHead":
             raise AfiError(f"rpn: MODEL.RPN.HEAD_NAME {r.HEAD_NAME!r} is not supported (StandardRPNHead only)")
         self.in_features = list(r.IN_FEATURES)
         missing = [f for f in self.in_features if f not in input_shape]
@@ -167,24 +158,24 @@ class RPN(nn.Module):
             raise AfiError(f"rpn: MODEL.RPN.IN_FEATURES {self.in_features} are not all outputs of the backbone ({sorted(input_shape)})")
         if len(self.in_features) > ops.RPN_MAX_LEVELS:
             raise AfiError(f"rpn: at most {ops.RPN_MAX_LEVELS} input features, got {len(self.in_features)}")
-        self.pre_nms_topk = int(_get(r, "PRE_NMS_TOPK_TEST", 6000))
+        self.pre_nms_topk = int(cfg_get(r, "PRE_NMS_TOPK_TEST", 6000))
         if not 0 < self.pre_nms_topk <= ops.RPN_MAX_TOPK:
             raise AfiError(f"rpn: MODEL.RPN.PRE_NMS_TOPK_TEST {self.pre_nms_topk} is outside 1..{ops.RPN_MAX_TOPK}, the per-level list the selection "
                            f"kernels hold (detectron2's default of 6000 is above it; every reference config sets 1000)")
-        self.post_nms_topk = int(_get(r, "POST_NMS_TOPK_TEST", 1000))
+        self.post_nms_topk = int(cfg_get(r, "POST_NMS_TOPK_TEST", 1000))
         if self.post_nms_topk <= 0:
             raise AfiError(f"rpn: MODEL.RPN.POST_NMS_TOPK_TEST {self.post_nms_topk} must be positive")
-        self.nms_thresh = float(_get(r, "NMS_THRESH", 0.7))
-        self.min_box_side_len = float(_get(pg, "MIN_SIZE", 0))
-        self.box_weights = tuple(float(w) for w in _get(r, "BBOX_REG_WEIGHTS", (1.0, 1.0, 1.0, 1.0)))
+        self.nms_thresh = float(cfg_get(r, "NMS_THRESH", 0.7))
+        self.min_box_side_len = float(cfg_get(pg, "MIN_SIZE", 0))
+        self.box_weights = tuple(float(w) for w in cfg_get(r, "BBOX_REG_WEIGHTS", (1.0, 1.0, 1.0, 1.0)))
         if len(self.box_weights) != 4 or min(self.box_weights) <= 0:
             raise AfiError(f"rpn: MODEL.RPN.BBOX_REG_WEIGHTS {self.box_weights} must be four positive numbers")
         shapes = [input_shape[f] for f in self.in_features]
         channels = {s.channels for s in shapes}
         if len(channels) != 1:
             raise AfiError(f"rpn: every input feature must have one channel count, got {sorted(channels)}")
-        self.anchor_generator = DefaultAnchorGenerator(_get(ag, "SIZES", [[32, 64, 128, 256, 512]]), _get(ag, "ASPECT_RATIOS", [[0.5, 1.0, 2.0]]),
-                                                       [s.stride for s in shapes], _get(ag, "OFFSET", 0.0))
+        self.anchor_generator = DefaultAnchorGenerator(cfg_get(ag, "SIZES", [[32, 64, 128, 256, 512]]), cfg_get(ag, "ASPECT_RATIOS", [[0.5, 1.0, 2.0]]),
+                                                       [s.stride for s in shapes], cfg_get(ag, "OFFSET", 0.0))
         na = set(self.anchor_generator.num_cell_anchors)
         if len(na) != 1:
             raise AfiError(f"rpn: every level must have the same number of cell anchors, got {self.anchor_generator.num_cell_anchors}")
@@ -201,17 +192,16 @@ class RPN(nn.Module):
         layout, rebuilt when a parameter changes."""
         h = self.rpn_head
         ts = [h.objectness_logits.weight, h.objectness_logits.bias, h.anchor_deltas.weight, h.anchor_deltas.bias, h.conv.weight, h.conv.bias]
-        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
-        if getattr(self, "_cat_key", None) != key:
+
+        def build():
             A, C_ = self.num_anchors, h.conv.weight.shape[0]
             cpad = (5 * A + 3) // 4 * 4
             w = torch.zeros((cpad, C_), device=ts[0].device, dtype=torch.float32)
             b = torch.zeros((cpad,), device=ts[0].device, dtype=torch.float32)
             w[:A], w[A:5 * A] = ts[0].detach().reshape(A, C_), ts[2].detach().reshape(4 * A, C_)
             b[:A], b[A:5 * A] = ts[1].detach(), ts[3].detach()
-            w3 = ts[4].detach().float().permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)       # [O][kh][kw][I] memory: what the conv kernels read
-            self._cat, self._cat_key = (w, b, w3, ts[5].detach().float().contiguous()), key
-        return self._cat
+            return w, b, ops.to_ohwi(ts[4].detach().float()), ts[5].detach().float().contiguous()
+        return prepared(self, "cat", ts, build)
 
     def _check(self, features):
         if self.training and torch.is_grad_enabled():
@@ -222,10 +212,7 @@ class RPN(nn.Module):
             raise AfiError(f"rpn: features {missing} are missing (got {sorted(features)})")
         xs = [features[f] for f in self.in_features]
         for f, x in zip(self.in_features, xs):
-            if not x.is_cuda:
-                raise AfiError(f"rpn: feature {f} is a CPU tensor; the proposal generator runs on the GPU only, there is no CPU fallback")
-            if x.dtype != torch.float32:
-                raise AfiError(f"rpn: feature {f} is {x.dtype}; fp32 features only (2-byte activations stop at the AFI backbone's boundary)")
+            check_feature("rpn", f"feature {f}", x, "the proposal generator runs", "fp32 features only")
             if x.dim() != 4 or x.shape[1] != self.rpn_head.conv.weight.shape[1] or x.shape[0] != xs[0].shape[0]:
                 raise AfiError(f"rpn: feature {f} has shape {tuple(x.shape)}; [N, {self.rpn_head.conv.weight.shape[1]}, H, W] expected")
             if torch.is_grad_enabled() and x.requires_grad:
@@ -239,7 +226,7 @@ class RPN(nn.Module):
             wcat, bcat, w3, b3 = self._prepare()
             outs = []
             for x in xs:
-                t = _conv3x3(ops.pixel_major(x), (w3, b3), relu=True)
+                t = conv3x3(ops.pixel_major(x), (w3, b3), relu=True)
                 outs.append(ops.conv1x1_fwd(t, wcat, bcat))
         return outs
 
@@ -297,7 +284,7 @@ class RPN(nn.Module):
 
 def build_proposal_generator(cfg, input_shape):
     """detectron2's build_proposal_generator: None for precomputed proposals, else the registered class."""
-    name = _get(_get(cfg.MODEL, "PROPOSAL_GENERATOR", None), "NAME", "RPN")
+    name = cfg_get(cfg_get(cfg.MODEL, "PROPOSAL_GENERATOR", None), "NAME", "RPN")
     if name == "PrecomputedProposals":
         return None
     try:

@@ -22,7 +22,7 @@ attention kernel synthesises padded tokens from the qkv bias itself); the merge 
 attention afi_swin_window_attn (fp32 MFMA); GELU afi_swin_gelu; qkv, proj (+ residual), fc1, fc2 (+ residual) and the reduction
 afi_conv1x1_fwd over pixel-major tokens.  No torch matmul / softmax / layer_norm, MIOpen or hipBLASLt kernel runs in the forward, and no
 atomics: it is bit-identical from run to run and under hipGraph replay.  The dense relative-position bias images are rebuilt from the table
-and the index buffer whenever a parameter or buffer changes (version, storage, device), like resnet_guide's folded weights.
+and the index buffer whenever a parameter or buffer changes (frozen.prepared: version, storage, device).
 
 Out of scope (AfiError at build time): APE, head dims other than 32, windows other than 7 and 12, EMBED_DIM above 192 (the kernels' widths),
 input channels other than 3; at call time, a CPU tensor and a forward that autograd could differentiate.  DROP_PATH_RATE and
@@ -33,7 +33,7 @@ import torch.nn as nn
 from . import ops, registry
 from ._lib import AfiError
 from .fpn_sr import ShapeSpec
-from .resnet_guide import _get
+from .frozen import cfg_get, check_forward_only, prepared
 
 HEAD_DIM = 32
 MAX_EMBED_DIM = 192         # patch embed <= 256 channels; the last merge's LayerNorm 16 EMBED_DIM <= 3072 channels
@@ -176,18 +176,11 @@ class SwinTransformer(nn.Module):
 
     def _prepare(self):
         """The dense relative-position bias image of every block, rebuilt when a parameter / buffer changes (version, storage, device)."""
-        ts = list(self.parameters()) + list(self.buffers())
-        key = tuple((t._version, t.data_ptr(), str(t.device)) for t in ts)
-        if getattr(self, "_prepared_key", None) != key:
-            self._prepared = {id(b): b.attn.bias_image() for b in self._blocks()}
-            self._prepared_key = key
-        return self._prepared
+        return prepared(self, "bias_images", list(self.parameters()) + list(self.buffers()),
+                        lambda: {id(b): b.attn.bias_image() for b in self._blocks()})
 
     def _check_frozen(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise AfiError("the Swin bottom-up is forward-only (frozen): run it under torch.no_grad() with no parameter or input requiring grad")
-        if not x.is_cuda:
-            raise AfiError("the Swin bottom-up runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+        check_forward_only(self, x, "the Swin bottom-up")
         if x.dim() != 4 or x.shape[1] != 3:
             raise AfiError(f"the Swin bottom-up takes [N, 3, H, W] images, got {tuple(x.shape)}")
 
@@ -215,15 +208,15 @@ class SwinTransformer(nn.Module):
 def build_swint_backbone(cfg, input_shape=None):
     """swin_transformer.py's build_swint_backbone restricted to the frozen, forward-only module: refuses every option it does not implement.
     For ``registry.set_bottom_up_builder("swint", build_swint_backbone)`` (opt-in: use_as_bottom_up)."""
-    s = _get(cfg.MODEL, "SWINT", None)
+    s = cfg_get(cfg.MODEL, "SWINT", None)
     if input_shape is not None and getattr(input_shape, "channels", 3) not in (None, 3):
         raise AfiError(f"swin_backbone: 3 input channels only, got {input_shape.channels}")
-    if _get(s, "APE", False):
+    if cfg_get(s, "APE", False):
         raise AfiError("swin_backbone: SWINT.APE True (absolute position embedding) is not supported")
-    return SwinTransformer(embed_dim=_get(s, "EMBED_DIM", 96), depths=list(_get(s, "DEPTHS", [2, 2, 6, 2])),
-                           num_heads=list(_get(s, "NUM_HEADS", [3, 6, 12, 24])), window_size=_get(s, "WINDOW_SIZE", 7),
-                           mlp_ratio=float(_get(s, "MLP_RATIO", 4.0)),
-                           out_features=list(_get(s, "OUT_FEATURES", ["stage2", "stage3", "stage4", "stage5"])))
+    return SwinTransformer(embed_dim=cfg_get(s, "EMBED_DIM", 96), depths=list(cfg_get(s, "DEPTHS", [2, 2, 6, 2])),
+                           num_heads=list(cfg_get(s, "NUM_HEADS", [3, 6, 12, 24])), window_size=cfg_get(s, "WINDOW_SIZE", 7),
+                           mlp_ratio=float(cfg_get(s, "MLP_RATIO", 4.0)),
+                           out_features=list(cfg_get(s, "OUT_FEATURES", ["stage2", "stage3", "stage4", "stage5"])))
 
 
 def use_as_bottom_up():
