@@ -1075,6 +1075,59 @@ def roi_pick(cand, keep, D):
     return ob, os_, oc, counts, trunc
 
 
+# ------------------------------------------------------------------------------------------------ ROI heads, mask branch (roi_heads.py)
+MASK_MAX_SIDE = 64                          # M: the mask afi_mask_paste holds in LDS
+
+
+def roi_mask_probs(h, w, bias, classes, counts, out=None):
+    """The class-selected mask predictor and sigmoid on the deconv's 4-phase output: h pixel-major [N D, 4 C, S, S] dense (memory
+    [R][S][S][4][C], phase 2a + b of input pixel (y, x) = output pixel (2y + a, 2x + b)), w [Km, C] (or [Km, C, 1, 1]), bias [Km], classes
+    [N, D] int32, counts [N] int32; returns probs [N D, 2S, 2S], rows past counts (and rows with a class outside 0..Km-1) zero
+    (afi_roi_mask_probs)."""
+    _check_cuda(h, w, bias, out)
+    _check_i32(classes, counts)
+    if classes.dim() != 2 or counts.dim() != 1 or counts.shape[0] != classes.shape[0] or not classes.is_contiguous() or not counts.is_contiguous():
+        raise _lib.AfiError(f"roi_mask_probs: dense classes [N, D] and counts [N] expected, got {tuple(classes.shape)} and {tuple(counts.shape)}")
+    N, D = classes.shape
+    Km = w.shape[0]
+    w2 = w.reshape(Km, -1).contiguous()
+    C_ = w2.shape[1]
+    if h.dim() != 4 or h.shape[0] != N * D or h.shape[1] != 4 * C_ or h.shape[2] != h.shape[3] or not is_dense_pm(h) or C_ % 4 \
+            or tuple(bias.shape) != (Km,) or not bias.is_contiguous():
+        raise _lib.AfiError(f"roi_mask_probs: a dense pixel-major h [{N * D}, 4 C, S, S] with C = {C_} (a multiple of 4) and a bias [{Km}] "
+                            f"expected, got {tuple(h.shape)} and {tuple(bias.shape)}")
+    S = h.shape[2]
+    if not 0 < S <= ROI_MAX_POOLED:
+        raise _lib.AfiError(f"roi_mask_probs: pooled size {S} (1..{ROI_MAX_POOLED})")
+    if out is None:
+        out = torch.empty((N * D, 2 * S, 2 * S), device=h.device, dtype=torch.float32)
+    elif tuple(out.shape) != (N * D, 2 * S, 2 * S) or not out.is_contiguous():
+        raise _lib.AfiError(f"roi_mask_probs: out must be a dense [{N * D}, {2 * S}, {2 * S}] tensor")
+    call("afi_roi_mask_probs", _p(h), _p(w2), _p(bias), _p(classes), _p(counts), N, D, C_, S, Km, _p(out), stream_ptr())
+    return out
+
+
+def mask_paste(probs, boxes, hw, threshold=0.5, out=None):
+    """detectron2's paste_masks_in_image: probs [R, M, M] pasted into boxes [R, 4] (x0, y0, x1, y1) of an image of hw = (H, W), compared with
+    ``>= threshold``: bool [R, H, W].  Pixels whose centre is outside their box are False; a box with a non-positive side gives all False
+    (afi_mask_paste).  out: a uint8 or bool [R, H, W] buffer."""
+    _check_cuda(probs, boxes)
+    H, W = int(hw[0]), int(hw[1])
+    if probs.dim() != 3 or probs.shape[1] != probs.shape[2] or tuple(boxes.shape) != (probs.shape[0], 4) or H <= 0 or W <= 0:
+        raise _lib.AfiError(f"mask_paste: probs [R, M, M], boxes [R, 4] and a positive output size expected, got {tuple(probs.shape)}, "
+                            f"{tuple(boxes.shape)}, {(H, W)}")
+    R, M = probs.shape[:2]
+    if not 0 < M <= MASK_MAX_SIDE:
+        raise _lib.AfiError(f"mask_paste: mask side {M} (1..{MASK_MAX_SIDE})")
+    if out is None:
+        out = torch.empty((R, H, W), device=probs.device, dtype=torch.uint8)
+    elif not out.is_cuda or out.dtype not in (torch.uint8, torch.bool) or tuple(out.shape) != (R, H, W) or not out.is_contiguous():
+        raise _lib.AfiError(f"mask_paste: out must be a dense uint8 / bool [{R}, {H}, {W}] tensor on the GPU")
+    if R:
+        call("afi_mask_paste", _p(probs.contiguous()), _p(boxes.contiguous()), R, M, H, W, float(threshold), _p(out), stream_ptr())
+    return out.view(torch.bool)
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

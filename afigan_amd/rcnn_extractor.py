@@ -4,7 +4,8 @@
 The backbone is the AFI pyramid of this package (FPN_AFIGAN / PAFPN_AFIGAN through BACKBONE_REGISTRY); the proposal generator is
 detectron2's when it is importable and this package's frozen, inference-only ``rpn.RPN`` otherwise; the ROI heads are built from a config
 by detectron2 when it is importable, and the constructor takes any callables with their contracts otherwise: ``roi_heads=`` this package's
-frozen box branch (``afigan_amd.build_roi_heads(cfg, backbone.output_shape())``, roi_heads.py), or a stand-in."""
+frozen box branch (``afigan_amd.build_roi_heads(cfg, backbone.output_shape())``, roi_heads.py; ``masks=True`` adds the mask branch, whose
+``pred_masks`` the postprocess pastes into image-size bool masks), or a stand-in."""
 import torch
 import torch.nn as nn
 
@@ -117,8 +118,9 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
     def _postprocess(instances, batched_inputs, image_sizes):
         """rcnn_extractor.py:129-143: ``detector_postprocess(results, height, width)`` per image.  detectron2's own function when it is
         importable; otherwise its box part (scale by output / network size, clip, drop empty boxes: detectron2 v0.1.1
-        modeling/postprocessing.py) on anything that carries ``image_size`` and ``pred_boxes`` -- and a loud error for instance fields this
-        package cannot rescale without detectron2 (masks, keypoints) rather than a silently wrong scale."""
+        modeling/postprocessing.py) on anything that carries ``image_size`` and ``pred_boxes``, then ``pred_masks`` pasted at the output
+        size into the scaled boxes (roi_heads.paste_masks_in_image, GPU only) -- and a loud error for the instance field this package cannot
+        rescale without detectron2 (keypoints) rather than a silently wrong scale."""
         try:
             from detectron2.modeling.postprocessing import detector_postprocess
         except Exception:
@@ -134,10 +136,13 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
 def _detector_postprocess_boxes(results, output_height, output_width):
     import copy
     from ._lib import AfiError
-    for f in ("pred_masks", "pred_keypoints"):
-        if getattr(results, f, None) is not None:
-            raise AfiError(f"rescaling `{f}` to the input size needs detectron2's detector_postprocess (not importable here); "
-                           "call inference(..., do_postprocess=False) for raw ROI-head results")
+    if getattr(results, "pred_keypoints", None) is not None:
+        raise AfiError("rescaling `pred_keypoints` to the input size needs detectron2's detector_postprocess (not importable here); "
+                       "call inference(..., do_postprocess=False) for raw ROI-head results")
+    masks = getattr(results, "pred_masks", None)
+    if masks is not None and not getattr(masks, "is_cuda", False):
+        raise AfiError("pasting `pred_masks` into the image runs on the GPU only (got a CPU tensor); there is no CPU fallback: call "
+                       "inference(..., do_postprocess=False) for raw ROI-head results")
     h, w = results.image_size
     sx, sy = output_width / w, output_height / h
     r = copy.copy(results)
@@ -149,6 +154,8 @@ def _detector_postprocess_boxes(results, output_height, output_width):
         name = "pred_boxes"
     r.image_size = (output_height, output_width)
     if boxes is None:
+        if masks is not None:
+            raise AfiError("`pred_masks` without `pred_boxes` to paste them into")
         return r
     t = (boxes.tensor if hasattr(boxes, "tensor") else boxes).clone()
     t[:, 0::2] *= sx
@@ -166,4 +173,9 @@ def _detector_postprocess_boxes(results, output_height, output_width):
         v = getattr(results, f, None)
         if v is not None and hasattr(v, "__getitem__") and len(v) == len(keep):
             setattr(r, f, v[keep])
+    if masks is not None:
+        if name != "pred_boxes" or len(masks) != len(keep):
+            raise AfiError(f"`pred_masks` of {len(masks)} rows without as many `pred_boxes` to paste them into")
+        from .roi_heads import paste_masks_in_image
+        r.pred_masks = paste_masks_in_image(masks[keep], t[keep], (int(output_height), int(output_width)), threshold=0.5)
     return r

@@ -1,6 +1,7 @@
 """The frozen box branch of the inference configs' ROI heads: detectron2 v0.1.1's ``StandardROIHeads`` (``ROIPooler`` with ROIAlignV2,
 ``FastRCNNConvFCHead`` with FCs only, ``FastRCNNOutputLayers``, ``fast_rcnn_inference``) at inference, forward only, fp32, on this package's
-HIP kernels.  The mask / keypoint branches and CascadeROIHeads are out of scope.
+HIP kernels; with ``masks=True`` the mask branch as well (``MaskRCNNConvUpsampleHead``, ``mask_rcnn_inference``; below).  The keypoint
+branch and CascadeROIHeads are out of scope.
 
 Per image, on the padded proposal list boxes [N, P, 4] with counts [N] (``RPN.forward_padded``'s layout):
   - ROIPooler: box -> level clamp(floor(4 + log2(sqrt(area) / 224)), min, max) of ``MODEL.ROI_HEADS.IN_FEATURES`` (zero / negative area: min),
@@ -24,7 +25,19 @@ Kernels: afi_roi_align; the FCs and the predictor are afi_conv1x1_fwd over the R
 memory in place, its weight permuted once from [out][C][S][S] to [out][S][S][C]; cls_score and bbox_pred are ONE weight, zero-padded to a
 multiple of 4; both rebuilt when a parameter changes: frozen.prepared); afi_roi_scores_boxes, afi_roi_candidates, afi_roi_nms,
 afi_roi_pick (csrc/roi.hip).  No torch mm / addmm / softmax / sort / topk, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host
-read and can be captured in a hipGraph; ``forward`` reads ``counts`` and ``truncated`` once."""
+read and can be captured in a hipGraph; ``forward`` reads ``counts`` and ``truncated`` once.
+
+The mask branch (``build_roi_heads(cfg, input_shape, masks=True)`` with MODEL.MASK_ON True; without the keyword a MASK_ON config is refused
+as before), on the box branch's padded detections boxes [N, D, 4], classes [N, D], counts [N]:
+  - mask pooler: a second ROIPooler (ROI_MASK_HEAD.POOLER_RESOLUTION / POOLER_SAMPLING_RATIO / POOLER_TYPE) on the PREDICTED boxes;
+  - ``mask_fcn1`` .. ``mask_fcn{NUM_CONV}``: Conv2d 3x3, pad 1, bias, ReLU (frozen.conv3x3: Winograd from R S^2 >= 1024 pixels, direct below);
+  - ``deconv``: ConvTranspose2d(kernel 2, stride 2) + ReLU as ONE afi_conv1x1_fwd over the prepared weight [4 Cout][Cin] (row (2a + b) Cout + co
+    = deconv.weight[ci, co, a, b], the bias four times): its dense output [R][S][S][4][Cout] is the four phases of every input pixel side by
+    side, and no pixel shuffle is materialised;
+  - ``predictor`` (1x1 to Km = NUM_CLASSES, or 1 under CLS_AGNOSTIC_MASK) for the row's own class only, sigmoid in fp64 rounded once:
+    afi_roi_mask_probs -> masks [N, D, 2S, 2S], rows past counts zero.  ``forward`` stores them as ``pred_masks`` [n, 1, 2S, 2S];
+  - ``paste_masks_in_image`` (afi_mask_paste) pastes them into image-size bool masks; the extractor's postprocess calls it.
+Keys: ``mask_head.{mask_fcn{i}, deconv, predictor}.{weight, bias}`` -- detectron2's."""
 import math
 
 import torch
@@ -32,7 +45,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import AfiError
-from .frozen import cfg_get, check_feature, prepared
+from .frozen import cfg_get, check_feature, conv3x3, prepared
 from .registry import detectron2_or_local
 from .rpn import SCALE_CLAMP, Boxes
 
@@ -49,19 +62,20 @@ def _check_feature(where, name, x):
 class ROIPooler(nn.Module):
     """detectron2's ROIPooler for ``pooler_type`` ROIAlignV2 on a padded box list: one afi_roi_align over all levels."""
 
-    def __init__(self, output_size, scales, sampling_ratio, pooler_type="ROIAlignV2", canonical_box_size=224, canonical_level=4):
+    def __init__(self, output_size, scales, sampling_ratio, pooler_type="ROIAlignV2", canonical_box_size=224, canonical_level=4,
+                 section="ROI_BOX_HEAD"):
         super().__init__()
         if pooler_type != "ROIAlignV2":
-            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_TYPE {pooler_type!r} is not supported (ROIAlignV2 only)")
+            raise AfiError(f"roi_heads: MODEL.{section}.POOLER_TYPE {pooler_type!r} is not supported (ROIAlignV2 only)")
         if isinstance(output_size, (tuple, list)):
             if len(output_size) != 2 or output_size[0] != output_size[1]:
-                raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {output_size} must be square")
+                raise AfiError(f"roi_heads: MODEL.{section}.POOLER_RESOLUTION {output_size} must be square")
             output_size = output_size[0]
         self.output_size, self.sampling_ratio = int(output_size), int(sampling_ratio)
         if not 0 < self.output_size <= ops.ROI_MAX_POOLED:
-            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {output_size} is outside 1..{ops.ROI_MAX_POOLED}")
+            raise AfiError(f"roi_heads: MODEL.{section}.POOLER_RESOLUTION {output_size} is outside 1..{ops.ROI_MAX_POOLED}")
         if self.sampling_ratio < 0:
-            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO {sampling_ratio} must be >= 0")
+            raise AfiError(f"roi_heads: MODEL.{section}.POOLER_SAMPLING_RATIO {sampling_ratio} must be >= 0")
         if canonical_box_size != 224 or canonical_level != 4:
             raise AfiError("roi_heads: the canonical box size / level are fixed at 224 / 4 (detectron2's defaults)")
         levels = [-math.log2(s) for s in scales]
@@ -117,29 +131,83 @@ class FastRCNNOutputLayers(nn.Module):
             nn.init.constant_(l.bias, 0)
 
 
-class Detections:
-    """One image's detections when detectron2's Instances is not importable: ``image_size``, ``pred_boxes``, ``scores``, ``pred_classes``."""
+class MaskRCNNConvUpsampleHead(nn.Module):
+    """detectron2's MaskRCNNConvUpsampleHead without norm: ``mask_fcn1`` .. ``mask_fcn{NUM_CONV}`` (3x3, ReLU), ``deconv`` (ConvTranspose2d
+    kernel 2, stride 2, ReLU), ``predictor`` (1x1 to Km classes)."""
 
-    def __init__(self, image_size, pred_boxes, scores, pred_classes):
+    def __init__(self, input_shape, num_classes, num_conv, conv_dim, norm="", cls_agnostic_mask=False):
+        super().__init__()
+        if norm:
+            raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.NORM {norm!r} is not supported (the mask head without norm only; the SyncBN head is "
+                           "the Cascade configs' and out of scope)")
+        if num_conv < 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.NUM_CONV {num_conv} must be >= 0")
+        if conv_dim <= 0 or conv_dim % 4:
+            raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.CONV_DIM {conv_dim} must be a positive multiple of 4")
+        self.input_shape = tuple(int(s) for s in input_shape)          # (C, S, S)
+        self.num_mask_classes = 1 if cls_agnostic_mask else int(num_classes)
+        self.conv_norm_relus = []
+        dim = self.input_shape[0]
+        for k in range(num_conv):
+            conv = nn.Conv2d(dim, conv_dim, 3, padding=1)
+            self.add_module(f"mask_fcn{k + 1}", conv)
+            self.conv_norm_relus.append(conv)
+            dim = conv_dim
+        self.deconv = nn.ConvTranspose2d(dim, conv_dim, 2, stride=2, padding=0)
+        self.predictor = nn.Conv2d(conv_dim, self.num_mask_classes, 1)
+        for l in self.conv_norm_relus + [self.deconv]:                 # detectron2's c2_msra_fill
+            nn.init.kaiming_normal_(l.weight, mode="fan_out", nonlinearity="relu")
+            nn.init.constant_(l.bias, 0)
+        nn.init.normal_(self.predictor.weight, std=0.001)
+        nn.init.constant_(self.predictor.bias, 0)
+
+
+def deconv_as_conv1x1(weight, bias):
+    """ConvTranspose2d(kernel 2, stride 2) parameters (weight [Cin, Cout, 2, 2]) as the 1x1 conv that writes the four output phases of an
+    input pixel side by side: ([4 Cout, Cin] with row (2a + b) Cout + co = weight[ci, co, a, b], the bias four times)."""
+    cin, cout = weight.shape[:2]
+    return weight.detach().float().permute(2, 3, 1, 0).reshape(4 * cout, cin).contiguous(), bias.detach().float().repeat(4).contiguous()
+
+
+class Detections:
+    """One image's detections when detectron2's Instances is not importable: ``image_size``, ``pred_boxes``, ``scores``, ``pred_classes`` and,
+    from the mask branch, ``pred_masks`` (else None)."""
+
+    def __init__(self, image_size, pred_boxes, scores, pred_classes, pred_masks=None):
         self.image_size, self.pred_boxes, self.scores, self.pred_classes = image_size, pred_boxes, scores, pred_classes
+        self.pred_masks = pred_masks
 
     def __len__(self):
         return len(self.pred_boxes)
 
     def to(self, device):
-        return Detections(self.image_size, self.pred_boxes.to(device), self.scores.to(device), self.pred_classes.to(device))
+        return Detections(self.image_size, self.pred_boxes.to(device), self.scores.to(device), self.pred_classes.to(device),
+                          self.pred_masks.to(device) if self.pred_masks is not None else None)
 
 
-def _make_detections(image_size, boxes, scores, classes):
+def _make_detections(image_size, boxes, scores, classes, masks=None):
     try:
         from detectron2.structures import Boxes as D2Boxes, Instances
     except Exception:
-        return Detections(tuple(image_size), Boxes(boxes), scores, classes)
+        return Detections(tuple(image_size), Boxes(boxes), scores, classes, masks)
     r = Instances(tuple(image_size))
     r.pred_boxes = D2Boxes(boxes)
     r.scores = scores
     r.pred_classes = classes
+    if masks is not None:
+        r.pred_masks = masks
     return r
+
+
+def paste_masks_in_image(masks, boxes, image_shape, threshold=0.5):
+    """detectron2's paste_masks_in_image on the GPU: masks [R, M, M] (or [R, 1, M, M]) fp32 probabilities, boxes [R, 4] or Boxes, image_shape
+    (H, W) -> bool [R, H, W] (afi_mask_paste; pixels whose centre is outside their box are False)."""
+    boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
+    if not torch.is_tensor(masks) or not torch.is_tensor(boxes) or not masks.is_cuda or not boxes.is_cuda:
+        raise AfiError("paste_masks_in_image: masks and boxes must be GPU tensors; the paste runs on the GPU only, there is no CPU fallback")
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    return ops.mask_paste(masks, boxes.reshape(-1, 4), image_shape, threshold)
 
 
 def _rows_as_pixels(t2d):
@@ -155,7 +223,7 @@ def _pixels_as_rows(t):
 
 @ROI_HEADS_REGISTRY.register()
 class StandardROIHeads(nn.Module):
-    def __init__(self, cfg, input_shape):
+    def __init__(self, cfg, input_shape, masks=False):
         super().__init__()
         m = cfg.MODEL
         rh, bh = cfg_get(m, "ROI_HEADS", None), cfg_get(m, "ROI_BOX_HEAD", None)
@@ -163,8 +231,11 @@ class StandardROIHeads(nn.Module):
             raise AfiError("roi_heads: the config has no MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD section (afigan_amd.config.get_cfg declares them)")
         if cfg_get(rh, "NAME", "StandardROIHeads") != "StandardROIHeads":
             raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {rh.NAME!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
-        if cfg_get(m, "MASK_ON", False):
-            raise AfiError("roi_heads: MODEL.MASK_ON is set -- box branch only; set MODEL.MASK_ON False")
+        if masks and not cfg_get(m, "MASK_ON", False):
+            raise AfiError("roi_heads: masks=True builds the mask branch and needs MODEL.MASK_ON True")
+        if cfg_get(m, "MASK_ON", False) and not masks:
+            raise AfiError("roi_heads: MODEL.MASK_ON is set -- box branch only; set MODEL.MASK_ON False, or build the mask branch as well with "
+                           "build_roi_heads(cfg, input_shape, masks=True)")
         if cfg_get(m, "KEYPOINT_ON", False):
             raise AfiError("roi_heads: MODEL.KEYPOINT_ON is set -- box branch only; set MODEL.KEYPOINT_ON False")
         if cfg_get(bh, "NAME", "FastRCNNConvFCHead") != "FastRCNNConvFCHead":
@@ -198,7 +269,18 @@ class StandardROIHeads(nn.Module):
         self.box_head = FastRCNNConvFCHead((C_, S, S), int(cfg_get(bh, "NUM_FC", 0)), int(cfg_get(bh, "FC_DIM", 1024)), int(cfg_get(bh, "NUM_CONV", 0)),
                                            cfg_get(bh, "NORM", ""))
         self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes, bool(cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
-        self.mask_on = self.keypoint_on = False
+        self.mask_on, self.keypoint_on = bool(masks), False
+        if self.mask_on:
+            mh = cfg_get(m, "ROI_MASK_HEAD", None)
+            if mh is None:
+                raise AfiError("roi_heads: the config has no MODEL.ROI_MASK_HEAD section (afigan_amd.config.get_cfg declares it)")
+            if cfg_get(mh, "NAME", "MaskRCNNConvUpsampleHead") != "MaskRCNNConvUpsampleHead":
+                raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.NAME {mh.NAME!r} is not supported (MaskRCNNConvUpsampleHead only)")
+            self.mask_pooler = ROIPooler(cfg_get(mh, "POOLER_RESOLUTION", 14), [1.0 / s.stride for s in shapes], cfg_get(mh, "POOLER_SAMPLING_RATIO", 0),
+                                         cfg_get(mh, "POOLER_TYPE", "ROIAlignV2"), section="ROI_MASK_HEAD")
+            Sm = self.mask_pooler.output_size
+            self.mask_head = MaskRCNNConvUpsampleHead((C_, Sm, Sm), self.num_classes, int(cfg_get(mh, "NUM_CONV", 0)), int(cfg_get(mh, "CONV_DIM", 256)),
+                                                      cfg_get(mh, "NORM", ""), bool(cfg_get(mh, "CLS_AGNOSTIC_MASK", False)))
         for p in self.parameters():
             p.requires_grad_(False)
 
@@ -221,6 +303,18 @@ class StandardROIHeads(nn.Module):
             b[:nc], b[nc:nc + nb] = ts[2].detach(), ts[4].detach()
             return w1, w, b
         return prepared(self, "prep", ts, build)
+
+    def _prepare_mask(self):
+        """([(3x3 weight in [O][kh][kw][I] memory, bias)], (deconv as a [4 Cout, Cin] 1x1 weight, its bias four times), (predictor [Km, C],
+        bias)), rebuilt when a parameter changes."""
+        mh = self.mask_head
+        ts = [t for l in mh.conv_norm_relus + [mh.deconv, mh.predictor] for t in (l.weight, l.bias)]
+
+        def build():
+            convs = [(ops.to_ohwi(l.weight.detach().float()), l.bias.detach().float().contiguous()) for l in mh.conv_norm_relus]
+            pw = mh.predictor.weight.detach().float().reshape(mh.num_mask_classes, -1).contiguous()
+            return convs, deconv_as_conv1x1(mh.deconv.weight, mh.deconv.bias), (pw, mh.predictor.bias.detach().float().contiguous())
+        return prepared(self, "mask_prep", ts, build)
 
     # ------------------------------------------------------------------ checks
     def _check(self, features, boxes=None, counts=None):
@@ -277,11 +371,43 @@ class StandardROIHeads(nn.Module):
         return {"boxes": ob, "scores": os_, "classes": oc, "counts": oc_n, "truncated": trunc, "class_scores": scores, "class_boxes": cboxes,
                 "cand": cand, "keep": keep}
 
+    def mask_features(self, features, boxes, counts):
+        """The mask pooler's features of a padded box list: pixel-major [N D, C, S, S], rows past counts zero."""
+        if not self.mask_on:
+            raise AfiError("roi_heads: the heads were built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
+        xs = self._check(features, boxes, counts)
+        with torch.no_grad():
+            return self.mask_pooler(xs, boxes.contiguous(), counts.contiguous())
+
+    def mask_head_forward(self, pooled, classes, counts, intermediates=False):
+        """pooled [N D, C, S, S] pixel-major, classes [N, D] int32, counts [N] -> mask probabilities [N, D, 2S, 2S], rows past counts zero;
+        intermediates: also (every conv's output [R, CONV_DIM, S, S], the deconv's 4-phase output [R, 4 CONV_DIM, S, S])."""
+        if not self.mask_on:
+            raise AfiError("roi_heads: the heads were built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
+        convs, (wd, bd), (wp, bp) = self._prepare_mask()
+        N, D = classes.shape
+        x, acts = pooled, []
+        for wb in convs:
+            x = conv3x3(x, wb, relu=True)
+            acts.append(x)
+        h = ops.conv1x1_fwd(x, wd, bd, act=2)
+        probs = ops.roi_mask_probs(h, wp, bp, classes.contiguous(), counts.contiguous())
+        probs = probs.view(N, D, probs.shape[1], probs.shape[2])
+        return (probs, acts, h) if intermediates else probs
+
+    def _mask_branch(self, xs, boxes, classes, counts, r=None):
+        pooled = self.mask_pooler(xs, boxes, counts)
+        probs, acts, h = self.mask_head_forward(pooled, classes, counts, intermediates=True)
+        if r is not None:
+            r.update(mask_pooled=pooled, mask_convs=acts, mask_deconv=h, mask_probs=probs)
+        return probs
+
     def forward_padded(self, image_sizes, features, boxes, counts, intermediates=False):
         """(boxes [N, D, 4], scores [N, D], classes [N, D] int32, counts [N] int32, truncated [N] int32) on the device, D =
         TEST.DETECTIONS_PER_IMAGE, rows past counts zero; image_sizes: [N, 2] device tensor (height, width) of the un-padded images; boxes
         [N, P, 4] / counts [N]: the proposals as ``RPN.forward_padded`` returns them.  No host read: capturable in a hipGraph.  intermediates:
-        the dict of ``select`` plus ``pooled``, ``fc`` and ``pred`` instead."""
+        the dict of ``select`` plus ``pooled``, ``fc`` and ``pred`` instead.  With the mask branch a sixth tensor, masks [N, D, 2S, 2S] (rows
+        past counts zero), and the intermediates ``mask_pooled``, ``mask_convs``, ``mask_deconv`` and ``mask_probs``."""
         xs = self._check(features, boxes, counts)
         if not torch.is_tensor(image_sizes) or not image_sizes.is_cuda:
             raise AfiError("roi_heads: forward_padded takes the image sizes as an [N, 2] tensor on the GPU (forward() takes a list)")
@@ -292,10 +418,12 @@ class StandardROIHeads(nn.Module):
             pooled = self.box_pooler(xs, boxes, counts)
             pred, acts = self.box_head_forward(pooled, intermediates=True)
             r = self.select(pred, boxes, counts, image_sizes.to(torch.float32).contiguous())
+            masks = self._mask_branch(xs, r["boxes"], r["classes"], r["counts"], r) if self.mask_on else None
         if intermediates:
             r.update(pooled=pooled, fc=acts, pred=pred)
             return r
-        return r["boxes"], r["scores"], r["classes"], r["counts"], r["truncated"]
+        out = (r["boxes"], r["scores"], r["classes"], r["counts"], r["truncated"])
+        return out + (masks,) if self.mask_on else out
 
     def forward(self, images, features, proposals, targets=None):
         """detectron2's StandardROIHeads.forward at inference: (one result per image -- image_size, pred_boxes, scores, pred_classes (int64),
@@ -319,25 +447,59 @@ class StandardROIHeads(nn.Module):
             boxes[n, :b.shape[0]] = b
         counts = torch.tensor([int(b.shape[0]) for b in pbs], dtype=torch.int32).to(dev)
         hw = torch.tensor(sizes, dtype=torch.float32).to(dev)
-        ob, os_, oc, cn, trunc = self.forward_padded(hw, features, boxes, counts)
+        ob, os_, oc, cn, trunc, *mk = self.forward_padded(hw, features, boxes, counts)
         host = torch.stack([cn, trunc]).tolist()
         if any(host[1]):
             raise AfiError(f"roi_heads: image(s) {[n for n, t in enumerate(host[1]) if t]} have more than {ROI_MAX_CANDIDATES} class scores above "
                            f"MODEL.ROI_HEADS.SCORE_THRESH_TEST {self.test_score_thresh} and fewer than TEST.DETECTIONS_PER_IMAGE "
                            f"{self.test_detections_per_img} survive NMS among the {ROI_MAX_CANDIDATES} highest (the candidate cap): the result "
                            "could differ from the uncapped one; raise SCORE_THRESH_TEST")
-        return [_make_detections(sz, ob[n, :c], os_[n, :c], oc[n, :c].to(torch.int64)) for n, (sz, c) in enumerate(zip(sizes, host[0]))], {}
+        return [_make_detections(sz, ob[n, :c], os_[n, :c], oc[n, :c].to(torch.int64), mk[0][n, :c].unsqueeze(1) if mk else None)
+                for n, (sz, c) in enumerate(zip(sizes, host[0]))], {}
 
     def forward_with_given_boxes(self, features, instances):
-        """detectron2's StandardROIHeads.forward_with_given_boxes with the mask and keypoint branches off: the instances unchanged."""
+        """detectron2's StandardROIHeads.forward_with_given_boxes: without the mask branch the instances unchanged; with it, ``pred_masks``
+        [n, 1, 2S, 2S] set on every instance from its ``pred_boxes`` and ``pred_classes``."""
         if self.training and torch.is_grad_enabled():
             raise AfiError("roi_heads: the ROI heads are inference-only (frozen): call .eval(), or run them under torch.no_grad()")
+        if not self.mask_on:
+            return instances
+        xs = self._check(features)
+        N, dev = xs[0].shape[0], xs[0].device
+        if len(instances) != N:
+            raise AfiError(f"roi_heads: {len(instances)} instance lists for a batch of {N}")
+        bs, cs = [], []
+        for inst in instances:
+            if getattr(inst, "pred_boxes", None) is None or getattr(inst, "pred_classes", None) is None:
+                raise AfiError("roi_heads: forward_with_given_boxes needs `pred_boxes` and `pred_classes` on every instance")
+            b = inst.pred_boxes.tensor if hasattr(inst.pred_boxes, "tensor") else inst.pred_boxes
+            _check_feature("roi_heads", "pred_boxes", b)
+            if not inst.pred_classes.is_cuda:
+                raise AfiError("roi_heads: pred_classes is a CPU tensor; the ROI heads run on the GPU only, there is no CPU fallback")
+            bs.append(b.reshape(-1, 4))
+            cs.append(inst.pred_classes.reshape(-1))
+            if cs[-1].shape[0] != bs[-1].shape[0]:
+                raise AfiError(f"roi_heads: {bs[-1].shape[0]} pred_boxes and {cs[-1].shape[0]} pred_classes")
+        # the list length forward_padded uses whenever the boxes fit, so that the same kernels run on the same shapes and the masks agree bit for bit
+        D = max(self.test_detections_per_img, max(int(b.shape[0]) for b in bs))
+        boxes = torch.zeros((N, D, 4), device=dev, dtype=torch.float32)
+        classes = torch.zeros((N, D), device=dev, dtype=torch.int32)
+        for n, (b, c) in enumerate(zip(bs, cs)):
+            boxes[n, :b.shape[0]] = b
+            classes[n, :b.shape[0]] = c.to(torch.int32)
+        counts = torch.tensor([int(b.shape[0]) for b in bs], dtype=torch.int32).to(dev)
+        with torch.no_grad():
+            probs = self._mask_branch(xs, boxes, classes, counts)
+        for n, (inst, b) in enumerate(zip(instances, bs)):
+            inst.pred_masks = probs[n, :b.shape[0]].unsqueeze(1)
         return instances
 
 
-def build_roi_heads(cfg, input_shape):
-    """detectron2's build_roi_heads: the class registered under MODEL.ROI_HEADS.NAME."""
+def build_roi_heads(cfg, input_shape, masks=False):
+    """detectron2's build_roi_heads: the class registered under MODEL.ROI_HEADS.NAME.  masks=True builds the mask branch as well (it needs
+    MODEL.MASK_ON True); without it a MASK_ON config is refused."""
     name = cfg_get(cfg_get(cfg.MODEL, "ROI_HEADS", None), "NAME", "StandardROIHeads")
     if name != "StandardROIHeads":
         raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (this package provides the box branch of 'StandardROIHeads')")
-    return ROI_HEADS_REGISTRY.get(name)(cfg, input_shape)
+    cls = ROI_HEADS_REGISTRY.get(name)
+    return cls(cfg, input_shape, masks=True) if masks else cls(cfg, input_shape)

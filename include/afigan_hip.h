@@ -650,6 +650,27 @@ int afi_roi_nms(const float* boxes, const int* cls, const int* valid, int N, int
 int afi_roi_pick(const float* cand_boxes, const float* cand_scores, const int* cand_cls, const int* keep, const int* n_over, int N, int M, int D,
                  float* out_boxes, float* out_scores, int* out_classes, int* counts, int* truncated, void* stream);
 
+/* ------------------------------------------------------------------ frozen mask branch of StandardROIHeads (afigan_amd/roi_heads.py)
+ * detectron2 v0.1.1's mask_rcnn_inference and paste_masks_in_image.  The mask pooler is afi_roi_align on the padded detections, the head's 3x3
+ * convs are the frozen conv dispatch, and the deconv (ConvTranspose2d kernel 2, stride 2) is one afi_conv1x1_fwd over a [4 Cout][Cin] weight
+ * (row (2a + b) Cout + co = deconv.weight[ci][co][a][b]), whose dense output [R][S][S][4][C] holds phase 2a + b of input pixel (y, x) = output
+ * pixel (2y + a, 2x + b).  No host synchronisation, no atomics; every result is bit-identical between runs.
+ * afi_roi_mask_probs: h = that layout, R = N D rows; w [Km][C], bias [Km]; classes [N][D] (int32), counts [N].  probs [N D][2S][2S]:
+ *   z = bias[c] + sum_k w[c][k] h[k] for the row's class c (0 when Km == 1) in fp32 (fmaf per lane in channel order, a fixed butterfly), then
+ *   p = 1 / (1 + exp(-z)) in fp64 from the fp32 z, rounded once.  Rows d >= counts[n] and rows whose class is outside 0 .. Km - 1 are zero and
+ *   read neither h nor w.  C % 4 == 0, 1 <= S <= 14, h and w 16-byte aligned, N <= 65535.
+ * afi_mask_paste: probs [R][M][M], boxes [R][4] (x0, y0, x1, y1, fp32), out [R][H][W], one byte per pixel, 0 or 1.  For a pixel (y, x) whose
+ *   centre lies inside the box (x0 <= x + 0.5 <= x1 and y0 <= y + 0.5 <= y1): gx = (x + 0.5 - x0) / (x1 - x0) 2 - 1, ix = ((gx + 1) M - 1) / 2
+ *   (gy, iy likewise), in fp64 from the fp32 box, operation by operation; taps floor(ix), floor(ix) + 1 with weights 1 - frac, frac per axis, a
+ *   tap outside 0 .. M - 1 contributing zero (grid_sample: bilinear, zeros padding, align_corners false); the four weights are rounded to fp32
+ *   and v = fma(w11, m11, fma(w10, m10, fma(w01, m01, w00 m00))) in fp32 (y0x0, y0x1, y1x0, y1x1); out = v >= threshold.  Every other pixel
+ *   is 0 -- detectron2 samples only a region around the boxes; at threshold 0.5 and probabilities <= 1 a pixel whose centre is outside its box
+ *   cannot reach the threshold, so this equals sampling the whole image.  A box with a non-positive or NaN side gives zeros.  M <= 64,
+ *   H <= 2097120; out may start at any byte.  R = 0 is accepted and launches nothing. */
+int afi_roi_mask_probs(const float* h, const float* w, const float* bias, const int* classes, const int* counts, int N, int D, int C, int S, int Km,
+                       float* probs, void* stream);
+int afi_mask_paste(const float* probs, const float* boxes, int R, int M, int H, int W, float threshold, unsigned char* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
