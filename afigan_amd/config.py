@@ -160,7 +160,7 @@ def get_cfg():
                                       "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0), "SMOOTH_L1_BETA": 0.0, "LOSS_WEIGHT": 1.0,
                                       "PRE_NMS_TOPK_TRAIN": 12000, "PRE_NMS_TOPK_TEST": 6000, "POST_NMS_TOPK_TRAIN": 2000,
                                       "POST_NMS_TOPK_TEST": 1000, "NMS_THRESH": 0.7},
-                              # detectron2 v0.1.1's ROI-head defaults (_C.MODEL.ROI_HEADS / ROI_BOX_HEAD / ROI_MASK_HEAD, MASK_ON, KEYPOINT_ON): what
+                              # detectron2 v0.1.1's ROI-head defaults (_C.MODEL.ROI_HEADS / ROI_BOX_HEAD / ROI_BOX_CASCADE_HEAD / ROI_MASK_HEAD, MASK_ON, KEYPOINT_ON): what
                               # roi_heads.py reads, and every key the reference yamls set there (the mask head's are declared only)
                               "MASK_ON": False, "KEYPOINT_ON": False,
                               "ROI_HEADS": {"NAME": "Res5ROIHeads", "NUM_CLASSES": 80, "IN_FEATURES": ["res4"], "IOU_THRESHOLDS": [0.5],
@@ -169,6 +169,8 @@ def get_cfg():
                               "ROI_BOX_HEAD": {"NAME": "", "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0), "SMOOTH_L1_BETA": 0.0,
                                                "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2", "NUM_FC": 0,
                                                "FC_DIM": 1024, "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_BBOX_REG": False},
+                              "ROI_BOX_CASCADE_HEAD": {"BBOX_REG_WEIGHTS": ((10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0), (30.0, 30.0, 15.0, 15.0)),
+                                                       "IOUS": (0.5, 0.6, 0.7)},
                               "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0,
                                                 "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False,
                                                 "POOLER_TYPE": "ROIAlignV2"}},

@@ -8,6 +8,8 @@
 //                         fp32 and the samples summed in fp32 in (iy, ix, corner) order.  No LDS, no atomics.
 //   afi_roi_scores_boxes  one wave per row: softmax over the K + 1 logits in fp64 (fixed butterfly order), Box2BoxTransform.apply_deltas
 //                         + clip per class in fp64, each rounded once.
+//   afi_roi_cascade_stage the same row code with class-agnostic boxes, the score added to the previous stages' running score and, at the last
+//                         stage, scaled by 1 / S (CascadeROIHeads): one launch per stage, the per-stage scores are never stored.
 //   afi_roi_candidates    afi_rpn_topk on the scores seen as a [N][P][K][1] map (index r K + c), then per candidate class, box, valid and the
 //                         count of all scores above the threshold (a fixed-order block sum).
 //   afi_roi_nms           afi_select.h's greedy NMS with classes.
@@ -153,19 +155,27 @@ __device__ __forceinline__ double roi_wave_sum(double v) {
     return v;
 }
 
-// One wave per row r = n P + j; lane c, c + 64, ...: class c.
-__global__ __launch_bounds__(256) void afi_roi_scores_boxes_kernel(const RoiDecode d, const float* __restrict__ pred,
-                                                                   const float* __restrict__ proposals, const int* __restrict__ counts,
-                                                                   const float* __restrict__ image_hw, float* __restrict__ scores,
-                                                                   float* __restrict__ boxes) {
+// The running score of the cascade: (prev + s) and then, when out_scale != 1, the product with out_scale -- one fp32 operation each.
+__device__ __forceinline__ float roi_running_score(float s, const float* prev, float out_scale) {
+#pragma clang fp contract(off)
+    float v = prev ? *prev + s : s;               // (the lane reads its own element before it writes it: scores may be prev_scores)
+    if (out_scale != 1.f) v = v * out_scale;
+    return v;
+}
+
+// One wave per row r = n P + j; lane c, c + 64, ...: class c.  CASCADE: the scores go through roi_running_score (d.agnostic is 1 there).
+template <bool CASCADE>
+__device__ __forceinline__ void roi_scores_boxes_row(const RoiDecode& d, const float* pred, const float* proposals, const int* counts,
+                                                     const float* image_hw, const float* prev, float out_scale, float* scores, float* boxes) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long long)d.N * d.P) return;
     const int n = (int)(row / d.P), j = (int)(row - (long long)n * d.P), K = d.K, Kb = d.agnostic ? 1 : K;
     float* sc = scores + row * K;
     float* bx = boxes + row * Kb * 4;
+    const float* pv = CASCADE && prev ? prev + row * K : nullptr;
     if (j >= counts[n]) {
-        for (int c = lane; c < K; c += 64) sc[c] = -INFINITY;
+        for (int c = lane; c < K; c += 64) sc[c] = CASCADE ? roi_running_score(-INFINITY, pv ? pv + c : nullptr, out_scale) : -INFINITY;
         for (int c = lane; c < 4 * Kb; c += 64) bx[c] = 0.f;
         return;
     }
@@ -188,7 +198,8 @@ __global__ __launch_bounds__(256) void afi_roi_scores_boxes_kernel(const RoiDeco
     const float ih = image_hw[2 * n], iw = image_hw[2 * n + 1];
     const float* dl = q + K + 1;
     for (int c = lane; c < K; c += 64) {
-        sc[c] = bad ? __builtin_nanf("") : (float)(exp((double)q[c] - m) / s);
+        const float sv = bad ? __builtin_nanf("") : (float)(exp((double)q[c] - m) / s);
+        sc[c] = CASCADE ? roi_running_score(sv, pv ? pv + c : nullptr, out_scale) : sv;
         if (c < Kb) {
             const float* t = dl + 4 * c;
             const double dx = (double)t[0] / (double)d.wx, dy = (double)t[1] / (double)d.wy;
@@ -201,6 +212,21 @@ __global__ __launch_bounds__(256) void afi_roi_scores_boxes_kernel(const RoiDeco
             o[3] = fminf(fmaxf((float)(pcy + 0.5 * ph), 0.f), ih);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void afi_roi_scores_boxes_kernel(const RoiDecode d, const float* __restrict__ pred,
+                                                                   const float* __restrict__ proposals, const int* __restrict__ counts,
+                                                                   const float* __restrict__ image_hw, float* __restrict__ scores,
+                                                                   float* __restrict__ boxes) {
+    roi_scores_boxes_row<false>(d, pred, proposals, counts, image_hw, nullptr, 1.f, scores, boxes);
+}
+
+// (scores and prev_scores may be one buffer: neither is __restrict__)
+__global__ __launch_bounds__(256) void afi_roi_cascade_stage_kernel(const RoiDecode d, const float* __restrict__ pred,
+                                                                    const float* __restrict__ proposals, const int* __restrict__ counts,
+                                                                    const float* __restrict__ image_hw, const float* prev_scores, float out_scale,
+                                                                    float* scores, float* __restrict__ boxes) {
+    roi_scores_boxes_row<true>(d, pred, proposals, counts, image_hw, prev_scores, out_scale, scores, boxes);
 }
 
 int afi_roi_scores_boxes(const float* pred, long long ld_pred, int N, int P, int K, int agnostic, const float* proposals, const int* counts,
@@ -217,6 +243,21 @@ int afi_roi_scores_boxes(const float* pred, long long ld_pred, int N, int P, int
     if (blocks > 0x7fffffffll) return AFI_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(afi_roi_scores_boxes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d, pred, proposals, counts, image_hw,
                        scores, boxes);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+int afi_roi_cascade_stage(const float* pred, long long ld_pred, int N, int P, int K, const float* proposals, const int* counts,
+                          const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, const float* prev_scores,
+                          float out_scale, float* scores, float* boxes, void* stream) {
+    if (!pred || !proposals || !counts || !image_hw || !scores || !boxes || N <= 0 || N > 65535 || P <= 0 || K <= 0) return AFI_ERR_BAD_ARG;
+    if (K > ROI_MAX_K) return AFI_ERR_UNSUPPORTED;
+    if (ld_pred < (long long)K + 1 + 4) return AFI_ERR_BAD_ARG;
+    if (!(wx > 0.f) || !(wy > 0.f) || !(ww > 0.f) || !(wh > 0.f) || !(out_scale > 0.f) || out_scale > 3.4e38f) return AFI_ERR_BAD_ARG;
+    const RoiDecode d{N, P, K, 1, ld_pred, wx, wy, ww, wh, scale_clamp};
+    const long long blocks = ((long long)N * P + 3) / 4;
+    if (blocks > 0x7fffffffll) return AFI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(afi_roi_cascade_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d, pred, proposals, counts, image_hw,
+                       prev_scores, out_scale, scores, boxes);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 

@@ -33,9 +33,10 @@ def fold_conv(conv, norm=None, scale=1.0):
         w = w * s.view(-1, 1, 1, 1)
         b = (b - norm.running_mean.double()) * s + norm.bias.double()
     w, b = w.float(), (b * scale).float().contiguous()
-    if conv.kernel_size == 1:
+    k = conv.kernel_size if isinstance(conv.kernel_size, int) else (conv.kernel_size[0] if len(set(conv.kernel_size)) == 1 else 0)   # nn.Conv2d: a tuple
+    if k == 1:
         return w.reshape(w.shape[0], w.shape[1]).contiguous(), b
-    if conv.kernel_size == 3:
+    if k == 3:
         return ops.to_ohwi(w), b
     return w.contiguous(), b
 

@@ -992,24 +992,55 @@ def roi_align(levels, min_level, boxes, counts, S, sampling_ratio=0, out=None):
     return out
 
 
+def _roi_pred_rows(name, pred, K, Kb, proposals, counts, image_hw):
+    """The checks roi_scores_boxes and roi_cascade_stage share; returns (pred as its [N P, Cpad] matrix, N, P)."""
+    _check_cuda(pred, proposals, image_hw)
+    _check_i32(counts)
+    N, P = proposals.shape[:2]
+    p2 = pred.reshape(pred.shape[0], -1) if pred.dim() == 4 and pred.shape[2:] == (1, 1) and pred.stride(1) == 1 else pred
+    if p2.dim() != 2 or p2.shape[0] != N * P or p2.shape[1] < K + 1 + 4 * Kb or p2.stride(1) != 1 or not 0 < K <= ROI_MAX_CLASSES \
+            or tuple(proposals.shape) != (N, P, 4) or tuple(image_hw.shape) != (N, 2) or tuple(counts.shape) != (N,):
+        raise _lib.AfiError(f"{name}: pred [{N * P}, >= {K + 1 + 4 * Kb}] with dense rows, proposals [N, P, 4], image sizes [N, 2], "
+                            f"counts [N] and 1 <= K <= {ROI_MAX_CLASSES} expected, got {tuple(pred.shape)}, {tuple(proposals.shape)}, "
+                            f"{tuple(image_hw.shape)}, {tuple(counts.shape)}, K {K}")
+    return p2, N, P
+
+
 def roi_scores_boxes(pred, K, agnostic, proposals, counts, image_hw, weights, scale_clamp=4.135166556742356):
     """pred: the predictor's output, pixel-major [N P, Cpad, 1, 1] (or [N P, Cpad]): K + 1 class logits (background last), then 4 K (or 4,
     agnostic) deltas.  Returns (scores [N, P, K] fp32 = softmax without the background column, -inf past counts; boxes [N, P, K or 1, 4] decoded
     from proposals [N, P, 4] and clipped to image_hw [N, 2]) (afi_roi_scores_boxes)."""
-    _check_cuda(pred, proposals, image_hw)
-    _check_i32(counts)
-    N, P = proposals.shape[:2]
     Kb = 1 if agnostic else K
-    p2 = pred.reshape(pred.shape[0], -1) if pred.dim() == 4 and pred.shape[2:] == (1, 1) and pred.stride(1) == 1 else pred
-    if p2.dim() != 2 or p2.shape[0] != N * P or p2.shape[1] < K + 1 + 4 * Kb or p2.stride(1) != 1 or not 0 < K <= ROI_MAX_CLASSES \
-            or tuple(proposals.shape) != (N, P, 4) or tuple(image_hw.shape) != (N, 2) or tuple(counts.shape) != (N,):
-        raise _lib.AfiError(f"roi_scores_boxes: pred [{N * P}, >= {K + 1 + 4 * Kb}] with dense rows, proposals [N, P, 4], image sizes [N, 2], "
-                            f"counts [N] and 1 <= K <= {ROI_MAX_CLASSES} expected, got {tuple(pred.shape)}, {tuple(proposals.shape)}, "
-                            f"{tuple(image_hw.shape)}, {tuple(counts.shape)}, K {K}")
+    p2, N, P = _roi_pred_rows("roi_scores_boxes", pred, K, Kb, proposals, counts, image_hw)
     scores = torch.empty((N, P, K), device=pred.device, dtype=torch.float32)
     boxes = torch.empty((N, P, Kb, 4), device=pred.device, dtype=torch.float32)
     call("afi_roi_scores_boxes", _p(p2), p2.stride(0), N, P, int(K), int(bool(agnostic)), _p(proposals.contiguous()), _p(counts.contiguous()),
          _p(image_hw.contiguous()), *[float(w) for w in weights], float(scale_clamp), _p(scores), _p(boxes), stream_ptr())
+    return scores, boxes
+
+
+def roi_cascade_stage(pred, K, proposals, counts, image_hw, weights, prev_scores=None, out_scale=1.0, scale_clamp=4.135166556742356, out=None,
+                      out_boxes=None):
+    """One stage of CascadeROIHeads on the predictor's output pred [N P, Cpad] (K + 1 class logits, 4 class-agnostic deltas): returns (scores
+    [N, P, K] = (prev_scores + s) out_scale with s roi_scores_boxes' scores -- one fp32 operation each, the product only when out_scale != 1;
+    boxes [N, P, 4] = the clipped decode, the next stage's proposals).  prev_scores None: the first stage.  out: where the scores go; it may be
+    prev_scores itself; out_boxes: where the boxes go (afi_roi_cascade_stage)."""
+    p2, N, P = _roi_pred_rows("roi_cascade_stage", pred, K, 1, proposals, counts, image_hw)
+    for name, t in (("prev_scores", prev_scores), ("out", out)):
+        if t is not None:
+            _check_cuda(t)
+            if tuple(t.shape) != (N, P, K) or not t.is_contiguous():
+                raise _lib.AfiError(f"roi_cascade_stage: {name} must be a dense [{N}, {P}, {K}] tensor, got {tuple(t.shape)}")
+    if not 0.0 < float(out_scale) < float("inf"):
+        raise _lib.AfiError(f"roi_cascade_stage: out_scale {out_scale} must be a positive number")
+    scores = out if out is not None else torch.empty((N, P, K), device=pred.device, dtype=torch.float32)
+    if out_boxes is not None:
+        _check_cuda(out_boxes)
+        if tuple(out_boxes.shape) != (N, P, 4) or not out_boxes.is_contiguous():
+            raise _lib.AfiError(f"roi_cascade_stage: out_boxes must be a dense [{N}, {P}, 4] tensor, got {tuple(out_boxes.shape)}")
+    boxes = out_boxes if out_boxes is not None else torch.empty((N, P, 4), device=pred.device, dtype=torch.float32)
+    call("afi_roi_cascade_stage", _p(p2), p2.stride(0), N, P, int(K), _p(proposals.contiguous()), _p(counts.contiguous()), _p(image_hw.contiguous()),
+         *[float(w) for w in weights], float(scale_clamp), _p(prev_scores), float(out_scale), _p(scores), _p(boxes), stream_ptr())
     return scores, boxes
 
 

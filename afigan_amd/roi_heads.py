@@ -1,7 +1,7 @@
 """The frozen box branch of the inference configs' ROI heads: detectron2 v0.1.1's ``StandardROIHeads`` (``ROIPooler`` with ROIAlignV2,
 ``FastRCNNConvFCHead`` with FCs only, ``FastRCNNOutputLayers``, ``fast_rcnn_inference``) at inference, forward only, fp32, on this package's
-HIP kernels; with ``masks=True`` the mask branch as well (``MaskRCNNConvUpsampleHead``, ``mask_rcnn_inference``; below).  The keypoint
-branch and CascadeROIHeads are out of scope.
+HIP kernels; with ``masks=True`` the mask branch as well (``MaskRCNNConvUpsampleHead``, ``mask_rcnn_inference``; below).  ``CascadeROIHeads``
+(``build_roi_heads(cfg, input_shape, cascade=True)``; at the end) shares all of it.  The keypoint branch is out of scope.
 
 Per image, on the padded proposal list boxes [N, P, 4] with counts [N] (``RPN.forward_padded``'s layout):
   - ROIPooler: box -> level clamp(floor(4 + log2(sqrt(area) / 224)), min, max) of ``MODEL.ROI_HEADS.IN_FEATURES`` (zero / negative area: min),
@@ -37,7 +37,19 @@ as before), on the box branch's padded detections boxes [N, D, 4], classes [N, D
   - ``predictor`` (1x1 to Km = NUM_CLASSES, or 1 under CLS_AGNOSTIC_MASK) for the row's own class only, sigmoid in fp64 rounded once:
     afi_roi_mask_probs -> masks [N, D, 2S, 2S], rows past counts zero.  ``forward`` stores them as ``pred_masks`` [n, 1, 2S, 2S];
   - ``paste_masks_in_image`` (afi_mask_paste) pastes them into image-size bool masks; the extractor's postprocess calls it.
-Keys: ``mask_head.{mask_fcn{i}, deconv, predictor}.{weight, bias}`` -- detectron2's."""
+Keys: ``mask_head.{mask_fcn{i}, deconv, predictor}.{weight, bias}`` -- detectron2's.
+
+``CascadeROIHeads`` (detectron2 v0.1.1's cascade_rcnn.py at inference): S = len(MODEL.ROI_BOX_CASCADE_HEAD.IOUS) stages on ONE box pooler, every
+stage with its own ``box_head.{k}`` (``conv1`` .. ``conv{NUM_CONV}``: 3x3, pad 1, norm, ReLU; flatten in [C][S][S] order; ``fc1`` ..) and
+``box_predictor.{k}`` (K + 1 logits, 4 class-agnostic deltas) and its own BBOX_REG_WEIGHTS[k]:
+  - stage k pools its box list, runs head and predictor, and afi_roi_cascade_stage gives boxes_k = clip(apply_deltas(weights_k)) -- the next
+    stage's list, no box dropped -- and the running score (s_0 + s_1 + ...) in fp32, left to right, times float32(1 / S) at the last stage:
+    detectron2's ``sum(scores_per_stage) * (1.0 / S)``.  The S score tensors are never stored;
+  - then fast_rcnn_inference on the mean scores and the last stage's boxes (class-agnostic), and StandardROIHeads' mask branch.
+The norm of a conv (ROI_BOX_HEAD.NORM / ROI_MASK_HEAD.NORM: "", "BN", "SyncBN", "FrozenBN") is its child ``norm`` (buffers weight, bias,
+running_mean, running_var; BN / SyncBN also num_batches_tracked, so an nn.SyncBatchNorm checkpoint loads with strict=True), always on its running
+statistics, eps 1e-5, folded into the conv in fp64 (frozen.fold_conv) and cached (frozen.prepared).  The conv head and the normed mask head are
+the Cascade class's only."""
 import math
 
 import torch
@@ -45,7 +57,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import AfiError
-from .frozen import cfg_get, check_feature, conv3x3, prepared
+from .frozen import FROZEN_BN_EPS, FrozenBatchNorm2d, cfg_get, check_feature, conv3x3, fold_conv, prepared
 from .registry import detectron2_or_local
 from .rpn import SCALE_CLAMP, Boxes
 
@@ -92,23 +104,76 @@ class ROIPooler(nn.Module):
         return ops.roi_align([ops.pixel_major(t) for t in x], self.min_level, boxes, counts, self.output_size, self.sampling_ratio)
 
 
-class FastRCNNConvFCHead(nn.Module):
-    """detectron2's FastRCNNConvFCHead with NUM_CONV 0: ``fc1`` .. ``fc{NUM_FC}`` with ReLU."""
+HEAD_NORMS = ("", "BN", "SyncBN", "FrozenBN")
 
-    def __init__(self, input_shape, num_fc, fc_dim, num_conv=0, norm=""):
+
+class TrackedFrozenBatchNorm2d(FrozenBatchNorm2d):
+    """The frozen norm under nn.BatchNorm2d's / nn.SyncBatchNorm's keys: the four buffers and ``num_batches_tracked`` (never read)."""
+
+    def __init__(self, num_features, eps=FROZEN_BN_EPS):
+        super().__init__(num_features, eps)
+        self.running_var.fill_(1.0)
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+
+def _check_norm(section, norm):
+    if norm not in HEAD_NORMS:
+        raise AfiError(f"roi_heads: MODEL.{section}.NORM {norm!r} is not supported ('', 'BN', 'SyncBN' or 'FrozenBN': a norm on its running "
+                       "statistics, folded into its conv)")
+
+
+def _head_norm(section, norm, channels):
+    _check_norm(section, norm)
+    return None if not norm else FrozenBatchNorm2d(channels) if norm == "FrozenBN" else TrackedFrozenBatchNorm2d(channels)
+
+
+def _head_conv(section, cin, cout, norm):
+    """detectron2's Conv2d(3x3, pad 1, bias = not norm) of a head, its norm the child ``norm``."""
+    conv = nn.Conv2d(cin, cout, 3, padding=1, bias=not norm)
+    if norm:
+        conv.norm = _head_norm(section, norm, cout)
+    return conv
+
+
+def _conv_tensors(conv):
+    """What a head conv's folded weight depends on: weight, bias and the norm's four tensors."""
+    n = getattr(conv, "norm", None)
+    return [t for t in (conv.weight, conv.bias) + ((n.weight, n.bias, n.running_mean, n.running_var) if n is not None else ()) if t is not None]
+
+
+class FastRCNNConvFCHead(nn.Module):
+    """detectron2's FastRCNNConvFCHead: ``fc1`` .. ``fc{NUM_FC}`` with ReLU; with convs=True (CascadeROIHeads) ``conv1`` .. ``conv{NUM_CONV}``
+    (3x3, norm, ReLU) in front of them."""
+
+    def __init__(self, input_shape, num_fc, fc_dim, num_conv=0, norm="", conv_dim=256, convs=False):
         super().__init__()
-        if num_conv != 0:
+        if num_conv != 0 and not convs:
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NUM_CONV {num_conv} is not supported (FC-only box head; the conv head is CascadeROIHeads' "
                            "and out of scope)")
-        if norm:
+        if norm and not convs:
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NORM {norm!r} is not supported (the FC-only box head has no norm)")
+        _check_norm("ROI_BOX_HEAD", norm)
+        if num_conv < 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NUM_CONV {num_conv} must be >= 0")
         if num_fc < 1:
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.NUM_FC {num_fc} must be >= 1")
         if fc_dim <= 0 or fc_dim % 4:
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.FC_DIM {fc_dim} must be a positive multiple of 4")
+        if convs and (conv_dim <= 0 or conv_dim % 4):
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.CONV_DIM {conv_dim} must be a positive multiple of 4")
         self.input_shape = tuple(int(s) for s in input_shape)          # (C, S, S)
-        self.fcs = []
-        dim = self.input_shape[0] * self.input_shape[1] * self.input_shape[2]
+        self.conv_norm_relus, self.fcs = [], []
+        dim = self.input_shape[0]
+        for k in range(num_conv):
+            conv = _head_conv("ROI_BOX_HEAD", dim, conv_dim, norm)
+            nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")          # detectron2's c2_msra_fill
+            if conv.bias is not None:
+                nn.init.constant_(conv.bias, 0)
+            self.add_module(f"conv{k + 1}", conv)
+            self.conv_norm_relus.append(conv)
+            dim = conv_dim
+        self.conv_output_shape = (dim, self.input_shape[1], self.input_shape[2])
+        dim = dim * self.input_shape[1] * self.input_shape[2]
         for k in range(num_fc):
             fc = nn.Linear(dim, fc_dim)
             nn.init.kaiming_uniform_(fc.weight, a=1)                   # detectron2's c2_xavier_fill
@@ -132,14 +197,15 @@ class FastRCNNOutputLayers(nn.Module):
 
 
 class MaskRCNNConvUpsampleHead(nn.Module):
-    """detectron2's MaskRCNNConvUpsampleHead without norm: ``mask_fcn1`` .. ``mask_fcn{NUM_CONV}`` (3x3, ReLU), ``deconv`` (ConvTranspose2d
-    kernel 2, stride 2, ReLU), ``predictor`` (1x1 to Km classes)."""
+    """detectron2's MaskRCNNConvUpsampleHead: ``mask_fcn1`` .. ``mask_fcn{NUM_CONV}`` (3x3, ReLU), ``deconv`` (ConvTranspose2d kernel 2,
+    stride 2, ReLU), ``predictor`` (1x1 to Km classes); without norm, or with norms=True (CascadeROIHeads) a norm in every ``mask_fcn``."""
 
-    def __init__(self, input_shape, num_classes, num_conv, conv_dim, norm="", cls_agnostic_mask=False):
+    def __init__(self, input_shape, num_classes, num_conv, conv_dim, norm="", cls_agnostic_mask=False, norms=False):
         super().__init__()
-        if norm:
+        if norm and not norms:
             raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.NORM {norm!r} is not supported (the mask head without norm only; the SyncBN head is "
                            "the Cascade configs' and out of scope)")
+        _check_norm("ROI_MASK_HEAD", norm)
         if num_conv < 0:
             raise AfiError(f"roi_heads: MODEL.ROI_MASK_HEAD.NUM_CONV {num_conv} must be >= 0")
         if conv_dim <= 0 or conv_dim % 4:
@@ -149,7 +215,7 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         self.conv_norm_relus = []
         dim = self.input_shape[0]
         for k in range(num_conv):
-            conv = nn.Conv2d(dim, conv_dim, 3, padding=1)
+            conv = _head_conv("ROI_MASK_HEAD", dim, conv_dim, norm)
             self.add_module(f"mask_fcn{k + 1}", conv)
             self.conv_norm_relus.append(conv)
             dim = conv_dim
@@ -157,7 +223,8 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         self.predictor = nn.Conv2d(conv_dim, self.num_mask_classes, 1)
         for l in self.conv_norm_relus + [self.deconv]:                 # detectron2's c2_msra_fill
             nn.init.kaiming_normal_(l.weight, mode="fan_out", nonlinearity="relu")
-            nn.init.constant_(l.bias, 0)
+            if l.bias is not None:
+                nn.init.constant_(l.bias, 0)
         nn.init.normal_(self.predictor.weight, std=0.001)
         nn.init.constant_(self.predictor.bias, 0)
 
@@ -221,16 +288,31 @@ def _pixels_as_rows(t):
     return t.permute(0, 2, 3, 1).reshape(t.shape[3], t.shape[1])
 
 
+def _reg_weights(key, w):
+    try:
+        out = tuple(float(v) for v in w)
+    except TypeError:
+        out = (w,)
+    if len(out) != 4 or not min(out) > 0:
+        raise AfiError(f"roi_heads: {key} {out} must be four positive numbers")
+    return out
+
+
 @ROI_HEADS_REGISTRY.register()
 class StandardROIHeads(nn.Module):
+    conv_norm_heads = False            # the conv box head and the normed mask head: CascadeROIHeads only
+
+    def _refuse_name(self, name):
+        return AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
+
     def __init__(self, cfg, input_shape, masks=False):
         super().__init__()
         m = cfg.MODEL
         rh, bh = cfg_get(m, "ROI_HEADS", None), cfg_get(m, "ROI_BOX_HEAD", None)
         if rh is None or bh is None:
             raise AfiError("roi_heads: the config has no MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD section (afigan_amd.config.get_cfg declares them)")
-        if cfg_get(rh, "NAME", "StandardROIHeads") != "StandardROIHeads":
-            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {rh.NAME!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
+        if cfg_get(rh, "NAME", "StandardROIHeads") != type(self).__name__:
+            raise self._refuse_name(rh.NAME)
         if masks and not cfg_get(m, "MASK_ON", False):
             raise AfiError("roi_heads: masks=True builds the mask branch and needs MODEL.MASK_ON True")
         if cfg_get(m, "MASK_ON", False) and not masks:
@@ -248,7 +330,7 @@ class StandardROIHeads(nn.Module):
         channels = {s.channels for s in shapes}
         if len(channels) != 1:
             raise AfiError(f"roi_heads: every feature of MODEL.ROI_HEADS.IN_FEATURES must have one channel count, got {sorted(channels)}")
-        C_ = channels.pop()
+        C_ = self.channels = channels.pop()
         if C_ % 4:
             raise AfiError(f"roi_heads: {C_} feature channels; a multiple of 4 is needed")
         self.num_classes = int(cfg_get(rh, "NUM_CLASSES", 80))
@@ -260,15 +342,9 @@ class StandardROIHeads(nn.Module):
         if not 0 < self.test_detections_per_img <= ROI_MAX_CANDIDATES:
             raise AfiError(f"roi_heads: TEST.DETECTIONS_PER_IMAGE {self.test_detections_per_img} is outside 1..{ROI_MAX_CANDIDATES}, the candidate "
                            "list the selection kernels hold")
-        self.box_weights = tuple(float(w) for w in cfg_get(bh, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0)))
-        if len(self.box_weights) != 4 or min(self.box_weights) <= 0:
-            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS {self.box_weights} must be four positive numbers")
         res = cfg_get(bh, "POOLER_RESOLUTION", 14)
         self.box_pooler = ROIPooler(res, [1.0 / s.stride for s in shapes], cfg_get(bh, "POOLER_SAMPLING_RATIO", 0), cfg_get(bh, "POOLER_TYPE", "ROIAlignV2"))
-        S = self.box_pooler.output_size
-        self.box_head = FastRCNNConvFCHead((C_, S, S), int(cfg_get(bh, "NUM_FC", 0)), int(cfg_get(bh, "FC_DIM", 1024)), int(cfg_get(bh, "NUM_CONV", 0)),
-                                           cfg_get(bh, "NORM", ""))
-        self.box_predictor = FastRCNNOutputLayers(self.box_head.output_size, self.num_classes, bool(cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
+        self._build_box_branch(cfg, bh)
         self.mask_on, self.keypoint_on = bool(masks), False
         if self.mask_on:
             mh = cfg_get(m, "ROI_MASK_HEAD", None)
@@ -280,19 +356,30 @@ class StandardROIHeads(nn.Module):
                                          cfg_get(mh, "POOLER_TYPE", "ROIAlignV2"), section="ROI_MASK_HEAD")
             Sm = self.mask_pooler.output_size
             self.mask_head = MaskRCNNConvUpsampleHead((C_, Sm, Sm), self.num_classes, int(cfg_get(mh, "NUM_CONV", 0)), int(cfg_get(mh, "CONV_DIM", 256)),
-                                                      cfg_get(mh, "NORM", ""), bool(cfg_get(mh, "CLS_AGNOSTIC_MASK", False)))
+                                                      cfg_get(mh, "NORM", ""), bool(cfg_get(mh, "CLS_AGNOSTIC_MASK", False)), norms=self.conv_norm_heads)
         for p in self.parameters():
             p.requires_grad_(False)
 
+    def _make_box_head(self, bh):
+        """One FastRCNNConvFCHead and its FastRCNNOutputLayers from MODEL.ROI_BOX_HEAD."""
+        S = self.box_pooler.output_size
+        head = FastRCNNConvFCHead((self.channels, S, S), int(cfg_get(bh, "NUM_FC", 0)), int(cfg_get(bh, "FC_DIM", 1024)), int(cfg_get(bh, "NUM_CONV", 0)),
+                                  cfg_get(bh, "NORM", ""), int(cfg_get(bh, "CONV_DIM", 256)), convs=self.conv_norm_heads)
+        return head, FastRCNNOutputLayers(head.output_size, self.num_classes, bool(cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False)))
+
+    def _build_box_branch(self, cfg, bh):
+        self.box_weights = _reg_weights("MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS", cfg_get(bh, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0)))
+        self.box_head, self.box_predictor = self._make_box_head(bh)
+
     # ------------------------------------------------------------------ weights in the kernels' layout
-    def _prepare(self):
-        """(fc1's weight in [out][S][S][C] order, the predictor's two layers as one [Cpad, D] weight and [Cpad] bias), rebuilt when a parameter
-        changes."""
-        fc1, pr = self.box_head.fcs[0], self.box_predictor
+    def _prepare_head(self, head, pr, name):
+        """(fc1's weight in [out][S][S][C] order, the predictor's two layers as one [Cpad, D] weight and [Cpad] bias), kept in the slot `name` and
+        rebuilt when a parameter changes."""
+        fc1 = head.fcs[0]
         ts = [fc1.weight, pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias]
 
         def build():
-            C_, S, _ = self.box_head.input_shape
+            C_, S, _ = head.conv_output_shape
             out = fc1.weight.shape[0]
             w1 = fc1.weight.detach().float().view(out, C_, S, S).permute(0, 2, 3, 1).reshape(out, S * S * C_).contiguous()
             nc, nb = pr.cls_score.weight.shape[0], pr.bbox_pred.weight.shape[0]
@@ -302,16 +389,25 @@ class StandardROIHeads(nn.Module):
             w[:nc], w[nc:nc + nb] = ts[1].detach(), ts[3].detach()
             b[:nc], b[nc:nc + nb] = ts[2].detach(), ts[4].detach()
             return w1, w, b
-        return prepared(self, "prep", ts, build)
+        return prepared(self, name, ts, build)
+
+    def _prepare_convs(self, head, name):
+        """[every conv's (weight in [O][kh][kw][I] memory, bias), its norm folded in (fp64, rounded once)], rebuilt when the conv's weight or
+        bias or one of the norm's four tensors changes."""
+        ts = [t for l in head.conv_norm_relus for t in _conv_tensors(l)]
+        return prepared(self, name, ts, lambda: [fold_conv(l, getattr(l, "norm", None)) for l in head.conv_norm_relus])
+
+    def _prepare(self):
+        return self._prepare_head(self.box_head, self.box_predictor, "prep")
 
     def _prepare_mask(self):
         """([(3x3 weight in [O][kh][kw][I] memory, bias)], (deconv as a [4 Cout, Cin] 1x1 weight, its bias four times), (predictor [Km, C],
         bias)), rebuilt when a parameter changes."""
         mh = self.mask_head
-        ts = [t for l in mh.conv_norm_relus + [mh.deconv, mh.predictor] for t in (l.weight, l.bias)]
+        ts = [t for l in mh.conv_norm_relus + [mh.deconv, mh.predictor] for t in _conv_tensors(l)]
 
         def build():
-            convs = [(ops.to_ohwi(l.weight.detach().float()), l.bias.detach().float().contiguous()) for l in mh.conv_norm_relus]
+            convs = [fold_conv(l, getattr(l, "norm", None)) for l in mh.conv_norm_relus]
             pw = mh.predictor.weight.detach().float().reshape(mh.num_mask_classes, -1).contiguous()
             return convs, deconv_as_conv1x1(mh.deconv.weight, mh.deconv.bias), (pw, mh.predictor.bias.detach().float().contiguous())
         return prepared(self, "mask_prep", ts, build)
@@ -325,7 +421,7 @@ class StandardROIHeads(nn.Module):
         if missing:
             raise AfiError(f"roi_heads: features {missing} are missing (got {sorted(features)})")
         xs = [features[f] for f in self.in_features]
-        C_ = self.box_head.input_shape[0]
+        C_ = self.channels
         for f, x in zip(self.in_features, xs):
             _check_feature("roi_heads", f"feature {f}", x)
             if x.dim() != 4 or x.shape[1] != C_ or x.shape[0] != xs[0].shape[0]:
@@ -351,20 +447,34 @@ class StandardROIHeads(nn.Module):
     def box_head_forward(self, pooled, intermediates=False):
         """pooled [R, C, S, S] pixel-major -> the predictor's output [R, Cpad] (K + 1 logits, the deltas, zero padding); intermediates: the list
         of every FC's output [R, FC_DIM] as well."""
-        w1, wp, bp = self._prepare()
-        R = pooled.shape[0]
-        x = _rows_as_pixels(pooled.permute(0, 2, 3, 1).reshape(R, -1))
-        acts = []
-        for k, fc in enumerate(self.box_head.fcs):
+        pred, _, acts = self._run_head(self.box_head, [], self._prepare(), pooled)
+        return (pred, acts) if intermediates else pred
+
+    @staticmethod
+    def _run_head(head, convs, prep, pooled):
+        """One box head and its predictor on pooled [R, C, S, S]: (pred [R, Cpad], every conv's output [R, CONV_DIM, S, S], every FC's [R, FC_DIM]);
+        fc1 reads the last conv's (or the pooler's) pixel-major memory in place."""
+        w1, wp, bp = prep
+        x, cacts, acts = pooled, [], []
+        for wb in convs:
+            x = conv3x3(x, wb, relu=True)
+            cacts.append(x)
+        if not ops.is_dense_pm(x):
+            raise AfiError("roi_heads: the box head reads dense pixel-major features")
+        x = _rows_as_pixels(x.permute(0, 2, 3, 1).reshape(x.shape[0], -1))
+        for k, fc in enumerate(head.fcs):
             x = ops.conv1x1_fwd(x, w1 if k == 0 else fc.weight.detach(), fc.bias.detach(), act=2)
             acts.append(_pixels_as_rows(x))
-        pred = _pixels_as_rows(ops.conv1x1_fwd(x, wp, bp))
-        return (pred, acts) if intermediates else pred
+        return _pixels_as_rows(ops.conv1x1_fwd(x, wp, bp)), cacts, acts
 
     def select(self, pred, boxes, counts, image_hw):
         """scores and boxes, candidates, NMS, pick on the predictor's output; returns every stage's output in a dict."""
         pr = self.box_predictor
         scores, cboxes = ops.roi_scores_boxes(pred, pr.num_classes, pr.cls_agnostic_bbox_reg, boxes, counts, image_hw, self.box_weights, SCALE_CLAMP)
+        return self._pick(scores, cboxes)
+
+    def _pick(self, scores, cboxes):
+        """fast_rcnn_inference on scores [N, P, K] and boxes [N, P, K or 1, 4]: candidates, NMS, pick."""
         cand = ops.roi_candidates(scores, cboxes, self.test_score_thresh, ROI_MAX_CANDIDATES)
         keep = ops.roi_nms(cand["boxes"], cand["cls"], cand["valid"], self.test_nms_thresh)
         ob, os_, oc, oc_n, trunc = ops.roi_pick(cand, keep, self.test_detections_per_img)
@@ -395,6 +505,14 @@ class StandardROIHeads(nn.Module):
         probs = probs.view(N, D, probs.shape[1], probs.shape[2])
         return (probs, acts, h) if intermediates else probs
 
+    def _box_branch(self, xs, boxes, counts, image_hw, intermediates):
+        """Pooler, head, predictor and selection on the padded proposals: ``select``'s dict plus ``pooled``, ``fc`` and ``pred``."""
+        pooled = self.box_pooler(xs, boxes, counts)
+        pred, acts = self.box_head_forward(pooled, intermediates=True)
+        r = self.select(pred, boxes, counts, image_hw)
+        r.update(pooled=pooled, fc=acts, pred=pred)
+        return r
+
     def _mask_branch(self, xs, boxes, classes, counts, r=None):
         pooled = self.mask_pooler(xs, boxes, counts)
         probs, acts, h = self.mask_head_forward(pooled, classes, counts, intermediates=True)
@@ -415,12 +533,9 @@ class StandardROIHeads(nn.Module):
             raise AfiError(f"roi_heads: image sizes of shape {tuple(image_sizes.shape)} for a batch of {xs[0].shape[0]}")
         with torch.no_grad():
             boxes, counts = boxes.contiguous(), counts.contiguous()
-            pooled = self.box_pooler(xs, boxes, counts)
-            pred, acts = self.box_head_forward(pooled, intermediates=True)
-            r = self.select(pred, boxes, counts, image_sizes.to(torch.float32).contiguous())
+            r = self._box_branch(xs, boxes, counts, image_sizes.to(torch.float32).contiguous(), intermediates)
             masks = self._mask_branch(xs, r["boxes"], r["classes"], r["counts"], r) if self.mask_on else None
         if intermediates:
-            r.update(pooled=pooled, fc=acts, pred=pred)
             return r
         out = (r["boxes"], r["scores"], r["classes"], r["counts"], r["truncated"])
         return out + (masks,) if self.mask_on else out
@@ -495,11 +610,85 @@ class StandardROIHeads(nn.Module):
         return instances
 
 
-def build_roi_heads(cfg, input_shape, masks=False):
+@ROI_HEADS_REGISTRY.register()
+class CascadeROIHeads(StandardROIHeads):
+    """detectron2 v0.1.1's CascadeROIHeads at inference (the module docstring's last part): StandardROIHeads' checks, pooler, selection, mask
+    branch, ``forward`` and ``forward_with_given_boxes``; ``box_head`` / ``box_predictor`` are ModuleLists of one head per stage."""
+    conv_norm_heads = True
+    MAX_STAGES = 8
+
+    def _refuse_name(self, name):
+        return AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not 'CascadeROIHeads', the class that was asked for")
+
+    def _build_box_branch(self, cfg, bh):
+        ch = cfg_get(cfg.MODEL, "ROI_BOX_CASCADE_HEAD", None)
+        if ch is None:
+            raise AfiError("roi_heads: the config has no MODEL.ROI_BOX_CASCADE_HEAD section (afigan_amd.config.get_cfg declares it)")
+        ious, weights = tuple(cfg_get(ch, "IOUS", ())), tuple(cfg_get(ch, "BBOX_REG_WEIGHTS", ()))
+        if len(ious) != len(weights):
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_CASCADE_HEAD.IOUS has {len(ious)} entries and MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS "
+                           f"{len(weights)}: one of each per stage")
+        if not 1 <= len(ious) <= self.MAX_STAGES:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_CASCADE_HEAD.IOUS gives {len(ious)} stages; 1..{self.MAX_STAGES} are supported")
+        first = list(cfg_get(cfg.MODEL.ROI_HEADS, "IOU_THRESHOLDS", [0.5]))[0]
+        if float(ious[0]) != float(first):
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_CASCADE_HEAD.IOUS[0] {ious[0]} must equal MODEL.ROI_HEADS.IOU_THRESHOLDS[0] {first} (detectron2 "
+                           "asserts it)")
+        self.num_stages = len(ious)
+        self.stage_weights = tuple(_reg_weights(f"MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS[{k}]", w) for k, w in enumerate(weights))
+        if not cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False):
+            raise AfiError("roi_heads: MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False is not supported by CascadeROIHeads (detectron2 asserts "
+                           "class-agnostic box regression)")
+        heads = [self._make_box_head(bh) for _ in range(self.num_stages)]
+        self.box_head = nn.ModuleList([h for h, _ in heads])
+        self.box_predictor = nn.ModuleList([p for _, p in heads])
+
+    def _prepare(self, stage=0):
+        """Stage `stage`'s (folded convs, (fc1's weight, the predictor's weight and bias))."""
+        return (self._prepare_convs(self.box_head[stage], f"prep_convs{stage}"),
+                self._prepare_head(self.box_head[stage], self.box_predictor[stage], f"prep{stage}"))
+
+    def box_head_forward(self, pooled, stage=0, intermediates=False):
+        """pooled [R, C, S, S] pixel-major -> stage `stage`'s predictor output [R, Cpad] (K + 1 logits, 4 deltas, zero padding); intermediates:
+        also (every conv's output [R, CONV_DIM, S, S], every FC's output [R, FC_DIM])."""
+        pred, cacts, acts = self._run_head(self.box_head[stage], *self._prepare(stage), pooled)
+        return (pred, cacts, acts) if intermediates else pred
+
+    def select(self, pred, boxes, counts, image_hw):
+        raise AfiError("roi_heads: CascadeROIHeads decodes stage by stage (forward_padded); there is no selection on one predictor output")
+
+    def _box_branch(self, xs, boxes, counts, image_hw, intermediates):
+        """The S stages and the selection: ``_pick``'s dict, ``class_scores`` the mean scores, ``class_boxes`` the last stage's boxes [N, P, 1, 4],
+        ``pooled`` / ``fc`` / ``pred`` the last stage's; intermediates: ``stages``, per stage ``proposals``, ``pooled``, ``convs``, ``fc``, ``pred``,
+        ``scores`` (the running score after it) and ``boxes``.  Without intermediates the running score is one buffer, updated in place."""
+        N, P = boxes.shape[:2]
+        scores, cur, stages = None, boxes, []
+        for k in range(self.num_stages):
+            pooled = self.box_pooler(xs, cur, counts)
+            pred, cacts, acts = self.box_head_forward(pooled, k, intermediates=True)
+            last = k == self.num_stages - 1
+            scores, nxt = ops.roi_cascade_stage(pred, self.num_classes, cur, counts, image_hw, self.stage_weights[k], prev_scores=scores,
+                                                out_scale=1.0 / self.num_stages if last else 1.0, scale_clamp=SCALE_CLAMP,
+                                                out=None if intermediates else scores)
+            if intermediates:
+                stages.append({"proposals": cur, "pooled": pooled, "convs": cacts, "fc": acts, "pred": pred, "scores": scores, "boxes": nxt})
+            cur = nxt
+        r = self._pick(scores, cur.view(N, P, 1, 4))
+        r.update(pooled=pooled, fc=acts, pred=pred)
+        if intermediates:
+            r["stages"] = stages
+        return r
+
+
+def build_roi_heads(cfg, input_shape, masks=False, cascade=False):
     """detectron2's build_roi_heads: the class registered under MODEL.ROI_HEADS.NAME.  masks=True builds the mask branch as well (it needs
-    MODEL.MASK_ON True); without it a MASK_ON config is refused."""
+    MODEL.MASK_ON True); without it a MASK_ON config is refused.  cascade=True builds 'CascadeROIHeads' (the NAME must say so); without it a
+    Cascade config is refused."""
     name = cfg_get(cfg_get(cfg.MODEL, "ROI_HEADS", None), "NAME", "StandardROIHeads")
-    if name != "StandardROIHeads":
-        raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (this package provides the box branch of 'StandardROIHeads')")
+    if cascade and name != "CascadeROIHeads":
+        raise AfiError(f"roi_heads: cascade=True builds 'CascadeROIHeads' and needs MODEL.ROI_HEADS.NAME 'CascadeROIHeads', got {name!r}")
+    if not cascade and name != "StandardROIHeads":
+        raise AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (this package provides the box branch of 'StandardROIHeads')"
+                       + ("; 'CascadeROIHeads' is built with build_roi_heads(cfg, input_shape, cascade=True)" if name == "CascadeROIHeads" else ""))
     cls = ROI_HEADS_REGISTRY.get(name)
     return cls(cfg, input_shape, masks=True) if masks else cls(cfg, input_shape)

@@ -628,6 +628,11 @@ int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N,
  *   deltas.  scores [N][P][K] = softmax over the K + 1 logits without the background column, boxes [N][P][Kb][4] (Kb = K, or 1 when agnostic) =
  *   clip(Box2BoxTransform(wx, wy, ww, wh).apply_deltas(proposal), dw / dh clamped from above at scale_clamp), both evaluated in fp64 from the
  *   fp32 inputs and rounded once; no size test.  Rows j >= counts[n]: scores -inf, boxes zero.  A row with a NaN logit scores NaN.  K <= 1024.
+ * afi_roi_cascade_stage: one stage of CascadeROIHeads.  s and boxes [N][P][4] are afi_roi_scores_boxes' with agnostic = 1, bit for bit (s = -inf
+ *   past counts[n], NaN for a row with a NaN logit).  scores [N][P][K] = prev_scores ? prev_scores + s : s, then, when out_scale != 1, that times
+ *   out_scale: one fp32 operation each, never contracted.  prev_scores NULL: the first stage.  scores may be prev_scores itself (a lane reads its
+ *   element before it writes it).  Rows past counts stay -inf for every prev_scores below +inf, NaN rows stay NaN; boxes are the clipped decode,
+ *   the next stage's proposals and the last stage's detection boxes.  0 < out_scale < inf.  ld_pred >= K + 5.
  * afi_roi_candidates: the m = min(M, P K) highest scores of image n by (score descending, index r K + c ascending), NaN below every number:
  *   cand_scores / cand_idx / cand_cls / cand_valid [N][M], cand_boxes [N][M][4]; valid = score > score_thresh; entries m.. are (-inf, -1, -1, 0,
  *   zero box).  n_over[n] = the count of ALL scores of image n above score_thresh.  M <= 1024, P K < 2^22 - 1.  ws:
@@ -642,6 +647,9 @@ int afi_roi_align(const afi_view_t* levels, const int* level_hw, int L, int min_
 int afi_roi_scores_boxes(const float* pred, long long ld_pred, int N, int P, int K, int agnostic, const float* proposals, const int* counts,
                          const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, float* scores, float* boxes,
                          void* stream);
+int afi_roi_cascade_stage(const float* pred, long long ld_pred, int N, int P, int K, const float* proposals, const int* counts,
+                          const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, const float* prev_scores,
+                          float out_scale, float* scores, float* boxes, void* stream);
 long long afi_roi_candidates_ws_floats(int N, int P, int K);
 int afi_roi_candidates(const float* scores, const float* boxes, int N, int P, int K, int agnostic, float score_thresh, int M, float* cand_scores,
                        int* cand_idx, float* cand_boxes, int* cand_cls, int* cand_valid, int* n_over, float* ws, long long ws_floats,
