@@ -1159,6 +1159,44 @@ def mask_paste(probs, boxes, hw, threshold=0.5, out=None):
     return out.view(torch.bool)
 
 
+def mask_paste_rle(probs, boxes, hw, threshold=0.5, ws=None):
+    """mask_paste's masks as COCO run-length starts, without the image-size masks: (starts int32 [T] on the GPU, detection after detection,
+    ascending; nstarts int64 [R] on the CPU).  A mask is read column-major (j = x H + y) and a start is a j whose pixel differs from pixel
+    j - 1; rle.counts_from_starts turns them into counts.  The pixels are mask_paste's, bit for bit; a box with a non-finite coordinate gives
+    an empty mask.  Count, ONE host read of the R counts, their running sum, emit (afi_mask_rle_count, afi_mask_rle_emit).  ws: a dense GPU
+    buffer of at least afi_mask_rle_ws_bytes(R, H, W) bytes to use instead of a fresh workspace."""
+    _check_cuda(probs, boxes)
+    H, W = int(hw[0]), int(hw[1])
+    if probs.dim() != 3 or probs.shape[1] != probs.shape[2] or tuple(boxes.shape) != (probs.shape[0], 4) or H <= 0 or W <= 0:
+        raise _lib.AfiError(f"mask_paste_rle: probs [R, M, M], boxes [R, 4] and a positive output size expected, got {tuple(probs.shape)}, "
+                            f"{tuple(boxes.shape)}, {(H, W)}")
+    R, M = probs.shape[:2]
+    if not 0 < M <= MASK_MAX_SIDE:
+        raise _lib.AfiError(f"mask_paste_rle: mask side {M} (1..{MASK_MAX_SIDE})")
+    dev = probs.device
+    if R == 0:
+        return torch.empty((0,), device=dev, dtype=torch.int32), torch.zeros((0,), dtype=torch.int64)
+    n = _lib.load().afi_mask_rle_ws_bytes(R, H, W)
+    if n < 0:
+        raise _lib.AfiError(f"mask_paste_rle: unsupported output size {H} x {W} (H W < 2^31)")
+    if ws is None:
+        ws = new_workspace((n + 3) // 4, dev)
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < n:
+        raise _lib.AfiError(f"mask_paste_rle: ws must be a dense GPU buffer of at least {n} bytes")
+    wsb = ws.numel() * ws.element_size()
+    boxes = boxes.contiguous()
+    nst = torch.empty((R,), device=dev, dtype=torch.int32)
+    call("afi_mask_rle_count", _p(probs.contiguous()), _p(boxes), R, M, H, W, float(threshold), _p(ws), wsb, _p(nst), stream_ptr())
+    nstarts = nst.cpu().to(torch.int64)                     # the one host read
+    ends = torch.cumsum(nstarts, 0)
+    total = int(ends[-1])
+    starts = torch.empty((total,), device=dev, dtype=torch.int32)
+    if total:
+        offsets = (ends - nstarts).to(dev)
+        call("afi_mask_rle_emit", _p(boxes), R, H, W, _p(ws), wsb, _p(offsets), _p(starts), stream_ptr())
+    return starts, nstarts
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

@@ -94,10 +94,15 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
         losses.update(proposal_losses)
         return losses, processed_results                                               # :67-70
 
-    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
+    def inference(self, batched_inputs, detected_instances=None, do_postprocess=True, mask_format="bitmask"):
         """rcnn_extractor.py:72-118: features -> proposals -> ROI-head predictions, then (do_postprocess) each image's instances rescaled
-        to the input's "height" / "width" and wrapped as ``{"instances": r}`` -- the contract evaluators are written against."""
+        to the input's "height" / "width" and wrapped as ``{"instances": r}`` -- the contract evaluators are written against.
+        mask_format "rle": the postprocess is this package's own, and the instances carry ``pred_masks_rle`` (a list of COCO RLE dicts at
+        the output size, roi_heads.paste_masks_rle) instead of the image-size bool ``pred_masks``, which are never formed."""
         assert not self.training
+        if mask_format not in ("bitmask", "rle"):
+            from ._lib import AfiError
+            raise AfiError(f"inference: mask_format must be 'bitmask' or 'rle', got {mask_format!r}")
         images = self.preprocess_image(batched_inputs)
         features = self.backbone(images.tensor)
         if detected_instances is None:
@@ -111,20 +116,24 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
             detected_instances = [x.to(self.device) if hasattr(x, "to") else x for x in detected_instances]        # :101
             results = self.roi_heads.forward_with_given_boxes(features, detected_instances)
         if do_postprocess:
-            return self._postprocess(results, batched_inputs, images.image_sizes)                                   # :106-107
+            return self._postprocess(results, batched_inputs, images.image_sizes, mask_format)                      # :106-107
         return results
 
     @staticmethod
-    def _postprocess(instances, batched_inputs, image_sizes):
+    def _postprocess(instances, batched_inputs, image_sizes, mask_format="bitmask"):
         """rcnn_extractor.py:129-143: ``detector_postprocess(results, height, width)`` per image.  detectron2's own function when it is
         importable; otherwise its box part (scale by output / network size, clip, drop empty boxes: detectron2 v0.1.1
         modeling/postprocessing.py) on anything that carries ``image_size`` and ``pred_boxes``, then ``pred_masks`` pasted at the output
         size into the scaled boxes (roi_heads.paste_masks_in_image, GPU only) -- and a loud error for the instance field this package cannot
         rescale without detectron2 (keypoints) rather than a silently wrong scale."""
-        try:
-            from detectron2.modeling.postprocessing import detector_postprocess
-        except Exception:
-            detector_postprocess = _detector_postprocess_boxes
+        if mask_format == "rle":                        # detectron2's function knows only the bitmask
+            def detector_postprocess(r, h, w):
+                return _detector_postprocess_boxes(r, h, w, mask_format="rle")
+        else:
+            try:
+                from detectron2.modeling.postprocessing import detector_postprocess
+            except Exception:
+                detector_postprocess = _detector_postprocess_boxes
         out = []
         for results_per_image, input_per_image, image_size in zip(instances, batched_inputs, image_sizes):
             height = input_per_image.get("height", image_size[0])
@@ -133,9 +142,11 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
         return out
 
 
-def _detector_postprocess_boxes(results, output_height, output_width):
+def _detector_postprocess_boxes(results, output_height, output_width, mask_format="bitmask"):
     import copy
     from ._lib import AfiError
+    if mask_format not in ("bitmask", "rle"):
+        raise AfiError(f"mask_format must be 'bitmask' or 'rle', got {mask_format!r}")
     if getattr(results, "pred_keypoints", None) is not None:
         raise AfiError("rescaling `pred_keypoints` to the input size needs detectron2's detector_postprocess (not importable here); "
                        "call inference(..., do_postprocess=False) for raw ROI-head results")
@@ -145,17 +156,26 @@ def _detector_postprocess_boxes(results, output_height, output_width):
                        "inference(..., do_postprocess=False) for raw ROI-head results")
     h, w = results.image_size
     sx, sy = output_width / w, output_height / h
-    r = copy.copy(results)
+    # detectron2's Instances (reached under mask_format "rle" only): image_size is read-only and every field has one length, so the result is
+    # a new object that receives the kept rows of every field; anything else is shallow-copied, as before
+    inst = hasattr(results, "get_fields") and hasattr(results, "_image_size")
+    if inst:
+        r = type(results)((output_height, output_width))
+    else:
+        r = copy.copy(results)
+        r.image_size = (output_height, output_width)
     boxes = getattr(results, "pred_boxes", None)
     if boxes is None:
         boxes = getattr(results, "proposal_boxes", None)
         name = "proposal_boxes"
     else:
         name = "pred_boxes"
-    r.image_size = (output_height, output_width)
     if boxes is None:
         if masks is not None:
             raise AfiError("`pred_masks` without `pred_boxes` to paste them into")
+        if inst:
+            for f, v in results.get_fields().items():
+                r.set(f, v)
         return r
     t = (boxes.tensor if hasattr(boxes, "tensor") else boxes).clone()
     t[:, 0::2] *= sx
@@ -169,13 +189,23 @@ def _detector_postprocess_boxes(results, output_height, output_width):
         setattr(r, name, nb)
     else:
         setattr(r, name, t[keep])
-    for f in ("scores", "pred_classes", "objectness_logits"):
-        v = getattr(results, f, None)
-        if v is not None and hasattr(v, "__getitem__") and len(v) == len(keep):
-            setattr(r, f, v[keep])
+    if inst:
+        for f, v in results.get_fields().items():
+            if f not in (name, "pred_masks"):
+                r.set(f, v[keep])
+    else:
+        for f in ("scores", "pred_classes", "objectness_logits"):
+            v = getattr(results, f, None)
+            if v is not None and hasattr(v, "__getitem__") and len(v) == len(keep):
+                setattr(r, f, v[keep])
     if masks is not None:
         if name != "pred_boxes" or len(masks) != len(keep):
             raise AfiError(f"`pred_masks` of {len(masks)} rows without as many `pred_boxes` to paste them into")
-        from .roi_heads import paste_masks_in_image
-        r.pred_masks = paste_masks_in_image(masks[keep], t[keep], (int(output_height), int(output_width)), threshold=0.5)
+        from .roi_heads import paste_masks_in_image, paste_masks_rle
+        if mask_format == "rle":
+            r.pred_masks_rle = paste_masks_rle(masks[keep], t[keep], (int(output_height), int(output_width)), threshold=0.5)
+            if not inst:
+                r.pred_masks = None
+        else:
+            r.pred_masks = paste_masks_in_image(masks[keep], t[keep], (int(output_height), int(output_width)), threshold=0.5)
     return r

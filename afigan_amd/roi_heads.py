@@ -37,6 +37,8 @@ as before), on the box branch's padded detections boxes [N, D, 4], classes [N, D
   - ``predictor`` (1x1 to Km = NUM_CLASSES, or 1 under CLS_AGNOSTIC_MASK) for the row's own class only, sigmoid in fp64 rounded once:
     afi_roi_mask_probs -> masks [N, D, 2S, 2S], rows past counts zero.  ``forward`` stores them as ``pred_masks`` [n, 1, 2S, 2S];
   - ``paste_masks_in_image`` (afi_mask_paste) pastes them into image-size bool masks; the extractor's postprocess calls it.
+  - ``paste_masks_rle`` (afi_mask_rle_count / afi_mask_rle_emit) gives the same masks as COCO RLEs without ever forming them: the postprocess
+    under ``inference(..., mask_format="rle")``; ``instances_to_coco_json`` is the evaluator's step on either form.
 Keys: ``mask_head.{mask_fcn{i}, deconv, predictor}.{weight, bias}`` -- detectron2's.
 
 ``CascadeROIHeads`` (detectron2 v0.1.1's cascade_rcnn.py at inference): S = len(MODEL.ROI_BOX_CASCADE_HEAD.IOUS) stages on ONE box pooler, every
@@ -55,7 +57,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, rle
 from ._lib import AfiError
 from .frozen import FROZEN_BN_EPS, FrozenBatchNorm2d, cfg_get, check_feature, conv3x3, fold_conv, prepared
 from .registry import detectron2_or_local
@@ -238,18 +240,19 @@ def deconv_as_conv1x1(weight, bias):
 
 class Detections:
     """One image's detections when detectron2's Instances is not importable: ``image_size``, ``pred_boxes``, ``scores``, ``pred_classes`` and,
-    from the mask branch, ``pred_masks`` (else None)."""
+    from the mask branch, ``pred_masks`` (else None) or, at the extractor's ``mask_format="rle"``, ``pred_masks_rle``."""
 
-    def __init__(self, image_size, pred_boxes, scores, pred_classes, pred_masks=None):
+    def __init__(self, image_size, pred_boxes, scores, pred_classes, pred_masks=None, pred_masks_rle=None):
         self.image_size, self.pred_boxes, self.scores, self.pred_classes = image_size, pred_boxes, scores, pred_classes
         self.pred_masks = pred_masks
+        self.pred_masks_rle = pred_masks_rle             # a list of COCO RLE dicts (host data) from inference(..., mask_format="rle")
 
     def __len__(self):
         return len(self.pred_boxes)
 
     def to(self, device):
         return Detections(self.image_size, self.pred_boxes.to(device), self.scores.to(device), self.pred_classes.to(device),
-                          self.pred_masks.to(device) if self.pred_masks is not None else None)
+                          self.pred_masks.to(device) if self.pred_masks is not None else None, self.pred_masks_rle)
 
 
 def _make_detections(image_size, boxes, scores, classes, masks=None):
@@ -275,6 +278,58 @@ def paste_masks_in_image(masks, boxes, image_shape, threshold=0.5):
     if masks.dim() == 4 and masks.shape[1] == 1:
         masks = masks[:, 0]
     return ops.mask_paste(masks, boxes.reshape(-1, 4), image_shape, threshold)
+
+
+def paste_masks_rle(masks, boxes, image_shape, threshold=0.5):
+    """paste_masks_in_image's masks as COCO RLEs, without the image-size masks: a list of R ``{"size": [H, W], "counts": str}``, what
+    pycocotools' ``encode`` gives for each pasted mask (afi_mask_rle_count / afi_mask_rle_emit find the runs on the GPU from the pixels inside
+    each box; the host only turns the run starts into strings: rle.py).  Same inputs as paste_masks_in_image, same refusals."""
+    boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
+    if not torch.is_tensor(masks) or not torch.is_tensor(boxes) or not masks.is_cuda or not boxes.is_cuda:
+        raise AfiError("paste_masks_rle: masks and boxes must be GPU tensors; the paste runs on the GPU only, there is no CPU fallback")
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    hw = (int(image_shape[0]), int(image_shape[1]))
+    starts, nstarts = ops.mask_paste_rle(masks, boxes.reshape(-1, 4), hw, threshold)
+    strings = rle.to_strings(rle.counts_from_starts(starts.cpu().numpy(), nstarts.numpy(), hw))
+    return [{"size": [hw[0], hw[1]], "counts": s} for s in strings]
+
+
+def instances_to_coco_json(instances, img_id):
+    """One image's detections (``Detections`` or detectron2 ``Instances``, postprocessed) as COCO result dicts, the reference evaluator's
+    function: ``image_id``, ``category_id``, ``bbox`` (XYWH), ``score`` and, with masks, ``segmentation`` = an RLE with a str ``counts`` --
+    ``pred_masks_rle`` as it is when present (inference(..., mask_format="rle")), else bool ``pred_masks`` copied to the host and encoded there
+    one mask at a time (rle.encode: the slow path, kept for parity).  Keypoints are refused."""
+    def field(name):
+        if hasattr(instances, "has") and hasattr(instances, "get"):       # detectron2's Instances
+            return instances.get(name) if instances.has(name) else None
+        return getattr(instances, name, None)
+    n = len(instances)
+    if n == 0:
+        return []
+    if field("pred_keypoints") is not None:
+        raise AfiError("instances_to_coco_json: `pred_keypoints` are not supported (the keypoint branch is out of scope)")
+    boxes = field("pred_boxes")
+    b = (boxes.tensor if hasattr(boxes, "tensor") else boxes).detach().cpu().double()
+    xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).tolist()
+    scores, classes = field("scores").tolist(), field("pred_classes").tolist()
+    segs = field("pred_masks_rle")
+    if segs is None and field("pred_masks") is not None:
+        m = field("pred_masks")
+        if m.dim() != 3 or m.dtype != torch.bool:
+            raise AfiError(f"instances_to_coco_json: bool `pred_masks` [n, H, W] expected (postprocessed instances), got {m.dtype} "
+                           f"{tuple(m.shape)}")
+        m = m.cpu().numpy()
+        segs = [rle.to_rle(rle.encode(x), x.shape) for x in m]
+    if segs is not None and len(segs) != n:
+        raise AfiError(f"instances_to_coco_json: {len(segs)} masks for {n} instances")
+    out = []
+    for k in range(n):
+        d = {"image_id": img_id, "category_id": classes[k], "bbox": xywh[k], "score": scores[k]}
+        if segs is not None:
+            d["segmentation"] = segs[k]
+        out.append(d)
+    return out
 
 
 def _rows_as_pixels(t2d):

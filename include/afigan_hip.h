@@ -679,6 +679,25 @@ int afi_roi_mask_probs(const float* h, const float* w, const float* bias, const 
                        float* probs, void* stream);
 int afi_mask_paste(const float* probs, const float* boxes, int R, int M, int H, int W, float threshold, unsigned char* out, void* stream);
 
+/* ------------------------------------------------------------------ pasted masks as COCO run-length starts (csrc/mask_rle.hip)
+ * The mask afi_mask_paste would write, pixel for pixel (the same inside test, fp64 coordinate steps, fp32-rounded weights, fmaf order and
+ * `>= threshold`), as the starts of its runs and without the image-size mask: only pixels inside a box are formed.  A mask [H][W] is read in
+ * column-major order, j = x H + y, f[-1] = 0; a start is a j with f[j] != f[j - 1].  With the starts B_0 < ... < B_{m-1} of a detection, COCO's
+ * counts are [B_0, B_1 - B_0, ..., H W - B_{m-1}] ([H W] for an empty mask).  A box with a non-positive or NaN side gives an empty mask, as in
+ * afi_mask_paste; so does, by definition here, a box with a non-finite coordinate.
+ * afi_mask_rle_ws_bytes: the workspace of one call pair: bits [R][ceil(H / 64)][W] (uint64, bit b of word k = row 64 k + b) and the per-column
+ *   start counts [R][W] (int32); -1 for an unsupported shape.  Only the words and columns of each box's pixel extent are written and read.
+ * afi_mask_rle_count: nstarts [R] (int32, device) = the number of starts of every detection; fills ws.
+ * afi_mask_rle_emit: after the caller turned nstarts into exclusive offsets [R] (long long, device, in elements of starts): the starts of
+ *   detection r, ascending, at starts[offsets[r] ..] (int32).  ws: unchanged since afi_mask_rle_count with the same boxes, R, H, W.
+ * M <= 64, H W < 2^31, H <= 2097120; ws and offsets 8-byte aligned.  R = 0 is accepted and launches nothing.  No atomics, no host
+ * synchronisation; bit-identical between runs. */
+long long afi_mask_rle_ws_bytes(int R, int H, int W);
+int afi_mask_rle_count(const float* probs, const float* boxes, int R, int M, int H, int W, float threshold, void* ws, long long ws_bytes,
+                       int* nstarts, void* stream);
+int afi_mask_rle_emit(const float* boxes, int R, int H, int W, const void* ws, long long ws_bytes, const long long* offsets, int* starts,
+                      void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
