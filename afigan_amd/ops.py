@@ -1197,6 +1197,93 @@ def mask_paste_rle(probs, boxes, hw, threshold=0.5, ws=None):
     return starts, nstarts
 
 
+# ------------------------------------------------------------------------------------------------ COCO evaluation (coco_eval.py)
+def _coco_arg(name, t, dtype, numel=None):
+    """A dense GPU tensor of `dtype` (and, when given, of `numel` elements); an empty one becomes one zero element, so that no pointer is null."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.AfiError(f"coco: `{name}` must be a GPU tensor (the evaluation kernels run on the GPU only; there is no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise _lib.AfiError(f"coco: `{name}` must be a dense {dtype} tensor" + (f" of {numel} elements" if numel is not None else "")
+                            + f", got {t.dtype} {tuple(t.shape)}")
+    return t if t.numel() else torch.zeros((1,), device=t.device, dtype=dtype)
+
+
+def _coco_groups(dt_off, gt_off, iou_off):
+    ng = dt_off.numel() - 1
+    if ng < 0:
+        raise _lib.AfiError("coco: offsets of ngroups + 1 elements expected, got an empty tensor")
+    return ng, [_coco_arg(n, t, torch.int64, ng + 1) for n, t in (("dt_off", dt_off), ("gt_off", gt_off), ("iou_off", iou_off))]
+
+
+def coco_box_iou(dt, gt, iscrowd, dt_off, gt_off, iou_off, total):
+    """The packed IoU matrices [total] (fp64) of every (image, category) group: dt [total_d, 4], gt [total_g, 4] xywh fp64, iscrowd [total_g] uint8,
+    dt_off / gt_off / iou_off [ngroups + 1] int64 on the GPU, total = iou_off[-1] (known to the caller) (afi_coco_box_iou)."""
+    ng, offs = _coco_groups(dt_off, gt_off, iou_off)
+    if dt.dim() != 2 or dt.shape[1] != 4 or gt.dim() != 2 or gt.shape[1] != 4:
+        raise _lib.AfiError(f"coco_box_iou: boxes [n, 4] expected, got {tuple(dt.shape)} and {tuple(gt.shape)}")
+    out = torch.empty((int(total),), device=dt.device, dtype=torch.float64)
+    call("afi_coco_box_iou", _p(_coco_arg("dt", dt, torch.float64)), _p(_coco_arg("gt", gt, torch.float64)),
+         _p(_coco_arg("iscrowd", iscrowd, torch.uint8, gt.shape[0])), _p(offs[0]), _p(offs[1]), _p(offs[2]), ng, int(total), _p(_coco_arg("iou", out, torch.float64)),
+         stream_ptr())
+    return out
+
+
+def coco_rle_area(starts, start_off, hw):
+    """The set pixels (int64 [nmask]) of masks given as ascending run starts: starts int32 [S], start_off int64 [nmask + 1], hw int32 [nmask] = H W
+    of every mask (afi_coco_rle_area)."""
+    nmask = hw.numel()
+    out = torch.empty((nmask,), device=hw.device, dtype=torch.int64)
+    if nmask:
+        call("afi_coco_rle_area", _p(_coco_arg("starts", starts, torch.int32)), _p(_coco_arg("start_off", start_off, torch.int64, nmask + 1)),
+             _p(_coco_arg("hw", hw, torch.int32)), nmask, _p(out), stream_ptr())
+    return out
+
+
+def coco_rle_iou(dt, gt, iscrowd, dt_off, gt_off, iou_off, total, want_inter=False):
+    """The packed mask IoU matrices [total] (fp64; with want_inter also the intersections, int64): dt and gt are (starts, start_off, hw, area) with
+    area = coco_rle_area's; a pair of masks with different H W gives -1 (afi_coco_rle_iou)."""
+    ng, offs = _coco_groups(dt_off, gt_off, iou_off)
+    args = []
+    for side, (starts, soff, hw, area) in (("dt", dt), ("gt", gt)):
+        n = hw.numel()
+        args += [_p(_coco_arg(f"{side} starts", starts, torch.int32)), _p(_coco_arg(f"{side} start_off", soff, torch.int64, n + 1)),
+                 _p(_coco_arg(f"{side} hw", hw, torch.int32)), _p(_coco_arg(f"{side} area", area, torch.int64, n))]
+    dev = dt[2].device
+    out = torch.empty((int(total),), device=dev, dtype=torch.float64)
+    inter = torch.empty((int(total),), device=dev, dtype=torch.int64) if want_inter else None
+    call("afi_coco_rle_iou", *args, _p(_coco_arg("iscrowd", iscrowd, torch.uint8, gt[2].numel())), _p(offs[0]), _p(offs[1]), _p(offs[2]), ng, int(total),
+         _p(_coco_arg("inter", inter, torch.int64)) if want_inter else _p(None), _p(_coco_arg("iou", out, torch.float64)), stream_ptr())
+    return (out, inter) if want_inter else out
+
+
+def coco_match(iou, dt_off, gt_off, iou_off, dt_area, gt_area, iscrowd, area_rng, iou_thr, max_g=None, ws=None):
+    """pycocotools' greedy matching of every group for A area ranges (area_rng [A, 2] fp64) x T thresholds (iou_thr [T] fp64): (dt_match int32
+    [A, T, total_d] = the matched GT's index inside its group or -1, dt_ignore uint8 [A, T, total_d], gt_ignore uint8 [A, total_g]).  dt_area
+    [total_d], gt_area [total_g] fp64, iscrowd [total_g] uint8.  max_g: an upper bound on the GTs of any group, when the caller knows one
+    (None: total_g); the kernel for groups of more than 64 GTs is launched only if it exceeds 64.  ws: a dense GPU buffer of at least afi_coco_match_ws_bytes(total_g, A, T) bytes
+    to use instead of a fresh workspace (afi_coco_match)."""
+    ng, offs = _coco_groups(dt_off, gt_off, iou_off)
+    if area_rng.dim() != 2 or area_rng.shape[1] != 2 or iou_thr.dim() != 1 or not area_rng.shape[0] or not iou_thr.shape[0]:
+        raise _lib.AfiError(f"coco_match: area_rng [A, 2] and iou_thr [T] expected, got {tuple(area_rng.shape)} and {tuple(iou_thr.shape)}")
+    A, T, nd, ngt, dev = area_rng.shape[0], iou_thr.shape[0], dt_area.numel(), gt_area.numel(), dt_area.device
+    n = _lib.load().afi_coco_match_ws_bytes(ngt, A, T)
+    if n < 0:
+        raise _lib.AfiError(f"coco_match: {A} area ranges x {T} thresholds are not supported (A T <= 4096)")
+    if ws is None:
+        ws = new_workspace((n + 3) // 4 + 1, dev)
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < n:
+        raise _lib.AfiError(f"coco_match: ws must be a dense GPU buffer of at least {n} bytes")
+    dtm = torch.empty((A, T, nd), device=dev, dtype=torch.int32)
+    dti = torch.empty((A, T, nd), device=dev, dtype=torch.uint8)
+    gti = torch.empty((A, ngt), device=dev, dtype=torch.uint8)
+    call("afi_coco_match", _p(_coco_arg("iou", iou, torch.float64)), _p(offs[0]), _p(offs[1]), _p(offs[2]), ng,
+         _p(_coco_arg("dt_area", dt_area, torch.float64)), _p(_coco_arg("gt_area", gt_area, torch.float64)),
+         _p(_coco_arg("iscrowd", iscrowd, torch.uint8, ngt)), nd, ngt, _p(_coco_arg("area_rng", area_rng, torch.float64)), A,
+         _p(_coco_arg("iou_thr", iou_thr, torch.float64)), T, ngt if max_g is None else int(max_g), _p(_coco_arg("dt_match", dtm, torch.int32)), _p(_coco_arg("dt_ignore", dti, torch.uint8)),
+         _p(_coco_arg("gt_ignore", gti, torch.uint8)), _p(ws), ws.numel() * ws.element_size(), stream_ptr())
+    return dtm, dti, gti
+
+
 # ------------------------------------------------------------------------------------------------ bandwidth ops
 def bilinear2x(x, out=None, beta=0.0):
     N, C_, H, W = x.shape

@@ -698,6 +698,46 @@ int afi_mask_rle_count(const float* probs, const float* boxes, int R, int M, int
 int afi_mask_rle_emit(const float* boxes, int R, int H, int W, const void* ws, long long ws_bytes, const long long* offsets, int* starts,
                       void* stream);
 
+/* ------------------------------------------------------------------ COCO evaluation: IoU and greedy matching (csrc/coco_eval.hip)
+ * pycocotools' COCOeval.computeIoU and evaluateImg for bbox and segm (afigan_amd/coco_eval.py accumulates on the host).  Work comes in groups,
+ * one per (image, category): the D detections of a group (the caller sorted them by descending score, stably, and cut them, to 100 for COCO) and
+ * its G ground truths in annotation order are rows dt_off[i] .. dt_off[i + 1] and gt_off[i] .. gt_off[i + 1] of the per-detection and per-GT
+ * arrays, and its matrix [D][G], row-major, is iou_off[i] .. iou_off[i + 1] of the packed matrices: three device arrays of ngroups + 1 long long
+ * with iou_off[i + 1] - iou_off[i] = D G; total = iou_off[ngroups] (the caller knows it).  Every pointer is a device pointer.  fp64 throughout,
+ * operation by operation as written here (no contraction), so a numpy fp64 restatement gives the same bits.  No atomics, no host
+ * synchronisation; bit-identical between runs.  ngroups = 0 or total = 0 is accepted and launches nothing.
+ * afi_coco_box_iou: dt [total_d][4], gt [total_g][4] as (x, y, w, h), iscrowd [total_g] bytes.  w = min(dx + dw, gx + gw) - max(dx, gx), h
+ *   likewise; w <= 0 or h <= 0 gives 0, else i = w h, u = crowd ? dw dh : dw dh + gw gh - i, iou = i / u.
+ * Masks are ascending run starts (afi_mask_rle_emit's, rle.counts_from_starts' format; equal neighbours, i.e. empty runs, are allowed): mask m
+ *   is starts[start_off[m] .. start_off[m + 1]) (start_off: nmask + 1 long long) on hw[m] = H W pixels (int32); pixels from an even-indexed start
+ *   up to the next start (or H W) are set.
+ * afi_coco_rle_area: area[m] = the number of set pixels (long long).
+ * afi_coco_rle_iou: inter = the number of pixels set in both masks of a pair (a two-pointer merge, entered by a binary search at the first pixel
+ *   where both masks have begun and left at the first where one has ended), u = crowd ? area(d) : area(d) + area(g) - inter,
+ *   iou = u == 0 ? 0 : (double)inter / (double)u.  dt_area / gt_area: afi_coco_rle_area's.  A pair of masks with different H W gives -1 (both
+ *   outputs).  inter (long long, packed like iou) may be NULL.
+ * afi_coco_match: the greedy matching for A area ranges (area_rng [A][2] = lo, hi) x T thresholds (iou_thr [T]) per group; dt_area [total_d],
+ *   gt_area [total_g] fp64.  gt_ignore [A][total_g] = iscrowd || area < lo || area > hi.  For each detection d in order: best = min(thr, 1 - 1e-10),
+ *   m = -1; over the non-ignored GTs in order, then -- only while m is still -1 -- over the ignored ones: skip a GT already matched at this
+ *   (a, t) unless it is a crowd; skip it if iou[d][g] < best; else best = iou[d][g], m = g (an equal IoU moves the match to the later GT).
+ *   dt_match [A][T][total_d] (int32) = m, the GT's index inside its group, or -1; dt_ignore [A][T][total_d] = gt_ignore[a][m], or, unmatched,
+ *   (dt_area < lo || dt_area > hi).  max_g: the caller's upper bound on the G of any group (it built the offsets); only when max_g > 64 is the
+ *   kernel for groups of more than 64 GTs launched at all; a group with G > max_g is left unmatched (its outputs are not written);
+ *   A max_g < 2^31 (AFI_ERR_UNSUPPORTED).  ws: afi_coco_match_ws_bytes(total_g, A, T) bytes (-1: unsupported, A T > 4096), read only after being
+ *   written; a smaller ws_bytes is AFI_ERR_BAD_ARG. */
+int afi_coco_box_iou(const double* dt, const double* gt, const unsigned char* iscrowd, const long long* dt_off, const long long* gt_off,
+                     const long long* iou_off, int ngroups, long long total, double* iou, void* stream);
+int afi_coco_rle_area(const int* starts, const long long* start_off, const int* hw, long long nmask, long long* area, void* stream);
+int afi_coco_rle_iou(const int* dt_starts, const long long* dt_start_off, const int* dt_hw, const long long* dt_area, const int* gt_starts,
+                     const long long* gt_start_off, const int* gt_hw, const long long* gt_area, const unsigned char* iscrowd,
+                     const long long* dt_off, const long long* gt_off, const long long* iou_off, int ngroups, long long total, long long* inter,
+                     double* iou, void* stream);
+long long afi_coco_match_ws_bytes(long long total_g, int A, int T);
+int afi_coco_match(const double* iou, const long long* dt_off, const long long* gt_off, const long long* iou_off, int ngroups,
+                   const double* dt_area, const double* gt_area, const unsigned char* iscrowd, long long total_d, long long total_g,
+                   const double* area_rng, int A, const double* iou_thr, int T, int max_g, int* dt_match, unsigned char* dt_ignore,
+                   unsigned char* gt_ignore, void* ws, long long ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
