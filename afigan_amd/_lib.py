@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AFI_LIB_PATH") or os.path.join(_HERE, "csrc", "libafigan_hip.so")   # override: A/B kernel builds
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "afigan_hip.h")   # the one statement of the boundary: read at import, ships with the package
-ABI_VERSION = 8                       # what this binding (the struct mirrors below, ops.py) was written against; load() compares it with the library's
+ABI_VERSION = 9                       # what this binding (the struct mirrors below, ops.py) was written against; load() compares it with the library's
 
 
 class AfiError(RuntimeError):

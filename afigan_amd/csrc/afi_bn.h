@@ -1,5 +1,5 @@
 // The BatchNorm affine of the discriminator blocks and its LeakyReLU, as ONE definition for every kernel that evaluates them: the stand-alone
-// apply pass and the backward's recomputed masks (elementwise.hip), and the Winograd input transforms that apply them on load (winograd.hip).
+// apply pass, the backward's recomputed masks and the fused tail that applies them on load (elementwise.hip).
 #pragma once
 #include "afi_common.h"
 

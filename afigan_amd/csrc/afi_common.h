@@ -22,8 +22,8 @@ struct AfiView {
 };
 
 // A tensor that is read THROUGH a BatchNorm affine and LeakyReLU(0.2): the reader sees lrelu(((x - mean) * invstd) * gamma + beta) per channel
-// (csrc/afi_bn.h: the exact arithmetic of the stand-alone apply pass), zero padding stays zero.  mean = null: off.  Taken by the Winograd
-// input transforms: a discriminator block's activation is then never written -- its consumers read the saved conv output.
+// (csrc/afi_bn.h: the exact arithmetic of the stand-alone apply pass).  mean = null: off.  Taken by the discriminator's fused tail
+// (afi_launch_disc_tail_*): the last block's activation is then never written -- the last conv reads the saved conv output.
 struct AfiBnLoad { const float* mean; const float* invstd; const float* gamma; const float* beta; };
 
 // Parameters of the pixel-M implicit GEMM (forward conv, conv-transpose forward, and both dgrads).
@@ -72,22 +72,12 @@ struct AfiPixGemm {
     // map otherwise): fp64 partial sums [stats_rows][2][Ncols] (sum, sum of squares per channel), one row per block of that launch; the
     // launcher fills stats_rows.  Taken only by the plain-store epilogue on 256 / 512 / 1024-channel outputs; null = off.
     double* stats; int stats_rows;
-    // ... and, beside them, the per-channel MINIMUM and MAXIMUM of the stored output as fp32 rows [stats_rows][2][Ncols] (min, max), one row per
-    // block: from them the statistics finalizer derives the largest magnitude of the block's ACTIVATION lrelu(affine(c)) -- the affine is
-    // monotonic per channel, so it is attained at one of the two -- before any kernel has evaluated it (AFI_OPT_D_FOLD_BN_APPLY).  Null = off.
-    float* stats_mm;
-    // The BatchNorm BACKWARD sums of the stored output, for an output that is the gradient with respect to a discriminator block's ACTIVATION (the
-    // data gradient of the next block): fp64 rows [stats_rows][2][Ncols] of sum g m and sum g m xhat per channel, m the LeakyReLU' factor and
-    // xhat the normalised value, both recomputed from the block's saved conv output bstats_c (dense [pixels][Ncols], the output's geometry)
-    // through bstats_bn (csrc/afi_bn.h) -- the pass afi_colred_partial_kernel<3> makes over both tensors otherwise.  Same shapes as `stats`; null = off.
-    double* bstats; const float* bstats_c; AfiBnLoad bstats_bn; float bstats_slope;
     int no_wcache;                             // Winograd form: B is a per-call scratch (its pointer says nothing about its contents): never cache its transform
     // Small-map bf16x6 form (csrc/smallmap.hip, afi_pix_gemm_wk6): the weights pre-split into bf16 MFMA-fragment images,
     // [N tile of 32][K stage of 32][n half][hi | mid | lo][lane] x 16 B, K stages in the kernel's own order (channel chunk, K phase, tap);
     // null = the fp32-MFMA kernel reads B itself.  A problem on input channels [c_lo, c_lo + Ck) of a wider weight starts at stage
     // bimg_stage0 = c_lo / 32 * ntaps of that weight's image; bimg_nstages = stages per N tile of the whole image.
     const unsigned char* Bimg; int bimg_stage0, bimg_nstages;
-    AfiBnLoad a_bn;                                        // Winograd form only: A is read through this affine + LeakyReLU (every other form refuses it)
     // Winograd form under the f16x3 arithmetic only: the largest magnitude of A (device memory).  a_amax_known = 1: its producer has published it
     // (the input transform then writes the planes split into fp16 pieces); 0: a zero-filled slot the input transform raises; null: a slot of the call's pool
     float* a_amax; int a_amax_known;
@@ -105,15 +95,13 @@ struct AfiPixGemm {
 static inline int afi_o16_refused(const AfiPixGemm& p) {
     if (p.o_dtype == AFI_STORE_F32) return AFI_OK;
     if (p.o_dtype != AFI_STORE_BF16 && p.o_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
-    if (p.beta != 0.f || p.r2_post || p.O2.p || p.stats || p.stats_mm || p.bstats) return AFI_ERR_UNSUPPORTED;
+    if (p.beta != 0.f || p.r2_post || p.O2.p || p.stats) return AFI_ERR_UNSUPPORTED;
     return AFI_OK;
 }
 #define AFI_WK6_STAGE_BYTES 6144
 // one weight (or weight view) to turn into such an image: the B addressing of AfiPixGemm (b_rc = 0: row n at B + n*b_sRow + tap*b_sTap + c;
 // b_rc = 1: row (kphase*Ck + c) at B + ...*b_sRow + tap*b_sTap + n), image bytes = ceil(Ncols/32) * ceil(Ck/32)*nKphase*ntaps * 6144
-// stage_off / nstages_img (0 = this job's own stage count): the job fills stages [stage_off, stage_off + its stages) of an image whose N tiles
-// are nstages_img stages apart -- several weights side by side along K in ONE image (the dense block's four growth convs as one data gradient)
-struct AfiWk6ImgJob { const float* B; long long b_sRow, b_sTap; int Ncols, Ck, ntaps, nKphase, b_rc, stage_off; unsigned char* dst; int nstages_img, pad1; };
+struct AfiWk6ImgJob { const float* B; long long b_sRow, b_sTap; int Ncols, Ck, ntaps, nKphase, b_rc; unsigned char* dst; };
 // Work of a small-map backward pass that depends on nothing the pass computes and rides in its image launch as extra blocks (a launch of its
 // own costs each of them more than the work): zero_p[0 .. 4 zero_n4) = 0 (the packed gradient buffers the stream-K weight gradients add into),
 // and bl_dx[N,H,W,C] = bilinear2x^T(bl_dout[N,2H,2W,C]) (the skip path's gradient, generator_rdb.py:125).  Null pointers: off.
@@ -124,22 +112,6 @@ struct AfiWk6Side { float* zero_p; long long zero_n4; const float* bl_dout; floa
 // tile (32 ci x 4 co, or 16 ci x 8 co, x 36 taps) so that reads and stores stay contiguous.  pack_dst (optional): the packed fp32 form Wp is
 // written as well, by further blocks of the same launch (for the callers that still read it).  Cin, Cout multiples of 32.
 struct AfiWk6ConvT { const float* W; unsigned char* dst; float* pack_dst; int Cin, Cout, mode, pad_; };
-
-// Fused growth-conv chain of one dense block on a small map (csrc/smallmap.hip: afi_rdb_chain6_kernel): three dependent 3x3 convs with
-// 32-channel outputs -- y2, y3, y4 of ResidualDenseBlock.forward, or the data gradients g3, g2, g1 of its backward -- in ONE launch.  A block
-// owns an 8 x 8 pixel tile, keeps region 0 (the chain's 32-channel input: y1 / g4) with a 3-pixel halo in LDS and recomputes each link on
-// a halo that shrinks by one (12 x 12, 10 x 10, 8 x 8): phase p multiplies regions 0..p (K chunks of 32 channels, 9 taps each, weights
-// from bf16x6 images) into the next region, adds `partial`, applies LeakyReLU (mode 0) or the LeakyReLU' factor of Z (mode 1), zeroes what
-// lies outside the map (the convs' zero padding), and the owner stores its own 8 x 8 pixels to `out`.
-struct AfiChain6Phase {
-    const unsigned char* img[3]; int stage0[3]; int pad_;    // K chunk ci (region ci): weight-image stages [stage0, stage0 + 9) of an N tile of 32
-    AfiView partial, Z, out;                                 // 32-channel views on the map (p points at the slice's first channel)
-};
-struct AfiChain6 {
-    int N, H, W, a_sgn, mode, tiles_y, tiles_x, pad_;
-    AfiView src0, copy0;                                     // region 0's source; optional copy of its own pixels (null p: off)
-    AfiChain6Phase ph[3];
-};
 
 // Parameters of the weight-gradient GEMM:  dW[co'][tap][ci] += alpha * sum_pix dY[pix][co'] * X[pix+tap][ci]
 struct AfiWgradGemm {

@@ -29,7 +29,6 @@ int afi_launch_pix_gemm_group(const AfiPixGemm* probs, int n, int b_rc, hipStrea
 // ---- smallmap.hip
 long long afi_wk6_image_bytes(int Ncols, int Ck, int ntaps, int nKphase);                       // bf16x6 weight images of the small-map kernels
 int afi_launch_wk6_images(const AfiWk6ImgJob* jobs, int n, hipStream_t st, const AfiWk6Side* side = nullptr, const AfiWk6ConvT* ct = nullptr);
-int afi_launch_rdb_chain6(const AfiChain6& c, hipStream_t st);                                   // a dense block's chain of 32-channel convs in one launch
 int afi_launch_pix_gemm_sk(const AfiPixGemm& p, int b_rc, hipStream_t st);                       // these four: called by the launchers of igemm.hip
 int afi_launch_pix_gemm_wk_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st);
 int afi_launch_wgrad_group(const AfiWgradGemm* probs, int n, int wide, hipStream_t st);
@@ -58,8 +57,6 @@ int afi_launch_bn_stats(const float* x, long long P, int C, float* mean, float* 
 int afi_launch_bn_stats_from_partials(const double* partial, int rows, long long P, int C, float* mean, float* invstd, float* var_out, float* running_mean,
                                       float* running_var, hipStream_t st, long long* num_batches_tracked = nullptr, float eps = -1.f, float momentum = -1.f);
 int afi_launch_view_absmax(AfiView x, int N, int H, int W, int C, float* amax, hipStream_t st);
-int afi_launch_bn_act_amax(const float* mm, int rows, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, float slope,
-                           float* amax, hipStream_t st);
 int afi_launch_bn_apply_lrelu(const float* x, float* y, const float* mean, const float* invstd, const float* gamma, const float* beta,
                               long long P, int C, hipStream_t st, float slope = AFI_LRELU_SLOPE, float* amax = nullptr);
 int afi_launch_bn_bwd(const float* g, const float* x, float* dx, const float* mean, const float* invstd, const float* gamma, float* dgamma,
@@ -72,9 +69,6 @@ int afi_launch_bn_bwd_apply(const float* g, const float* x, float* dx, const flo
                             long long P_total, int C, hipStream_t st);
 int afi_launch_stencil9_sum(const float* d9, int ld, const float* bias, float* out, int N, int H, int W, hipStream_t st);
 int afi_launch_stencil9_scatter(const float* dlogit, float* dd9, int ld, int N, int H, int W, hipStream_t st);
-int afi_launch_bn_bwd_from_partials(const double* partial, int rows, const float* g, const float* x, float* dx, const float* mean, const float* invstd,
-                                    const float* gamma, float* dgamma, float* dbeta, float gscale, long long P, int C, float* scratch, hipStream_t st,
-                                    const float* mask_beta, float slope, float* amax);
 extern "C" long long afi_disc_tail_scratch_floats(int C);
 int afi_launch_disc_tail_fwd(const float* x, const AfiBnLoad* bn, float slope, const float* w3, float* d9, long long P, int C, hipStream_t st);
 int afi_launch_disc_tail_bwd(const float* x, const float* dd9, const AfiBnLoad bn, float slope, const float* w3, float* dx, float* dgamma, float* dbeta, float* dw3,
@@ -100,14 +94,14 @@ int afi_launch_invstd(const float* var, float* invstd, int C, hipStream_t st);
 #endif
 int afi_wino_stats_rows(long long T, int C);               // rows of fp64 partials a STATS output transform writes (0: not fused), at most AFI_STATS_MAX_ROWS
 int afi_launch_wino_weight(const float* w, float* U, int O, int I, int mode, hipStream_t st, float* wmax = nullptr);
-int afi_launch_wino_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo = 0, const AfiBnLoad* bn = nullptr, float* amax = nullptr,
+int afi_launch_wino_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo = 0, float* amax = nullptr,
                           const AfiF16Bound* pre = nullptr);
 int afi_launch_wino_output(const float* M, long long Tpad, int N, int H, int W, int C, const float* bias, float alpha, AfiView out, AfiView z,
                            hipStream_t st);
 int afi_launch_wino_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st);
 int afi_launch_wino_dy(AfiView dy, int N, int H, int W, int C, long long Tpad, float* Q, hipStream_t st, long long ldo = 0, float* amax = nullptr, const AfiF16Bound* pre = nullptr);
 int afi_launch_wino_dw(const float* dU, float* dW, int O, int I, float alpha, hipStream_t st);
-int afi_launch_wino4_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo = 0, const AfiBnLoad* bn = nullptr, float* amax = nullptr,
+int afi_launch_wino4_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo = 0, float* amax = nullptr,
                            const AfiF16Bound* pre = nullptr);
 int afi_launch_wino4_weight(const float* w, float* U, int O, int I, int mode, hipStream_t st, float* wmax = nullptr);
 int afi_launch_wino4_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st);

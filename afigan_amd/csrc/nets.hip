@@ -66,8 +66,8 @@ struct AfiOptions { long long v[AFI_OPT_COUNT]; };
 #endif
 static const AfiOptions kDefaultOptions = {{/*WINOGRAD*/ 1, /*F4_BACKWARD*/ 1, /*F4_FORWARD*/ AFI_DEFAULT_F4_FORWARD, /*BN_STATS_FP64*/ 1, /*D_WINOGRAD_MIN_PIXELS*/ 1024,
                                             /*G_WINOGRAD_MIN_PIXELS*/ 2048, /*G_SMALLMAP_MAX_PIXELS*/ 2048, /*G_GROUPED_WGRAD_MAX_PIXELS*/ 3000,
-                                            /*G_BATCH_GROWTH_GRADS*/ 1, /*G_SMALLMAP6_MAX_PIXELS*/ 4096, /*G_RDB_CHAIN*/ 0, /*D_FOLD_BN_APPLY*/ 0, /*DETERMINISTIC*/ 0, /*F16_PRESPLIT*/ 1, /*F16_NT256_MIN_TILES*/ 512,
-                                            /*F16_LOCAL_SUMS*/ AFI_DEFAULT_LOCAL_SUMS, /*D_FUSE_TAIL*/ 1, /*D_FUSE_BWD_SUMS*/ 0}};
+                                            /*G_BATCH_GROWTH_GRADS*/ 1, /*G_SMALLMAP6_MAX_PIXELS*/ 4096, /*DETERMINISTIC*/ 0, /*F16_PRESPLIT*/ 1, /*F16_NT256_MIN_TILES*/ 512,
+                                            /*F16_LOCAL_SUMS*/ AFI_DEFAULT_LOCAL_SUMS, /*D_FUSE_TAIL*/ 1}};
 struct afi_ctx {
     int device = -1;                                       // the device the context was created on; calls on another one are refused
     float* op_scratch = nullptr; long long op_scratch_floats = 0;
@@ -296,36 +296,25 @@ static float* wino_wcache_slot(afi_ctx* cx, const float* w, int f4, int mode, in
 // missing ones in ONE launch, and attaches the image to each GEMM descriptor; a descriptor without an image runs on the fp32-MFMA kernel.
 #define AFI_WG6_WIDE 16                                    // wide weight-gradient problems of one small-map backward pass (7 + one per dense block)
 constexpr long long kWk6MaxPixels = 8192;                  // workspaces reserve the image arena for calls up to this many low-res pixels
-constexpr int kWk6MaxReq = 24, kWk6MaxJobs = 40;
-// One image request: `key` names it in the cache (with `tag`: 0 forward / K-contiguous weights, 1 data gradient / row-contiguous weights,
-// 2 a dense block's four growth convs side by side along K: the data gradient 4G -> C of their block-input columns); njob source weights,
-// job j filling the K chunks [chunk0_j, chunk0_j + Ck_j / 32) of every N tile.
-struct Wk6Src { const float* src; int Ck; long long b_sRow, b_sTap; };
+constexpr int kWk6MaxReq = 24;
+// One image request: `key` names it in the cache (with b_rc: 0 forward / K-contiguous weights, 1 data gradient / row-contiguous weights); src:
+// the weight it is built from.
 // convT: the source is the conv-transpose weight in its torch layout [Cin][Cout][6][6] (AfiWk6ConvT; 1 the forward's image, 2 the data gradient's;
 // pack_dst: the packed fp32 form written by the same launch) instead of a K- / row-contiguous matrix
-struct Wk6Req { const float* key; int tag, Ncols, Ck, nKphase, b_rc, njob; Wk6Src j[4]; int convT; float* pack_dst; };
+struct Wk6Req { const float* key; const float* src; int Ncols, Ck, nKphase, b_rc; long long b_sRow, b_sTap; int convT; float* pack_dst; };
 static inline Wk6Req wk6_req(const float* key, const float* src, int Ncols, int Ck, int nKphase, int b_rc, long long b_sRow, long long b_sTap) {
-    Wk6Req r;
-    r.key = key; r.tag = b_rc; r.Ncols = Ncols; r.Ck = Ck; r.nKphase = nKphase; r.b_rc = b_rc; r.njob = 1;
-    r.j[0] = Wk6Src{src, Ck, b_sRow, b_sTap};
-    r.convT = 0; r.pack_dst = nullptr;
-    return r;
+    return Wk6Req{key, src, Ncols, Ck, nKphase, b_rc, b_sRow, b_sTap, 0, nullptr};
 }
 static inline long long wk6_req_floats(int Ncols, int Ck, int nKphase) { return align4((afi_wk6_image_bytes(Ncols, Ck, 9, nKphase) + 3) / 4); }
 struct Wk6Images {
     bool on = false;
     int n = 0;
-    struct Ent { const float* key; int tag; const unsigned char* img; int nstages; } e[kWk6MaxReq];
-    const Ent* find(const float* key, int tag) const {
-        if (!on) return nullptr;
-        for (int i = 0; i < n; ++i) if (e[i].key == key && e[i].tag == tag) return &e[i];
-        return nullptr;
-    }
+    struct Ent { const float* key; const unsigned char* img; int nstages; } e[kWk6MaxReq];
     // the image of the weight `key`, for a problem that reads its input channels [c_lo, c_lo + g.Ck) (c_lo a multiple of 32)
-    void attach(AfiPixGemm& g, const float* key, int c_lo = 0, int tag = -1) const {
+    void attach(AfiPixGemm& g, const float* key, int c_lo = 0) const {
         if (!on || (c_lo & 31)) return;
         for (int i = 0; i < n; ++i)
-            if (e[i].key == key && (tag < 0 ? e[i].tag < 2 : e[i].tag == tag)) { g.Bimg = e[i].img; g.bimg_nstages = e[i].nstages; g.bimg_stage0 = (c_lo / 32) * g.ntaps; return; }
+            if (e[i].key == key) { g.Bimg = e[i].img; g.bimg_nstages = e[i].nstages; g.bimg_stage0 = (c_lo / 32) * g.ntaps; return; }
     }
 };
 // side (optional): work that rides in the image launch (AfiWk6Side); *side_done says whether it did -- no launch happens when every image
@@ -344,7 +333,7 @@ static int wk6_build(afi_ctx* cx, Wk6Images& im, const Wk6Req* reqs, int n, floa
         explicit CacheRollback(afi_ctx* c) : cx(c), n0(c ? c->wcache.n : 0), used0(c ? c->wcache.used : 0) {}
         ~CacheRollback() { if (cx && !keep) { cx->wcache.n = n0; cx->wcache.used = used0; } }
     } rollback(cx);
-    AfiWk6ImgJob jobs[kWk6MaxJobs];
+    AfiWk6ImgJob jobs[kWk6MaxReq];
     AfiWk6ConvT ct;
     bool have_ct = false;
     int nj = 0;
@@ -353,7 +342,7 @@ static int wk6_build(afi_ctx* cx, Wk6Images& im, const Wk6Req* reqs, int n, floa
         const Wk6Req& r = reqs[i];
         const long long need = wk6_req_floats(r.Ncols, r.Ck, r.nKphase);
         bool hit = false;
-        float* slot = wino_wcache_slot(cx, r.key, /*tags 4..6: wk6 images*/ 4 + r.tag, r.nKphase, r.Ncols, r.Ck, need, hit);
+        float* slot = wino_wcache_slot(cx, r.key, /*tags 4, 5: wk6 images*/ 4 + r.b_rc, r.nKphase, r.Ncols, r.Ck, need, hit);
         if (!slot) {
             if (!arena || used + need > arena_floats) { im.n = 0; return AFI_OK; }      // no room: the call stays on the fp32-MFMA kernels
             slot = arena + used; used += need; hit = false;
@@ -362,18 +351,12 @@ static int wk6_build(afi_ctx* cx, Wk6Images& im, const Wk6Req* reqs, int n, floa
         if (!hit && r.convT) {
             if (have_ct) { im.n = 0; return AFI_OK; }                                    // (one per launch)
             // forward: Ncols = 4 Cout, Ck = Cin; data gradient: Ncols = Cin, Ck = Cout
-            ct = AfiWk6ConvT{r.j[0].src, (unsigned char*)slot, r.pack_dst, r.convT == 1 ? r.Ck : r.Ncols, r.convT == 1 ? r.Ncols / 4 : r.Ck, r.convT == 1 ? 0 : 1, 0};
+            ct = AfiWk6ConvT{r.src, (unsigned char*)slot, r.pack_dst, r.convT == 1 ? r.Ck : r.Ncols, r.convT == 1 ? r.Ncols / 4 : r.Ck, r.convT == 1 ? 0 : 1, 0};
             have_ct = true;
         } else if (!hit) {
-            int chunk0 = 0;
-            for (int k = 0; k < r.njob; ++k) {
-                if (nj == kWk6MaxJobs) { im.n = 0; return AFI_OK; }
-                jobs[nj++] = AfiWk6ImgJob{r.j[k].src, r.j[k].b_sRow, r.j[k].b_sTap, r.Ncols, r.j[k].Ck, 9, r.nKphase, r.b_rc, chunk0 * 9 * r.nKphase,
-                                          (unsigned char*)slot, r.njob > 1 ? nst : 0, 0};
-                chunk0 += afi_cdiv(r.j[k].Ck, 32);
-            }
+            jobs[nj++] = AfiWk6ImgJob{r.src, r.b_sRow, r.b_sTap, r.Ncols, r.Ck, 9, r.nKphase, r.b_rc, (unsigned char*)slot};
         }
-        im.e[im.n++] = Wk6Images::Ent{r.key, r.tag, (const unsigned char*)slot, nst};
+        im.e[im.n++] = Wk6Images::Ent{r.key, (const unsigned char*)slot, nst};
     }
     if (nj || have_ct) {
         AFI_TRY(afi_launch_wk6_images(jobs, nj, st, side, have_ct ? &ct : nullptr));
@@ -384,7 +367,8 @@ static int wk6_build(afi_ctx* cx, Wk6Images& im, const Wk6Req* reqs, int n, floa
     im.on = true;
     return AFI_OK;
 }
-static inline bool wk6_shapes_ok(int C, int G, int R) { return (C % 32) == 0 && (G % 32) == 0 && 6 * R + 4 <= kWk6MaxReq && 9 * R + 4 <= kWk6MaxJobs; }
+// (a call lists 5 R + 4 images; the bound stays where the schedule was measured: up to three dense blocks)
+static inline bool wk6_shapes_ok(int C, int G, int R) { return (C % 32) == 0 && (G % 32) == 0 && 6 * R + 4 <= kWk6MaxReq; }
 // the final conv on the up-sampled map (4x the pixels) stays on the small-map kernel while the map has at most this many pixels: at config 1
 // (50 x 68) the Winograd form is five launches of 9 .. 19 us (weight transform, bf16 split, input transform, GEMM, output transform)
 constexpr long long kWk6HiResMaxPixels = 4096;
@@ -401,7 +385,7 @@ static long long gen_wk6_bwd_floats(int C, int G, int R, long long P) {
     const int L = C + 4 * G;
     long long f = 3 * wk6_req_floats(C, C, 1) + wk6_req_floats(C, C, 4);             // head, trunk, final conv; conv-transpose
     for (int k = 1; k <= 4; ++k) f += (long long)R * wk6_req_floats(C + (k - 1) * G, G, 1);
-    return f + (long long)R * (wk6_req_floats(L, C, 1) + wk6_req_floats(C, 4 * G, 1));           // (+ the growth convs' block-input columns side by side)
+    return f + (long long)R * wk6_req_floats(L, C, 1);
 }
 
 // a forward or data-gradient descriptor in the form f (wino_form of the same descriptor)
@@ -434,8 +418,6 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* 
     // f16x3: the largest magnitude of A.  g.a_amax given and known (its producer published it): the transform writes the planes already
     // split into fp16 pieces; given and not known: a zero-filled slot of the caller's that the transform raises (the caller keeps it, e.g. for
     // the backward pass); not given: a slot of the call's pool.
-    // (an input read through a BatchNorm affine -- AFI_OPT_D_FOLD_BN_APPLY -- is split like any other once its maximum is known: the statistics
-    //  finalizer derives it from the conv output's per-channel extremes, afi_launch_bn_act_amax)
     const bool a_pre = f.presplit && g.a_amax && g.a_amax_known;
     if (f16 && !(amax = g.a_amax ? g.a_amax : wino_amax_take(cx, ws, ws_floats, 1, st))) return AFI_ERR_LAUNCH;
     const AfiF16Bound abound = afi_f16_bound(amax, f4 ? 2 : 1);
@@ -446,8 +428,8 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* 
         if (nph == 4) { a.p += (ph >> 1) * g.A.sH + (ph & 1) * g.A.sW; a.sH *= 2; a.sW *= 2; }
         // (a caller's not-yet-known slot is raised under every arithmetic: a later pass may read it)
         float* raise = g.a_amax ? (g.a_amax_known ? nullptr : g.a_amax) : (f16 ? amax : nullptr);
-        AFI_TRY(f4 ? afi_launch_wino4_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, &g.a_bn, raise, a_pre ? &abound : nullptr)
-                   : afi_launch_wino_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, &g.a_bn, raise, a_pre ? &abound : nullptr));
+        AFI_TRY(f4 ? afi_launch_wino4_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, raise, a_pre ? &abound : nullptr)
+                   : afi_launch_wino_input(a, g.N, g.H, g.W, g.Ck, Tpad, Vb + ph * g.Ck, st, K, raise, a_pre ? &abound : nullptr));
     }
     if (dma) {
         if (f16) AFI_TRY(afi_launch_gemm_nt_f16x3(Vb, Usp, Mb, np, Tpad, Nc, K, abound, st, a_pre, afi_opt(cx, AFI_OPT_F16_NT256_MIN_TILES), g.nt_local_sums != 0));
@@ -470,18 +452,14 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* 
     return f4 ? afi_launch_wino4_output_epi(Mb, Tpad, g, st) : afi_launch_wino_output_epi(Mb, Tpad, g, st);
 }
 
-// what a data gradient's output transform needs to take the BatchNorm-backward sums of its output along (AfiPixGemm::bstats)
-struct AfiBwdSums { double* rows; const float* c; AfiBnLoad bn; float slope; };
 // what a whole-net call adds to a plain Winograd conv (wino_conv); every member is optional
 struct WinoConvOpt {
-    // forward: fp64 partial rows for the BatchNorm statistics of the output, accumulated by the output transform (afi_common.h), with (stats_mm)
-    // the output's per-channel minimum / maximum; *stats_rows: the rows written, 0 when this call did not fuse them (the caller runs the separate pass)
-    double* stats = nullptr; float* stats_mm = nullptr; int* stats_rows = nullptr;
-    const AfiBnLoad* in_bn = nullptr;   // `in` is read through a BatchNorm affine + LeakyReLU: the activation of the block that produced it is never written
+    // forward: fp64 partial rows for the BatchNorm statistics of the output, accumulated by the output transform (afi_common.h);
+    // *stats_rows: the rows written, 0 when this call did not fuse them (the caller runs the separate pass)
+    double* stats = nullptr; int* stats_rows = nullptr;
     float* in_amax = nullptr; bool in_amax_known = false;   // f16x3: the slot of in's largest magnitude, and whether its producer published it
     float* v_keep = nullptr;            // forward in a keeping form (WinoForm::keep): write the input planes here, for the weight gradient
     bool local_sums = false;            // f16x3: the NT GEMM takes k-step-local sums (AFI_OPT_F16_LOCAL_SUMS)
-    const AfiBwdSums* bsums = nullptr; int* bsums_rows = nullptr;   // data gradient: the BatchNorm-backward sums of its output, as stats
 };
 // forward (kinds kWinoFwd / kWinoFwdF4: out = conv(in, w) + bias) or data gradient (kWinoDgrad: out = conv^T(in, w) * lrelu'(z)) by descriptor
 static int wino_conv(afi_ctx* cx, WinoKind kind, AfiView in, int N, int H, int W, int K, const float* w, int Nc, const float* bias, AfiView out, AfiView z,
@@ -489,7 +467,6 @@ static int wino_conv(afi_ctx* cx, WinoKind kind, AfiView in, int N, int H, int W
     if ((K & 3) || (Nc & 3)) return AFI_ERR_UNSUPPORTED;
     const bool dgrad = kind == kWinoDgrad;
     AfiPixGemm g = dgrad ? conv_dgrad_desc(in, N, H, W, K, w, Nc, out) : conv_fwd_desc(in, N, H, W, K, w, bias, Nc, out);
-    if (o.in_bn) g.a_bn = *o.in_bn;
     g.a_amax = o.in_amax; g.a_amax_known = o.in_amax_known ? 1 : 0;
     g.v_keep = o.v_keep;
     g.nt_local_sums = o.local_sums ? 1 : 0;
@@ -497,11 +474,7 @@ static int wino_conv(afi_ctx* cx, WinoKind kind, AfiView in, int N, int H, int W
     const WinoForm f = wino_form(cx, g, dgrad, kind == kWinoFwdF4);
     const int rows = afi_wino_stats_rows(f.T, Nc);
     if (o.stats_rows) *o.stats_rows = 0;
-    if (o.stats && o.stats_rows && !dgrad && rows > 0) { g.stats = o.stats; g.stats_mm = o.stats_mm; *o.stats_rows = rows; }
-    if (o.bsums_rows) *o.bsums_rows = 0;
-    if (o.bsums && o.bsums_rows && dgrad && o.bsums->rows && !z.p && rows > 0) {
-        g.bstats = o.bsums->rows; g.bstats_c = o.bsums->c; g.bstats_bn = o.bsums->bn; g.bstats_slope = o.bsums->slope; *o.bsums_rows = rows;
-    }
+    if (o.stats && o.stats_rows && !dgrad && rows > 0) { g.stats = o.stats; *o.stats_rows = rows; }
     return wino_run(cx, g, f, ws, ws_floats, part, part_floats, st);
 }
 
@@ -536,7 +509,6 @@ static float* wino_wgacc_slot(afi_ctx* cx, float* dw, int f4, int O, int I, floa
 // what a whole-net call adds to a plain Winograd weight gradient (wino_wgrad); every member is optional
 struct WinoWgradOpt {
     int dy_phases = 1; bool accumulate = true;
-    const AfiBnLoad* x_bn = nullptr;    // x is read through a BatchNorm affine + LeakyReLU (AfiBnLoad)
     // f16x3: the largest magnitudes of the two source tensors where their producers published them: both transforms then write their planes
     // already split into fp16 pieces and the GEMM stages them by DMA alone; otherwise the transforms raise two slots of the pool
     const float* dy_amax = nullptr; const float* x_amax = nullptr;
@@ -564,8 +536,8 @@ static int wino_wgrad(afi_ctx* cx, AfiView dy, AfiView x, int N, int H, int W, i
     const AfiF16Bound vbound = afi_f16_bound(known ? o.x_amax : amax, f4 ? 2 : 1), qbound = afi_f16_bound(known ? o.dy_amax : amax + 4, f4 ? 4 : 3);
     if (o.v_have && !(f.keep && pre)) return AFI_ERR_BAD_ARG;      // (never read planes that were not written pre-split)
     if (o.v_have) Vb = (float*)o.v_have;
-    else AFI_TRY(f4 ? afi_launch_wino4_input(x, N, H, W, Cin, Tpad, Vb, st, 0, o.x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr)
-                    : afi_launch_wino_input(x, N, H, W, Cin, Tpad, Vb, st, 0, o.x_bn, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr));
+    else AFI_TRY(f4 ? afi_launch_wino4_input(x, N, H, W, Cin, Tpad, Vb, st, 0, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr)
+                    : afi_launch_wino_input(x, N, H, W, Cin, Tpad, Vb, st, 0, f16 && !known ? amax : nullptr, pre ? &vbound : nullptr));
     const int cph = Cout / dy_phases;
     for (int ph = 0; ph < dy_phases; ++ph) {
         AfiView d = dy;
@@ -616,11 +588,11 @@ int afi_debug_wk6_convT_images(const float* W, int Cin, int Cout, int mode, void
     const AfiWk6ConvT ct{W, (unsigned char*)direct, pack_ride, Cin, Cout, mode, 0};
     AFI_TRY(afi_launch_wk6_images(nullptr, 0, st, nullptr, &ct));
     AFI_TRY(afi_launch_convT_pack(W, pack_ref, Cin, Cout, st));
-    const AfiWk6ImgJob job = mode == 0 ? AfiWk6ImgJob{pack_ref, 9LL * Cin, Cin, 4 * Cout, Cin, 9, 1, 0, 0, (unsigned char*)via_pack, 0, 0}
-                                       : AfiWk6ImgJob{pack_ref, 9LL * Cin, Cin, Cin, Cout, 9, 4, 1, 0, (unsigned char*)via_pack, 0, 0};
+    const AfiWk6ImgJob job = mode == 0 ? AfiWk6ImgJob{pack_ref, 9LL * Cin, Cin, 4 * Cout, Cin, 9, 1, 0, (unsigned char*)via_pack}
+                                       : AfiWk6ImgJob{pack_ref, 9LL * Cin, Cin, Cin, Cout, 9, 4, 1, (unsigned char*)via_pack};
     return afi_launch_wk6_images(&job, 1, st, nullptr, nullptr);
 }
-int afi_abi_version(void) { return 8; }
+int afi_abi_version(void) { return 9; }
 // digest of the sources this binary was compiled from (__graft_entry__.build() writes csrc/afi_build_id.h in front of the compile:
 // sha256 over every *.hip / *.h of csrc/ and include/afigan_hip.h, the generated header excluded).  The Python binding recomputes it from the
 // tree it sits in and refuses a library built from other sources; smoke() prints it.
@@ -1143,7 +1115,7 @@ long long afi_generator_fwd_ws_floats(int C, int G, int n_rdb, int N, int H, int
 
 // backward scratch layout: [dU 4P*C][gA P*C][gB P*C][dBuf0 P*L][dBuf1 P*L][dWp 36*C*C][red]
 struct GenBwdWs {
-    long long o_du, o_ga, o_gb, o_db0, o_db1, o_dwp, o_rdbw, n_rdbw, o_rdbx, n_rdbx, o_red, o_part, n_part, o_wino, n_wino, o_wino2, o_img, n_img, o_gch, n_gch, total;
+    long long o_du, o_ga, o_gb, o_db0, o_db1, o_dwp, o_rdbw, n_rdbw, o_rdbx, n_rdbx, o_red, o_part, n_part, o_wino, n_wino, o_wino2, o_img, n_img, total;
 };
 static GenBwdWs gen_bwd_ws(int C, int G, int n_rdb, int N, int H, int W) {
     GenBwdWs w;
@@ -1167,8 +1139,6 @@ static GenBwdWs gen_bwd_ws(int C, int G, int n_rdb, int N, int H, int W) {
     w.o_wino2 = o; o += w.n_wino;                         // weight gradients (side stream on small maps)
     w.n_img = gen_wk6_bwd_floats(C, G, n_rdb, P);           // small maps: bf16x6 weight images of the data-gradient GEMMs
     w.o_img = o; o += w.n_img;
-    w.n_gch = w.n_img > 0 ? align4(P * 4LL * G) : 0;        // small maps: the final growth-conv gradients g1..g4 of a block, [P][4G] (the chain kernel's output)
-    w.o_gch = o; o += (long long)n_rdb * w.n_gch;
     w.total = o;
     return w;
 }
@@ -1265,45 +1235,6 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
             im.attach(g, prm->rdb_w[r][4], c_lo);
             return g;
         };
-        // The chain y1 -> y2 -> y3 -> y4 in ONE launch (csrc/smallmap.hip: afi_rdb_chain6_kernel) under the bf16x6 small-map schedule: step 0
-        // leaves conv_2..4's sums over the block input as raw partials in a scratch (the trunk conv's output buffer, free until then), the
-        // chain kernel adds what they take from y1..y3 (recomputing tile halos), activates and writes y2..y4 into the dense buffer, and
-        // conv5's 4G growth channels are ONE GEMM behind it: three launches per block instead of five.
-        const bool chain = batched && im.on && (afi_opt(cx, AFI_OPT_G_RDB_CHAIN) & 1) != 0 && G == 32 && 3 * G <= C && im.find(prm->rdb_w[r][1], 0) && im.find(prm->rdb_w[r][2], 0) &&
-                           im.find(prm->rdb_w[r][3], 0) && im.find(prm->rdb_w[r][4], 0);
-        if (chain) {
-            AfiPixGemm probs[5];
-            int n = 0;
-            for (int k = 1; k <= 4; ++k) {              // what conv_k takes from the block input x: y1 complete, conv_2..4 raw partials -> scratch
-                const int cin = C + (k - 1) * G;
-                AfiPixGemm g = conv_fwd_desc(b, N, H, W, C, prm->rdb_w[r][k - 1], nullptr, G, k == 1 ? ch_off(b, C) : ch_off(a7, (k - 2) * G));
-                g.b_sRow = 9LL * cin; g.b_sTap = cin;
-                g.lrelu = k == 1 ? 1 : 0;
-                im.attach(g, prm->rdb_w[r][k - 1], 0);
-                probs[n++] = g;
-            }
-            AfiPixGemm g5 = conv5_desc(0, C);
-            g5.R1 = b; g5.r1_lo = 0; g5.r1_hi = C; g5.r1s = last ? rs : 1.f;
-            if (last) { g5.R2 = buf(0); g5.r2s = 1.f; g5.r2_lo = 0; g5.r2_hi = C; }
-            probs[n++] = g5;
-            AFI_TRY(afi_launch_pix_gemm_group(probs, n, 0, st));
-            AfiChain6 cd;
-            memset(&cd, 0, sizeof(cd));
-            cd.N = N; cd.H = H; cd.W = W; cd.a_sgn = 1; cd.mode = 0;
-            cd.src0 = ch_off(b, C);
-            for (int ph = 0; ph < 3; ++ph) {            // phase ph: conv_{ph + 2} over y1 .. y_{ph + 1}
-                const Wk6Images::Ent* e = im.find(prm->rdb_w[r][ph + 1], 0);
-                for (int ci = 0; ci <= ph; ++ci) { cd.ph[ph].img[ci] = e->img; cd.ph[ph].stage0[ci] = (C / 32 + ci) * 9; }
-                cd.ph[ph].partial = ch_off(a7, ph * G);
-                cd.ph[ph].Z = null_view();
-                cd.ph[ph].out = ch_off(b, C + (ph + 1) * G);
-            }
-            AFI_TRY(afi_launch_rdb_chain6(cd, st));
-            AfiPixGemm gy = conv5_desc(C, 4 * G);       // conv5 over y1..y4, added to what step 0 stored
-            gy.beta = 1.f;
-            AFI_TRY(PG(gy, 0));
-            continue;
-        }
         if (batched) {
             for (int j = 0; j <= 4; ++j) {              // source slice j: x (j = 0) or y_j
                 const int c_lo = j == 0 ? 0 : C + (j - 1) * G, nch = j == 0 ? C : G;
@@ -1500,8 +1431,6 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
         n_wide = n_narrow = n_cs = 0; n_wide_has_convT = false;
         return AFI_OK;
     };
-    // (the dense blocks' gradient chains g4 -> g3 -> g2 -> g1 as one launch each, below: needs the packed weight gradients and 32-channel slices)
-    const bool chain_shapes = six && pack_growth6 && s.n_gch > 0 && G == 32 && (C % 32) == 0 && (afi_opt(cx, AFI_OPT_G_RDB_CHAIN) == 1 || afi_opt(cx, AFI_OPT_G_RDB_CHAIN) == 2);
     Wk6Images im;                                          // weight images of the data-gradient GEMMs (row-contiguous weights)
     // (the packed conv-transpose gradient and the packed growth-conv gradients are neighbours in the scratch: ONE fill for both)
     const bool one_fill = pack_growth6 && gr->wT && s.o_rdbw == s.o_dwp + align4(36LL * C * C) && (s.n_rdbw & 3) == 0;
@@ -1515,12 +1444,6 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
         for (int r = 0; r < R; ++r) {
             rq[nr++] = wk6_req(prm->rdb_w[r][4], prm->rdb_w[r][4], L, C, 1, 1, 9LL * L, L);
             for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; rq[nr++] = wk6_req(prm->rdb_w[r][k - 1], prm->rdb_w[r][k - 1], cin, G, 1, 1, 9LL * cin, cin); }
-            if (chain_shapes) {                             // the four growth convs' block-input columns side by side along K: ONE data gradient 4G -> C
-                Wk6Req q;
-                q.key = prm->rdb_w[r][0]; q.tag = 2; q.Ncols = C; q.Ck = 4 * G; q.nKphase = 1; q.b_rc = 1; q.njob = 4; q.convT = 0; q.pack_dst = nullptr;
-                for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; q.j[k - 1] = Wk6Src{prm->rdb_w[r][k - 1], G, 9LL * cin, cin}; }
-                rq[nr++] = q;
-            }
         }
         if (dx) rq[nr++] = wk6_req(prm->w0, prm->w0, C, C, 1, 1, 9LL * C, C);
         if (4 * P <= kWk6HiResMaxPixels) rq[nr++] = wk6_req(prm->w9, prm->w9, C, C, 1, 1, 9LL * C, C);
@@ -1595,50 +1518,6 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
             g.Z = b; g.z_lo = C + 3 * G; g.z_hi = L;                   // conv4's LReLU: its slice is final after this kernel
             im.attach(g, prm->rdb_w[r][4]);
             AFI_TRY(PG(g, 1));
-        }
-        const bool chain = chain_shapes && im.find(prm->rdb_w[r][0], 2) && im.find(prm->rdb_w[r][1], 1) && im.find(prm->rdb_w[r][2], 1) && im.find(prm->rdb_w[r][3], 1);
-        if (chain) {
-            // g4 (final above) -> g3 -> g2 -> g1 in ONE launch (csrc/smallmap.hip: afi_rdb_chain6_kernel): link k adds what conv_{k+1} .. conv_4
-            // send back to y_k to conv5's share (the raw slice of d), applies y_k's LeakyReLU' and stores g_k -- into a [P][4G] buffer of
-            // its own, next to a copy of g4: the raw slices of d stay intact for the neighbour tiles that recompute them on their halo.
-            // What the four convs send to the block input is then ONE data gradient 4G -> C on their block-input columns side by side.
-            AfiView Gc = dense_view(scratch + s.o_gch + (long long)r * s.n_gch, H, W, 4LL * G);
-            AfiChain6 cd;
-            memset(&cd, 0, sizeof(cd));
-            cd.N = N; cd.H = H; cd.W = W; cd.a_sgn = -1; cd.mode = 1;
-            cd.src0 = ch_off(d, C + 3 * G);
-            cd.copy0 = ch_off(Gc, 3 * G);
-            for (int ph = 0; ph < 3; ++ph) {                            // phase ph: g_{3 - ph} from g4 .. g_{4 - ph}
-                const int kout = 3 - ph, slice = C + (kout - 1) * G;    // conv index whose output gradient this link produces; its channel slice
-                for (int ci = 0; ci <= ph; ++ci) {                      // region ci holds g_{4 - ci}: it returns through conv_{4 - ci}'s columns of slice kout
-                    const Wk6Images::Ent* e = im.find(prm->rdb_w[r][3 - ci], 1);
-                    cd.ph[ph].img[ci] = e->img + (long long)(slice / 32) * e->nstages * AFI_WK6_STAGE_BYTES;
-                    cd.ph[ph].stage0[ci] = 0;
-                }
-                cd.ph[ph].partial = ch_off(d, slice);
-                cd.ph[ph].Z = ch_off(b, slice);
-                cd.ph[ph].out = ch_off(Gc, (kout - 1) * G);
-            }
-            AFI_TRY(afi_launch_rdb_chain6(cd, st));
-            {
-                AfiPixGemm g = conv_dgrad_desc(Gc, N, H, W, 4 * G, prm->rdb_w[r][0], C, d);
-                g.beta = 1.f;
-                if (r == 0) {                                           // RRDB skip (+dT) and the head conv's LReLU
-                    g.R2 = gB; g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
-                    g.Z = b; g.z_lo = 0; g.z_hi = C;
-                }
-                im.attach(g, prm->rdb_w[r][0], 0, /*tag: the four growth convs side by side*/ 2);
-                if (!g.Bimg) return AFI_ERR_LAUNCH;
-                g.B = nullptr;                              // this problem is DEFINED by its image: rdb_w[r][0] alone is not a [4G rows] matrix, so a
-                AFI_TRY(PG(g, 1));                          // launcher that would read B instead (afi_launch_pix_gemm) refuses a null B loudly
-            }
-            if (gr->rdb_w[r][0] || gr->rdb_w[r][1] || gr->rdb_w[r][2] || gr->rdb_w[r][3]) {
-                AFI_TRY(defer(conv_wgrad_desc(Gc, b, N, H, W, 4 * G, L, scratch + s.o_rdbw + (long long)r * s.n_rdbw, 1.f)));
-                packed_mask |= 1u << r; ++packed_blocks;
-            }
-            AFI_TRY(flush(false));
-            Gt = d; gs = 1.f;
-            continue;
         }
         for (int k = 4; k >= 1; --k) {
             const int cin = C + (k - 1) * G;
@@ -1733,7 +1612,7 @@ int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen
 // forward workspace (floats): [c0 P*F1][y0 P*F1][c1 P*F2][y1 P*F2][c2 P*F3][d9 P*16][mean,invstd x3][red] ... [y2 P*F3, where it is written][kept planes]
 struct DiscWs {
     long long P;
-    long long o_c[3], o_y[3], o_d9, o_mean[3], o_invstd[3], o_red, o_stats, o_stats_mm, o_amax, o_part, n_part, o_wino, n_wino, o_mean_b[3], o_invstd_b[3], o_vkeep[3], total;
+    long long o_c[3], o_y[3], o_d9, o_mean[3], o_invstd[3], o_red, o_stats, o_amax, o_part, n_part, o_wino, n_wino, o_mean_b[3], o_invstd_b[3], o_vkeep[3], total;
 };
 // keep_mask: bit n reserves the kept F(4x4) input planes of block n (DiscPlan::Block::keep).  The planes sit at the END of the layout, so every other
 // offset is the same under every mask; the context-free queries reserve them wherever some context could keep them (disc_ws_bound), the
@@ -1758,7 +1637,6 @@ static DiscWs disc_ws(const int F[4], int N, int H, int W, int keep_mask, bool y
     }
     w.o_red = o; o += align4(afi_reduce_scratch_floats(fmax));
     w.o_stats = o; o += 4LL * AFI_STATS_MAX_ROWS * fmax;  // fp64 partial rows [rows][2][C] of the statistics fused into the output transforms
-    w.o_stats_mm = o; o += 2LL * AFI_STATS_MAX_ROWS * fmax;      // fp32 rows [rows][2][C]: per-channel minimum / maximum of the conv output, beside them (the folded apply pass)
     w.o_amax = o; o += 16;                                // [4 n]: the largest magnitude of block n's INPUT (x, y0, y1), raised by its producer (Winograd path; kept for the backward)
     w.n_part = part_floats({w.P * F[1], w.P * F[2], w.P * F[3]});
     w.o_part = o; o += w.n_part;
@@ -1779,7 +1657,7 @@ static DiscWs disc_ws(const int F[4], int N, int H, int W, int keep_mask, bool y
 }
 // blocks 1 and 2 (the only ones that keep planes) wherever their form can be F(4x4), and y2
 static DiscWs disc_ws_bound(const int F[4], int N, int H, int W) { return disc_ws(F, N, H, W, (long long)N * H * W >= kWinoF4MinPixels ? 6 : 0, true); }
-struct DiscBwdWs { long long o_g[3], o_dd9, o_amax, o_red, o_red2, o_tail, o_bsums, o_part, n_part, o_wino, n_wino, o_wino2, total; };
+struct DiscBwdWs { long long o_g[3], o_dd9, o_amax, o_red, o_red2, o_tail, o_part, n_part, o_wino, n_wino, o_wino2, total; };
 static DiscBwdWs disc_bwd_ws(const int F[4], int N, int H, int W) {
     DiscBwdWs w;
     const long long P = (long long)N * H * W;
@@ -1792,7 +1670,6 @@ static DiscBwdWs disc_bwd_ws(const int F[4], int N, int H, int W) {
     w.o_red = o; o += align4(afi_reduce_scratch_floats(fmax));       // BatchNorm backward (main stream)
     w.o_red2 = o; o += align4(afi_reduce_scratch_floats(fmax));      // bias column sums (side stream)
     w.o_tail = o; o += align4(afi_disc_tail_scratch_floats(F[3]));   // the fused tail's partial sums (AFI_OPT_D_FUSE_TAIL)
-    w.o_bsums = o; o += 4LL * AFI_STATS_MAX_ROWS * fmax;             // fp64 rows [rows][2][C]: BatchNorm-backward sums taken by a data gradient's output transform (AFI_OPT_D_FUSE_BWD_SUMS)
     w.n_part = part_floats({P * F[0], P * F[1], P * F[2], P * F[3]});
     w.o_part = o; o += w.n_part;
     w.n_wino = disc_wino_floats(F, N, H, W);
@@ -1813,14 +1690,8 @@ struct DiscPlan {
     // AFI_OPT_D_FUSE_TAIL in force for F3 last-block channels: block 2's apply pass, the last conv and their backward run as the fused passes of
     // csrc/elementwise.hip (afi_launch_disc_tail_*): y[2] and the gradient with respect to it are never written
     bool tail;
-    // AFI_OPT_D_FOLD_BN_APPLY in force (off by default: measured slower, include/afigan_hip.h): Winograd form and ONE affine per tensor (a paired
-    // call normalises its halves separately: it runs unfolded).  The activation of blocks 0 and 1 is never written -- the next block's input
-    // transform reads the saved conv output through the block's BatchNorm affine + LeakyReLU (AfiBnLoad: the arithmetic of the apply pass, bit
-    // for bit), and so do the backward's weight-gradient input transforms.  Block 2's activation feeds the last conv and is always written.
-    bool fold;
     // the forward leaves every block input's largest magnitude in DiscWs::o_amax, whatever arithmetic it runs in (the backward trusts the slots):
-    // x's by the first input transform; y0's / y1's by the BatchNorm apply passes, or -- folded apply pass -- by the statistics finalizer, from
-    // the conv output's per-channel extremes; where neither exists (an eval-mode folded call) by the transform that reads it
+    // x's by the first input transform; y0's / y1's by the BatchNorm apply passes
     bool fwd_amax;
     // the backward (f16x3) raises the largest magnitude of every d(conv output) into DiscBwdWs::o_amax, by the BatchNorm backward that writes it:
     // with the forward's slots every Winograd transform of the pass knows its source's maximum beforehand and writes its planes pre-split
@@ -1829,16 +1700,12 @@ struct DiscPlan {
     // over x (137 MB, ~30 us at 2x200x336).  This test asks less than block 0's form (F[0] % 32 == 0 but not WinoForm::presplit's F[1] % 128):
     // it is the one that governs, so at F0 = 32 x is measured although block 0's planes are not written pre-split
     bool x_amax;
-    // AFI_OPT_D_FUSE_BWD_SUMS (off: measured, no gain): the data gradient of block n + 1 leaves the BatchNorm-backward sums of block n beside the
-    // gradient it writes (one affine per tensor: not a paired call)
-    bool fuse_bsums;
     struct Block {
         WinoForm fwd, wgrad;   // the forms of the block's forward conv and of its weight gradient
         bool local_sums;       // AFI_OPT_F16_LOCAL_SUMS: the forward's GEMM takes k-step-local sums
         bool stats;            // the forward's output transform accumulates the BatchNorm statistics (training, one affine per tensor, shapes it takes)
         // the forward keeps its input planes for the backward's weight gradient: both forms keep, and the input's maximum is known before its
-        // transform runs (blocks 1 and 2; under the folded apply pass the previous block's statistics -- with them the conv output's extremes --
-        // must be fused into its output transform).  The weight gradient's channel test governs: F[n] % 128 == 0, where the forward's form asks
+        // transform runs (blocks 1 and 2).  The weight gradient's channel test governs: F[n] % 128 == 0, where the forward's form asks
         // F[n] % 32 == 0 (at F0 = 32 block 1 keeps nothing)
         bool keep;
     } b[3];
@@ -1850,12 +1717,10 @@ static DiscPlan disc_plan(const afi_ctx* cx, const int F[4], int N, int H, int W
     const long long minpix = afi_opt(cx, AFI_OPT_D_WINOGRAD_MIN_PIXELS);
     p.wino = disc_wino_floats(F, N, H, W) > 0 && afi_opt(cx, AFI_OPT_WINOGRAD) && (long long)N * H * W >= (minpix < 1024 ? 1024 : minpix);
     p.tail = afi_opt(cx, AFI_OPT_D_FUSE_TAIL) != 0 && !(F[3] & 15) && F[3] <= 1024;
-    p.fold = p.wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FOLD_BN_APPLY) != 0;
     const int dtype = cx ? cx->dtype : afi_default_dtype();
     p.fwd_amax = p.wino;
     p.bwd_amax = p.wino && dtype == AFI_DTYPE_F16X3;
     p.x_amax = p.wino && training == 1 && disc_local_sums(cx, 0) && dtype == AFI_DTYPE_F16X3 && afi_opt(cx, AFI_OPT_F16_PRESPLIT) != 0 && !(F[0] & 31);
-    p.fuse_bsums = p.wino && halves == 1 && afi_opt(cx, AFI_OPT_D_FUSE_BWD_SUMS) != 0;
     int keep_mask = 0;
     for (int n = 0; n < 3; ++n) {
         DiscPlan::Block& b = p.b[n];
@@ -1863,9 +1728,8 @@ static DiscPlan disc_plan(const afi_ctx* cx, const int F[4], int N, int H, int W
         b.wgrad = wino_form(cx, N, H, W, F[n], F[n + 1], kWinoWgrad);
         b.local_sums = training == 1 && disc_local_sums(cx, n);
         b.stats = p.wino && training && halves == 1 && afi_opt(cx, AFI_OPT_BN_STATS_FP64) != 0 && afi_wino_stats_rows(b.fwd.T, F[n + 1]) > 0;
-        const bool can_keep = n > 0 && training == 1 && p.wino && b.fwd.keep && b.wgrad.keep;
-        b.keep = can_keep && (!p.fold || p.b[n - 1].stats);
-        if (can_keep) keep_mask |= 1 << n;               // (a paired call never folds: it keeps wherever the forms allow)
+        b.keep = n > 0 && training == 1 && p.wino && b.fwd.keep && b.wgrad.keep;
+        if (b.keep) keep_mask |= 1 << n;
     }
     p.ws = disc_ws(F, N, H, W, keep_mask, !p.tail);
     p.bws = disc_bwd_ws(F, N, H, W);
@@ -1888,7 +1752,7 @@ int afi_discriminator_ws_layout(const int F[4], int N, int H, int W, long long* 
 int afi_discriminator_saved_activations(const afi_ctx_t* ctx, const int F[4], int N, int H, int W) {
     if (!F || N <= 0 || H <= 0 || W <= 0) return -1;
     const DiscPlan p = disc_plan(ctx, F, N, H, W, 1, 1);
-    return (p.fold ? 0 : 3) | (p.tail ? 0 : 4);            // (y[2]: read by the last conv only)
+    return 3 | (p.tail ? 0 : 4);                           // (y[2]: read by the last conv only)
 }
 long long afi_discriminator_bwd_ws_floats(const int F[4], int N, int H, int W) { return disc_bwd_ws(F, N, H, W).total; }
 
@@ -1924,9 +1788,8 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
     const long long P = l.P;
     float* red = ws + l.o_red;
     AfiView in = V(xv);
-    const bool wino = pl.wino, fold = pl.fold, tail = pl.tail;
+    const bool wino = pl.wino, tail = pl.tail;
     const long long Ph = P / halves;
-    AfiBnLoad in_bn{nullptr, nullptr, nullptr, nullptr};
     float* amax = ws + l.o_amax;                            // (DiscPlan::fwd_amax)
     if (pl.fwd_amax && hipMemsetAsync(amax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
     bool in_known = false;                                  // block n's input maximum is published before its transform runs
@@ -1942,12 +1805,10 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
         int stats_rows = 0;
         double* stats = (double*)(ws + l.o_stats);          // (8-byte aligned: every offset of the layout is a multiple of 4 floats and ws comes from an allocator)
         const bool fuse_stats = b.stats && (((uintptr_t)stats) & 7) == 0;
-        const bool fold_n = fold && n < 2;                  // this block's activation is never written: its readers evaluate it
         if (wino) {
             if (b.keep && !in_known) return AFI_ERR_LAUNCH; // (the plan promised a known maximum: never hand the backward planes this pass cannot split)
             WinoConvOpt o;
-            if (fuse_stats) { o.stats = stats; o.stats_rows = &stats_rows; o.stats_mm = fold_n ? ws + l.o_stats_mm : nullptr; }
-            o.in_bn = in_bn.mean ? &in_bn : nullptr;
+            if (fuse_stats) { o.stats = stats; o.stats_rows = &stats_rows; }
             o.in_amax = pl.fwd_amax ? amax + 4 * n : nullptr; o.in_amax_known = in_known;
             o.v_keep = b.keep ? ws + l.o_vkeep[n] : nullptr; o.local_sums = b.local_sums;
             AFI_TRY(wino_conv(cx, b.fwd.kind, in, N, H, W, ci, prm->w[n], co, prm->b[n], dense_view(c, H, W, co), null_view(), ws + l.o_wino, l.n_wino, part_,
@@ -1955,8 +1816,8 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
         } else {
             AFI_TRY(PG(conv_fwd_desc(in, N, H, W, ci, prm->w[n], prm->b[n], co, dense_view(c, H, W, co)), 0));
         }
-        // nothing reads the last block's activation / the next block reads c through the affine / the last conv does
-        const bool skip_apply = (stats_only && n == 2) || fold_n || (n == 2 && tail);
+        // nothing reads the last block's activation / the last conv reads c through the affine
+        const bool skip_apply = (stats_only && n == 2) || (n == 2 && tail);
         const float* mean_used = mean;
         if (!training) {
             AFI_TRY(afi_launch_invstd(prm->running_var[n], invstd, co, st));
@@ -1970,10 +1831,6 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
             if (training && stats_rows > 0) {               // the output transform accumulated the sums while it stored c: only the finalizer is left
                 AFI_TRY(afi_launch_bn_stats_from_partials(stats, stats_rows, P, co, mean, invstd, nullptr, prm->running_mean[n], prm->running_var[n], st,
                                                           prm->num_batches_tracked[n]));
-                if (fold_n && pl.fwd_amax) {                      // ... and, the apply pass being folded away, the activation's maximum from the extremes of c
-                    AFI_TRY(afi_launch_bn_act_amax(ws + l.o_stats_mm, stats_rows, co, mean, invstd, prm->gamma[n], prm->beta[n], AFI_LRELU_SLOPE, amax + 4 * (n + 1), st));
-                    in_known = true;
-                }
             } else if (training) {
                 AFI_TRY(afi_launch_bn_stats(ch, Ph, co, mean_h, invstd_h, nullptr, prm->running_mean[n], prm->running_var[n], red, st,
                                             prm->num_batches_tracked[n], -1.f, -1.f, afi_opt(cx, AFI_OPT_BN_STATS_FP64) != 0));  // the counter ticks inside the statistics finalizer
@@ -1984,13 +1841,7 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
                 in_known = pl.fwd_amax && n < 2;                 // (published by the pass that wrote the activation)
             }
         }
-        if (fold_n) {
-            in = dense_view(c, H, W, co);
-            in_bn = AfiBnLoad{mean_used, invstd, prm->gamma[n], prm->beta[n]};
-        } else {
-            in = dense_view(y, H, W, co);
-            in_bn = AfiBnLoad{nullptr, nullptr, nullptr, nullptr};
-        }
+        in = dense_view(y, H, W, co);
     }
     if (!stats_only && tail) {   // last conv 3x3 F3 -> 1 (:40-41) reading c2 through block 2's affine + LeakyReLU (y2 is never written), then the 9-tap stencil
         const int F3 = prm->F[3];
@@ -2037,9 +1888,9 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
     //  two A/B pairs on one box -- the chip has no room left beside the GEMMs)
     Fork fk(cx, st, P <= kSideStreamMaxPixels);
     hipStream_t sd = fk.side;                              // weight / bias gradients run beside the data-gradient chain
-    const bool wino = pl.wino, fold = pl.fold, tail = pl.tail;
+    const bool wino = pl.wino, tail = pl.tail;
     const int F3 = prm->F[3];
-    float* gmax = scratch + s.o_amax;                      // (DiscPlan::bwd_amax; folded apply pass or not, the forward filled its slots, xmax)
+    float* gmax = scratch + s.o_amax;                      // (DiscPlan::bwd_amax; the forward filled its slots, xmax)
     const bool bwd_amax = pl.bwd_amax;
     if (bwd_amax && hipMemsetAsync(gmax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
     const float* xmax = ws + l.o_amax;
@@ -2062,8 +1913,6 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
         AFI_TRY(PG(g, 1));
     }
     // ---- conv + BN + LReLU blocks, last first
-    const bool fuse_bsums = pl.fuse_bsums && (((uintptr_t)(scratch + s.o_bsums)) & 7) == 0;
-    int bsums_rows = 0;                               // rows the previous iteration's data gradient left for THIS block (0: the separate pass)
     for (int n = 2; n >= 0; --n) {
         const int ci = prm->F[n], co = prm->F[n + 1];
         float* g_ = scratch + s.o_g[n];               // d(activation of block n)
@@ -2079,12 +1928,6 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
                                                  scratch + s.o_tail, bwd_amax ? gmax + 4 * n : nullptr, st));
                 continue;
             }
-            if (bsums_rows > 0) {                     // (halves == 1) the sums came with g_: finalize + apply
-                AFI_TRY(afi_launch_bn_bwd_from_partials((const double*)(scratch + s.o_bsums), bsums_rows, g_, c, g_, ws + l.o_mean[n], ws + l.o_invstd[n], prm->gamma[n],
-                                                        gr->gamma[n], gr->beta[n], 1.f, P, co, red, st, prm->beta[n],
-                                                        AFI_LRELU_SLOPE, bwd_amax ? gmax + 4 * n : nullptr));
-                continue;
-            }
             AFI_TRY(afi_launch_bn_bwd(g_ + o, c + o, g_ + o, ws + (h ? l.o_mean_b[n] : l.o_mean[n]), ws + (h ? l.o_invstd_b[n] : l.o_invstd[n]), prm->gamma[n],
                                       gr->gamma[n], gr->beta[n], 1.f, Ph, co, red, st, prm->beta[n], AFI_LRELU_SLOPE,
                                       bwd_amax ? gmax + 4 * n : nullptr));                                              // in place: g_ = d(conv output)
@@ -2096,30 +1939,17 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
         // full HBM pass over g_ per layer.  (Eval-mode BN has no backward here; the bias of the last conv is handled above.)
         (void)red2;
         AfiView gy = dense_view(g_, H, W, co);
-        // (Winograd path: the forward never wrote the activations of blocks 0 and 1 -- the input transform reads block n - 1's saved conv
-        //  output through its affine + LeakyReLU, as the forward's did)
-        const bool xin_folded = fold && n > 0;
-        AfiView xin = (n == 0) ? V(xv) : dense_view(ws + (xin_folded ? l.o_c[n - 1] : l.o_y[n - 1]), H, W, ci);
-        AfiBnLoad x_bn{nullptr, nullptr, nullptr, nullptr};
-        if (xin_folded) x_bn = AfiBnLoad{ws + l.o_mean[n - 1], ws + l.o_invstd[n - 1], prm->gamma[n - 1], prm->beta[n - 1]};
+        AfiView xin = (n == 0) ? V(xv) : dense_view(ws + l.o_y[n - 1], H, W, ci);
         if (gr->w[n] && wino) {
             WinoWgradOpt o;
-            o.x_bn = xin_folded ? &x_bn : nullptr;
             if (bwd_amax) { o.dy_amax = gmax + 4 * n; o.x_amax = xmax + 4 * n; }
             o.v_have = pl.b[n].keep ? ws + l.o_vkeep[n] : nullptr;
             AFI_TRY(wino_wgrad(cx, gy, xin, N, H, W, co, ci, gr->w[n], 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
         } else if (gr->w[n]) AFI_TRY(wgrad_launch(cx, conv_wgrad_desc(gy, xin, N, H, W, co, ci, gr->w[n], 1.f), sd));
-        bsums_rows = 0;
         float* gx = n > 0 ? scratch + s.o_g[n - 1] : dx;   // d(activation of block n - 1), or dx
         if (gx && wino) {
             WinoConvOpt o;
             o.in_amax = bwd_amax ? gmax + 4 * n : nullptr; o.in_amax_known = true;
-            AfiBwdSums bs;
-            if (n > 0) {
-                bs = AfiBwdSums{fuse_bsums ? (double*)(scratch + s.o_bsums) : nullptr, ws + l.o_c[n - 1],
-                                AfiBnLoad{ws + l.o_mean[n - 1], ws + l.o_invstd[n - 1], prm->gamma[n - 1], prm->beta[n - 1]}, AFI_LRELU_SLOPE};
-                o.bsums = &bs; o.bsums_rows = &bsums_rows;
-            }
             AFI_TRY(wino_conv(cx, kWinoDgrad, gy, N, H, W, co, prm->w[n], ci, nullptr, dense_view(gx, H, W, ci), null_view(), scratch + s.o_wino, s.n_wino, part_,
                               part_n_, st, o));
         } else if (gx) {

@@ -17,14 +17,13 @@
 #include "afi_common.h"
 #include "afi_launch.h"
 #include "afi_epilogue.h"
-#include "afi_bn.h"
 #include "afi_f16_split.h"
 
 // ---------------------------------------------------------------- largest magnitude of a transform's SOURCE tensor, as a by-product
 // (the f16x3 arithmetic of the batched GEMMs, afi_gemm_f16.h: every plane of a transform is bounded by a constant times this value, and the
-// GEMM derives its power-of-two operand scale from it).  A thread keeps the maximum of what it loads (after the BatchNorm affine, where
-// the tensor is read through one); at the end of its grid-stride walk the block reduces and publishes with ONE conditional atomic max on
-// the bit pattern (non-negative floats order like unsigned integers).  The slot is zero-filled before the launch.
+// GEMM derives its power-of-two operand scale from it).  A thread keeps the maximum of what it loads; at the end of its grid-stride walk
+// the block reduces and publishes with ONE conditional atomic max on the bit pattern (non-negative floats order like unsigned integers).
+// The slot is zero-filled before the launch.
 __device__ __forceinline__ float afi_amax4(float m, f32x4 v) {
     return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
 }
@@ -115,11 +114,10 @@ int afi_launch_wino_weight(const float* w, float* U, int O, int I, int mode, hip
 
 // ---------------------------------------------------------------- input: X (view, [N][H][W][C]) -> V [16][Tpad][C]
 // thread = (tile, channel quad); the 4x4 patch starts at (2*ty - 1, 2*tx - 1), zeros outside the image
-// BN: x is read through a BatchNorm affine + LeakyReLU (AfiBnLoad, afi_bn.h) -- the input is a discriminator block's saved conv output
 // AM: 0 fp32 planes; 1 fp32 planes + the source's largest magnitude raised into *amax; 2 planes split into fp16 pieces with the scales of `bnd`
-template <bool BN, int AM = 0>
+template <int AM = 0>
 __global__ __launch_bounds__(256) void afi_wino_input_kernel(const AfiView x, int N, int H, int W, int C, int Th, int Tw, long long T,
-                                                             long long Tpad, float* __restrict__ Vout, long long ldo, const AfiBnLoad bn, float* amax, const AfiF16Bound bnd) {
+                                                             long long Tpad, float* __restrict__ Vout, long long ldo, float* amax, const AfiF16Bound bnd) {
     constexpr bool AMAX = AM == 1;
     const float src_max = AM == 2 ? bnd.amax[0] : 0.f;
     const int C4 = C >> 2;
@@ -143,8 +141,6 @@ __global__ __launch_bounds__(256) void afi_wino_input_kernel(const AfiView x, in
         }
         const int tx = (int)(t % Tw); const long long r = t / Tw; const int ty = (int)(r % Th); const int n = (int)(r / Th);
         const float* base = x.p + (long long)n * x.sN + c;
-        f32x4 mu, is, ga, be;
-        if constexpr (BN) { mu = *(const f32x4*)(bn.mean + c); is = *(const f32x4*)(bn.invstd + c); ga = *(const f32x4*)(bn.gamma + c); be = *(const f32x4*)(bn.beta + c); }
         f32x4 d[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -153,10 +149,7 @@ __global__ __launch_bounds__(256) void afi_wino_input_kernel(const AfiView x, in
             for (int j = 0; j < 4; ++j) {
                 const int xx = 2 * tx - 1 + j;
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                    v = *(const f32x4*)(base + (long long)yy * x.sH + (long long)xx * x.sW);
-                    if constexpr (BN) v = afi_bn_lrelu(v, mu, is, ga, be, AFI_LRELU_SLOPE);
-                }
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) v = *(const f32x4*)(base + (long long)yy * x.sH + (long long)xx * x.sW);
                 d[i][j] = v;
             }
         }
@@ -184,30 +177,21 @@ __global__ __launch_bounds__(256) void afi_wino_input_kernel(const AfiView x, in
     }
     if constexpr (AMAX) afi_amax_publish(am, amax);
 }
-static inline bool wino_bn_ok(const AfiBnLoad* bn) {
-    return !bn || !bn->mean || (bn->invstd && bn->gamma && bn->beta && !((((uintptr_t)bn->mean) | ((uintptr_t)bn->invstd) | ((uintptr_t)bn->gamma) | ((uintptr_t)bn->beta)) & 15));
-}
 // amax (optional): raised to the largest magnitude of what the launch reads of x (see afi_amax_publish; zero-filled by the caller).
 // pre (optional, instead): the planes are written split into fp16 pieces with the scales pre->amax[0] x pre->cmul[plane] (ldo, C multiples of 32)
 static const AfiF16Bound kNoBound = {nullptr, 0, 0, {0}};
-int afi_launch_wino_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo, const AfiBnLoad* bn, float* amax,
-                          const AfiF16Bound* pre) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || !wino_bn_ok(bn)) return AFI_ERR_BAD_ARG;
+int afi_launch_wino_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo, float* amax, const AfiF16Bound* pre) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return AFI_ERR_BAD_ARG;
     const int Th = (H + 1) / 2, Tw = (W + 1) / 2;
     const long long T = (long long)N * Th * Tw;
     if (Tpad < T) return AFI_ERR_BAD_ARG;
-    const AfiBnLoad off{nullptr, nullptr, nullptr, nullptr};
     const dim3 grid(wino_grid(Tpad * (C >> 2))), blk(256);
     const long long ld = ldo > 0 ? ldo : (long long)C;
-    const bool b = bn && bn->mean;
     if (pre) {
         if (!pre->amax || (ld & 31) || (C & 31) || amax) return AFI_ERR_BAD_ARG;
-        if (b) hipLaunchKernelGGL((afi_wino_input_kernel<true, 2>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, *pre);
-        else hipLaunchKernelGGL((afi_wino_input_kernel<false, 2>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, *pre);
-    } else if (b && amax) hipLaunchKernelGGL((afi_wino_input_kernel<true, 1>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, kNoBound);
-    else if (b) hipLaunchKernelGGL((afi_wino_input_kernel<true, 0>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, kNoBound);
-    else if (amax) hipLaunchKernelGGL((afi_wino_input_kernel<false, 1>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, kNoBound);
-    else hipLaunchKernelGGL((afi_wino_input_kernel<false, 0>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, kNoBound);
+        hipLaunchKernelGGL(afi_wino_input_kernel<2>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, *pre);
+    } else if (amax) hipLaunchKernelGGL(afi_wino_input_kernel<1>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, kNoBound);
+    else hipLaunchKernelGGL(afi_wino_input_kernel<0>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, kNoBound);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 
@@ -275,41 +259,20 @@ int afi_launch_wino_output(const float* M, long long Tpad, int N, int H, int W, 
 // row of partials [2][C]; afi_launch_bn_stats_from_partials sums the rows in a fixed order.  Replaces a full pass over the map
 // (afi_bn_stats_partial_kernel: 1.85 ms of a stage-1 step).
 typedef double f64x4w __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void afi_stats_acc(f64x4w& s0, f64x4w& s1, f32x4& mn, f32x4& mx, f32x4 v) {
+__device__ __forceinline__ void afi_stats_acc(f64x4w& s0, f64x4w& s1, f32x4 v) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { const double d = (double)v[j]; s0[j] += d; s1[j] += d * d; mn[j] = fminf(mn[j], v[j]); mx[j] = fmaxf(mx[j], v[j]); }
+    for (int j = 0; j < 4; ++j) { const double d = (double)v[j]; s0[j] += d; s1[j] += d * d; }
 }
-// the backward sums of one stored float4 (AfiPixGemm::bstats): o = d(loss)/d(activation) at (pixel row, channel quad c), cv the conv output there
-__device__ __forceinline__ void afi_bstats_acc(f64x4w& s0, f64x4w& s1, f32x4 o, f32x4 cv, f32x4 mu, f32x4 is, f32x4 ga, f32x4 be, float slope) {
-    const f32x4 z = afi_bn_affine(cv, mu, is, ga, be);
-    const f32x4 xh = (cv - mu) * is;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double gm = (double)(z[j] > 0.f ? o[j] : o[j] * slope);
-        s0[j] += gm; s1[j] += gm * (double)xh[j];
-    }
-}
-__device__ __forceinline__ void afi_stats_block_write(const AfiPixGemm& p, f64x4w s0, f64x4w s1, f32x4 mn, f32x4 mx, double* dst_rows = nullptr) {
+__device__ __forceinline__ void afi_stats_block_write(const AfiPixGemm& p, f64x4w s0, f64x4w s1) {
     __shared__ f64x4w red[2][256];
-    __shared__ f32x4 redm[2][256];
     const int C4 = p.Ncols >> 2;
     red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-    redm[0][threadIdx.x] = mn; redm[1][threadIdx.x] = mx;
     __syncthreads();
     if ((int)threadIdx.x < C4) {
-        for (int k = threadIdx.x + C4; k < 256; k += C4) {                                           // fixed order: bit-reproducible
-            s0 += red[0][k]; s1 += red[1][k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { mn[j] = fminf(mn[j], redm[0][k][j]); mx[j] = fmaxf(mx[j], redm[1][k][j]); }
-        }
-        double* row = (dst_rows ? dst_rows : p.stats) + (long long)blockIdx.x * 2 * p.Ncols;
+        for (int k = threadIdx.x + C4; k < 256; k += C4) { s0 += red[0][k]; s1 += red[1][k]; }      // fixed order: bit-reproducible
+        double* row = p.stats + (long long)blockIdx.x * 2 * p.Ncols;
         *(f64x4w*)(row + 4 * threadIdx.x) = s0;
         *(f64x4w*)(row + p.Ncols + 4 * threadIdx.x) = s1;
-        if (p.stats_mm && !dst_rows) {                                                                            // (a thread that stored nothing leaves +-inf: neutral)
-            float* mrow = p.stats_mm + (long long)blockIdx.x * 2 * p.Ncols;
-            *(f32x4*)(mrow + 4 * threadIdx.x) = mn;
-            *(f32x4*)(mrow + p.Ncols + 4 * threadIdx.x) = mx;
-        }
     }
 }
 // rows of partials (= blocks) the STATS launch of an output transform over T tiles x C channels uses; 0 = this shape is not fused
@@ -319,23 +282,16 @@ int afi_wino_stats_rows(long long T, int C) {
     if (g > AFI_STATS_MAX_ROWS) g = AFI_STATS_MAX_ROWS;
     return (int)(g < 1 ? 1 : g);
 }
-static bool afi_stats_fusable(const AfiPixGemm& p) { return (p.stats || p.bstats) && (p.Ncols == 256 || p.Ncols == 512 || p.Ncols == 1024); }
+static bool afi_stats_fusable(const AfiPixGemm& p) { return p.stats && (p.Ncols == 256 || p.Ncols == 512 || p.Ncols == 1024); }
 
-// STATS: 0 none, 1 the forward's statistics of the stored output, 2 the BatchNorm-backward sums of it (AfiPixGemm::bstats)
-template <bool SIMPLE, int STATS = 0>
+// STATS: the BatchNorm statistics of the stored output are taken along (AfiPixGemm::stats)
+template <bool SIMPLE, bool STATS = false>
 __global__ __launch_bounds__(256) void afi_wino_output_epi_kernel(const float* __restrict__ Min, long long Tpad, int Th, int Tw, long long T,
                                                                   const AfiPixGemm p) {
     const int C = p.Ncols, C4 = C >> 2;
     const long long total = T * C4;
     const long long plane = Tpad * C;
     f64x4w st0 = {0, 0, 0, 0}, st1 = {0, 0, 0, 0};
-    f32x4 smn = {INFINITY, INFINITY, INFINITY, INFINITY}, smx = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    f32x4 bmu = {0, 0, 0, 0}, bis = bmu, bga = bmu, bbe = bmu;   // STATS == 2: this thread's channel quad never changes along its walk (blockDim % C4 == 0)
-    if (STATS == 2) {
-        const int cq = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) % C4) * 4;
-        bmu = *(const f32x4*)(p.bstats_bn.mean + cq); bis = *(const f32x4*)(p.bstats_bn.invstd + cq);
-        bga = *(const f32x4*)(p.bstats_bn.gamma + cq); bbe = *(const f32x4*)(p.bstats_bn.beta + cq);
-    }
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(e % C4) * 4;
         const long long t = e / C4;
@@ -361,16 +317,12 @@ __global__ __launch_bounds__(256) void afi_wino_output_epi_kernel(const float* _
                 const f32x4 v = (j == 0) ? s[i][0] + s[i][1] + s[i][2] : s[i][1] - s[i][2] - s[i][3];
                 if (SIMPLE) {
                     const f32x4 o = afi_epilogue_store_simple(p, n, yy, xx, c, v);
-                    if (STATS == 1) afi_stats_acc(st0, st1, smn, smx, o);
-                    if (STATS == 2) {
-                        const f32x4 cv = __builtin_nontemporal_load((const f32x4*)(p.bstats_c + (((long long)n * p.H + yy) * p.W + xx) * C + c));
-                        afi_bstats_acc(st0, st1, o, cv, bmu, bis, bga, bbe, p.bstats_slope);
-                    }
+                    if (STATS) afi_stats_acc(st0, st1, o);
                 } else afi_epilogue_store(p, n, yy, xx, c, v);
             }
         }
     }
-    if (STATS) afi_stats_block_write(p, st0, st1, smn, smx, STATS == 2 ? p.bstats : nullptr);
+    if (STATS) afi_stats_block_write(p, st0, st1);
 }
 int afi_launch_wino_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st) {
     AFI_TRY(afi_o16_refused(p));
@@ -378,12 +330,11 @@ int afi_launch_wino_output_epi(const float* M, long long Tpad, const AfiPixGemm&
     const int Th = (p.H + 1) / 2, Tw = (p.W + 1) / 2;
     const long long T = (long long)p.N * Th * Tw;
     if (Tpad < T) return AFI_ERR_BAD_ARG;
-    if (p.stats || p.bstats) {                              // (the caller asked for fused statistics: afi_wino_stats_rows said this shape takes them)
-        if (!afi_epilogue_is_simple_host(p) || !afi_stats_fusable(p) || (p.stats && p.bstats) || (p.bstats && (!p.bstats_c || !p.bstats_bn.mean))) return AFI_ERR_BAD_ARG;
+    if (p.stats) {                                          // (the caller asked for fused statistics: afi_wino_stats_rows said this shape takes them)
+        if (!afi_epilogue_is_simple_host(p) || !afi_stats_fusable(p)) return AFI_ERR_BAD_ARG;
         AfiPixGemm q = p;
         q.stats_rows = afi_wino_stats_rows(T, p.Ncols);
-        if (p.stats) hipLaunchKernelGGL((afi_wino_output_epi_kernel<true, 1>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
-        else hipLaunchKernelGGL((afi_wino_output_epi_kernel<true, 2>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
+        hipLaunchKernelGGL((afi_wino_output_epi_kernel<true, true>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
     } else if (afi_epilogue_is_simple_host(p)) hipLaunchKernelGGL((afi_wino_output_epi_kernel<true>), dim3(wino_grid(T * (p.Ncols >> 2))), dim3(256), 0, st, M, Tpad, Th, Tw, T, p);
     else hipLaunchKernelGGL((afi_wino_output_epi_kernel<false>), dim3(wino_grid(T * (p.Ncols >> 2))), dim3(256), 0, st, M, Tpad, Th, Tw, T, p);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
@@ -602,9 +553,9 @@ __device__ __forceinline__ void wino4_at3(const T m0, const T m1, const T m2, co
 }
 
 // input: X (view) -> V [36][Tpad][C]; the 6x6 patch of tile (ty, tx) starts at (4*ty - 1, 4*tx - 1)
-template <bool BN, int AM = 0>
+template <int AM = 0>
 __global__ __launch_bounds__(256) void afi_wino4_input_kernel(const AfiView x, int N, int H, int W, int C, int Th, int Tw, long long T, long long Tpad,
-                                                              float* __restrict__ Vout, long long ldo, const AfiBnLoad bn, float* amax, const AfiF16Bound bnd) {
+                                                              float* __restrict__ Vout, long long ldo, float* amax, const AfiF16Bound bnd) {
     constexpr bool AMAX = AM == 1;
     const float src_max = AM == 2 ? bnd.amax[0] : 0.f;
     const int C4 = C >> 2;
@@ -623,8 +574,6 @@ __global__ __launch_bounds__(256) void afi_wino4_input_kernel(const AfiView x, i
         }
         const int tx = (int)(t % Tw); const long long r = t / Tw; const int ty = (int)(r % Th); const int n = (int)(r / Th);
         const float* base = x.p + (long long)n * x.sN + c;
-        f32x4 mu, is, ga, be;
-        if constexpr (BN) { mu = *(const f32x4*)(bn.mean + c); is = *(const f32x4*)(bn.invstd + c); ga = *(const f32x4*)(bn.gamma + c); be = *(const f32x4*)(bn.beta + c); }
         f32x4 d[6][6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
@@ -633,10 +582,7 @@ __global__ __launch_bounds__(256) void afi_wino4_input_kernel(const AfiView x, i
             for (int j = 0; j < 6; ++j) {
                 const int xx = 4 * tx - 1 + j;
                 f32x4 v = zero;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                    v = *(const f32x4*)(base + (long long)yy * x.sH + (long long)xx * x.sW);
-                    if constexpr (BN) v = afi_bn_lrelu(v, mu, is, ga, be, AFI_LRELU_SLOPE);
-                }
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) v = *(const f32x4*)(base + (long long)yy * x.sH + (long long)xx * x.sW);
                 d[i][j] = v;
             }
         }
@@ -660,24 +606,18 @@ __global__ __launch_bounds__(256) void afi_wino4_input_kernel(const AfiView x, i
     }
     if constexpr (AMAX) afi_amax_publish(am, amax);
 }
-int afi_launch_wino4_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo, const AfiBnLoad* bn, float* amax,
-                           const AfiF16Bound* pre) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || !wino_bn_ok(bn)) return AFI_ERR_BAD_ARG;
+int afi_launch_wino4_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo, float* amax, const AfiF16Bound* pre) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return AFI_ERR_BAD_ARG;
     const int Th = (H + 3) / 4, Tw = (W + 3) / 4;
     const long long T = (long long)N * Th * Tw;
     if (Tpad < T) return AFI_ERR_BAD_ARG;
-    const AfiBnLoad off{nullptr, nullptr, nullptr, nullptr};
     const dim3 grid(wino_grid(Tpad * (C >> 2))), blk(256);
     const long long ld = ldo > 0 ? ldo : (long long)C;
-    const bool b = bn && bn->mean;
     if (pre) {
         if (!pre->amax || (ld & 31) || (C & 31) || amax) return AFI_ERR_BAD_ARG;
-        if (b) hipLaunchKernelGGL((afi_wino4_input_kernel<true, 2>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, *pre);
-        else hipLaunchKernelGGL((afi_wino4_input_kernel<false, 2>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, *pre);
-    } else if (b && amax) hipLaunchKernelGGL((afi_wino4_input_kernel<true, 1>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, kNoBound);
-    else if (b) hipLaunchKernelGGL((afi_wino4_input_kernel<true, 0>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, *bn, amax, kNoBound);
-    else if (amax) hipLaunchKernelGGL((afi_wino4_input_kernel<false, 1>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, kNoBound);
-    else hipLaunchKernelGGL((afi_wino4_input_kernel<false, 0>), grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, off, amax, kNoBound);
+        hipLaunchKernelGGL(afi_wino4_input_kernel<2>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, *pre);
+    } else if (amax) hipLaunchKernelGGL(afi_wino4_input_kernel<1>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, kNoBound);
+    else hipLaunchKernelGGL(afi_wino4_input_kernel<0>, grid, blk, 0, st, x, N, H, W, C, Th, Tw, T, Tpad, V, ld, amax, kNoBound);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 
@@ -731,20 +671,13 @@ int afi_launch_wino4_weight(const float* w, float* U, int O, int I, int mode, hi
 }
 
 // output: M [36][Tpad][C] -> 4x4 pixels per tile through the descriptor's epilogue
-template <bool SIMPLE, int STATS = 0>
+template <bool SIMPLE, bool STATS = false>
 __global__ __launch_bounds__(256) void afi_wino4_output_epi_kernel(const float* __restrict__ Min, long long Tpad, int Th, int Tw, long long T,
                                                                    const AfiPixGemm p) {
     const int C = p.Ncols, C4 = C >> 2;
     const long long total = T * C4;
     const long long plane = Tpad * C;
     f64x4w st0 = {0, 0, 0, 0}, st1 = {0, 0, 0, 0};
-    f32x4 smn = {INFINITY, INFINITY, INFINITY, INFINITY}, smx = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    f32x4 bmu = {0, 0, 0, 0}, bis = bmu, bga = bmu, bbe = bmu;   // STATS == 2: this thread's channel quad never changes along its walk (blockDim % C4 == 0)
-    if (STATS == 2) {
-        const int cq = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) % C4) * 4;
-        bmu = *(const f32x4*)(p.bstats_bn.mean + cq); bis = *(const f32x4*)(p.bstats_bn.invstd + cq);
-        bga = *(const f32x4*)(p.bstats_bn.gamma + cq); bbe = *(const f32x4*)(p.bstats_bn.beta + cq);
-    }
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(e % C4) * 4;
         const long long t = e / C4;
@@ -769,11 +702,7 @@ __global__ __launch_bounds__(256) void afi_wino4_output_epi_kernel(const float* 
             auto put = [&](int xo, f32x4 v) {
                 if (SIMPLE) {
                     const f32x4 o = afi_epilogue_store_simple(p, n, yy, xo, c, v);
-                    if (STATS == 1) afi_stats_acc(st0, st1, smn, smx, o);
-                    if (STATS == 2) {
-                        const f32x4 cv = __builtin_nontemporal_load((const f32x4*)(p.bstats_c + (((long long)n * p.H + yy) * p.W + xo) * C + c));
-                        afi_bstats_acc(st0, st1, o, cv, bmu, bis, bga, bbe, p.bstats_slope);
-                    }
+                    if (STATS) afi_stats_acc(st0, st1, o);
                 } else afi_epilogue_store(p, n, yy, xo, c, v);
             };
             if (xx < p.W) put(xx, y0);
@@ -782,7 +711,7 @@ __global__ __launch_bounds__(256) void afi_wino4_output_epi_kernel(const float* 
             if (xx + 3 < p.W) put(xx + 3, y3);
         }
     }
-    if (STATS) afi_stats_block_write(p, st0, st1, smn, smx, STATS == 2 ? p.bstats : nullptr);
+    if (STATS) afi_stats_block_write(p, st0, st1);
 }
 int afi_launch_wino4_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st) {
     AFI_TRY(afi_o16_refused(p));
@@ -790,12 +719,11 @@ int afi_launch_wino4_output_epi(const float* M, long long Tpad, const AfiPixGemm
     const int Th = (p.H + 3) / 4, Tw = (p.W + 3) / 4;
     const long long T = (long long)p.N * Th * Tw;
     if (Tpad < T) return AFI_ERR_BAD_ARG;
-    if (p.stats || p.bstats) {
-        if (!afi_epilogue_is_simple_host(p) || !afi_stats_fusable(p) || (p.stats && p.bstats) || (p.bstats && (!p.bstats_c || !p.bstats_bn.mean))) return AFI_ERR_BAD_ARG;
+    if (p.stats) {
+        if (!afi_epilogue_is_simple_host(p) || !afi_stats_fusable(p)) return AFI_ERR_BAD_ARG;
         AfiPixGemm q = p;
         q.stats_rows = afi_wino_stats_rows(T, p.Ncols);
-        if (p.stats) hipLaunchKernelGGL((afi_wino4_output_epi_kernel<true, 1>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
-        else hipLaunchKernelGGL((afi_wino4_output_epi_kernel<true, 2>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
+        hipLaunchKernelGGL((afi_wino4_output_epi_kernel<true, true>), dim3(q.stats_rows), dim3(256), 0, st, M, Tpad, Th, Tw, T, q);
     } else if (afi_epilogue_is_simple_host(p)) hipLaunchKernelGGL((afi_wino4_output_epi_kernel<true>), dim3(wino_grid(T * (p.Ncols >> 2))), dim3(256), 0, st, M, Tpad, Th, Tw, T, p);
     else hipLaunchKernelGGL((afi_wino4_output_epi_kernel<false>), dim3(wino_grid(T * (p.Ncols >> 2))), dim3(256), 0, st, M, Tpad, Th, Tw, T, p);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;

@@ -313,8 +313,8 @@ class Stage1Step:
         self.ctx.set_option(name, value)
         self.bctx.set_option(name, value)
 
-    _PAIRED_OPTIONS = ("winograd", "winograd_f4_backward", "winograd_f4_forward", "d_winograd_min_pixels", "d_fold_bn_apply", "f16_presplit",
-                       "f16_local_sums", "d_fuse_tail", "d_fuse_bwd_sums")
+    _PAIRED_OPTIONS = ("winograd", "winograd_f4_backward", "winograd_f4_forward", "d_winograd_min_pixels", "f16_presplit",
+                       "f16_local_sums", "d_fuse_tail")
 
     def _check_contexts_agree(self) -> None:
         if self.ctx.dtype != self.bctx.dtype:

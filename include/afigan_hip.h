@@ -144,48 +144,31 @@ int afi_ctx_get_compute_dtype(const afi_ctx_t* ctx);
 #define AFI_OPT_G_SMALLMAP6_MAX_PIXELS 9      /* 4096: under AFI_DTYPE_BF16X6 (and channel counts that are multiples of 32) interpolator calls of up to this many
                                                * low-res pixels run the small-map schedule -- column-batched dense blocks, grouped weight gradients, every conv on the
                                                * bf16x6 small-map kernels with pre-split weight images (csrc/smallmap.hip) -- whatever options 5..7 say; 0: options 5..7 alone */
-#define AFI_OPT_G_RDB_CHAIN 10                /* 0 (default): one launch per link of a dense block's chain of 32-channel convs.  1: under the small-map bf16x6
-                                               * schedule the chain (y1 -> y2 -> y3 -> y4 forward, g4 -> g3 -> g2 -> g1 backward; growth rate 32) is ONE launch that
-                                               * recomputes tile halos (afi_rdb_chain6_kernel): three launches per block and direction instead of five, 35 instead of 47
-                                               * per config-1 forward + backward -- measured at break-even (19 us per chain launch against four links of 9 us minus the
-                                               * 11 us GEMM it adds), so off by default; 2 / 3: backward / forward only (A/B) */
-#define AFI_OPT_D_FOLD_BN_APPLY 11            /* 0 (default): every block's BatchNorm apply + LeakyReLU pass writes its activation.  1: where the discriminator's 3x3 convs
-                                               * run in Winograd form the pass of blocks 0 and 1 is folded into the readers of the activation (the next block's input
-                                               * transform, the backward's weight-gradient input transform read the saved conv output through the affine) and the
-                                               * activation is never written (afi_discriminator_saved_activations) -- bit-identical results, one full read + write of
-                                               * the activation less per block, and measured SLOWER: the transforms re-apply the affine on every overlapping tile read
-                                               * (stage-1 step 103.7 against 103.5 ms, 113.6 against 113.2 with every kernel alone on the chip) */
-#define AFI_OPT_DETERMINISTIC 12              /* 0 (default): weight-gradient GEMMs whose pixel range is split over blocks add their partial tiles by fp32 atomics
+#define AFI_OPT_DETERMINISTIC 10              /* 0 (default): weight-gradient GEMMs whose pixel range is split over blocks add their partial tiles by fp32 atomics
                                                * (summation order varies run to run: results agree to ~1e-6, not bit for bit).  1: no weight gradient is split
                                                * over blocks -- the Winograd TN GEMM and the direct weight-gradient kernel run one block per tile over the whole
                                                * pixel range, the interpolator's small-map backward takes the per-layer launches instead of the grouped
                                                * stream-K ones, bias sums take the two-stage fixed-order reduction -- so that two runs from the same state produce
                                                * the same bits (a resumed run continues bit for bit: tests/test_gpu_stage1.py).  Slower: for reproducing, not for speed. */
-#define AFI_OPT_F16_PRESPLIT 13               /* 1 (default): under AFI_DTYPE_F16X3, a Winograd transform whose source tensor's largest magnitude is known before it
+#define AFI_OPT_F16_PRESPLIT 11               /* 1 (default): under AFI_DTYPE_F16X3, a Winograd transform whose source tensor's largest magnitude is known before it
                                                * runs (the discriminator's activations and gradients: published by the BatchNorm passes that write them) writes
                                                * its planes already split into the two fp16 pieces and the GEMM stages them by DMA alone.  0: every plane is
                                                * written in fp32 and split when the GEMM reads its fragments (same results; stage-1 step 86.6 against 84.4 ms) */
-#define AFI_OPT_F16_NT256_MIN_TILES 14        /* 512: the f16x3 NT GEMM takes its 256 x 256 tile (sixteen waves per block, half the operand bytes per product)
+#define AFI_OPT_F16_NT256_MIN_TILES 12        /* 512: the f16x3 NT GEMM takes its 256 x 256 tile (sixteen waves per block, half the operand bytes per product)
                                                * from this many tiles on (and 256-column multiples); 0: never (the 128 x 128 tile everywhere) */
-#define AFI_OPT_F16_LOCAL_SUMS 15             /* under AFI_DTYPE_F16X3, which of the discriminator's forward convs that a backward follows (training == 1: their rounding
+#define AFI_OPT_F16_LOCAL_SUMS 13             /* under AFI_DTYPE_F16X3, which of the discriminator's forward convs that a backward follows (training == 1: their rounding
                                                * decides LeakyReLU masks) sum the three products of every k-step in a fresh fragment and add that fragment to the
                                                * accumulator with ONE fp32 addition, instead of three accumulating MFMAs: bit n + 1 = block n, 1 = every block, 0 = none.
                                                * Same products, fewer roundings of the large accumulator (an fp32 accumulate rounds at the accumulator's magnitude,
                                                * whatever the addend).  Pre-split planes and 256-column multiples only (blocks 1 and 2 at the reference's widths; other
                                                * shapes keep the plain order).  Default and measurements: DESIGN.md 0 / 4b */
-#define AFI_OPT_D_FUSE_TAIL 16                /* 1 (default): the discriminator's last block and last conv (F3 -> 1, F3 <= 1024, F3 % 16 == 0) run fused -- the last conv reads the
+#define AFI_OPT_D_FUSE_TAIL 14                /* 1 (default): the discriminator's last block and last conv (F3 -> 1, F3 <= 1024, F3 % 16 == 0) run fused -- the last conv reads the
                                                * block's saved conv output through its BatchNorm affine + LeakyReLU (the activation y[2] is never written:
                                                * afi_discriminator_saved_activations), and the block's BatchNorm backward GENERATES the gradient with respect to that
                                                * activation from the nine logit gradients of each pixel instead of reading it, taking the last conv's weight gradient
                                                * along: at 2 x 200 x 336 x 1024, 1.1 GB less traffic per forward and 2.2 GB less per backward.  Same decisions of
                                                * the LeakyReLU masks (the pinned affine), sums in another order.  0: the separate passes of rounds 1-5 */
-#define AFI_OPT_D_FUSE_BWD_SUMS 17            /* 0 (default).  1: where the discriminator's data gradients run in Winograd form (and the call is not a paired one), the output
-                                               * transform that writes the gradient with respect to a block's activation also takes that block's two BatchNorm-backward
-                                               * sums (the LeakyReLU' mask and the normalised value recomputed from the saved conv output, fp64 partial rows), so the
-                                               * separate sums pass -- one read of the gradient and one of the conv output -- becomes one read of the conv output.
-                                               * Same gradients to fp32 rounding; measured: the transform with the sums takes 213 us more per call where the pass it
-                                               * replaces took 185 (2 x 200 x 336, four calls per step), 69.5-69.7 against 69.1-69.5 ms per step -- off */
-#define AFI_OPT_COUNT 18
+#define AFI_OPT_COUNT 15
 int afi_ctx_set_option(afi_ctx_t* ctx, int option, long long value);
 long long afi_ctx_get_option(const afi_ctx_t* ctx, int option);
 /* The batched "NT" GEMM those convolutions run on, for tests and micro-benchmarks:  C[g][m][n] = sum_k A[g][m][k] * B[g][n][k] over
@@ -273,7 +256,7 @@ long long afi_discriminator_fwd_ws_floats(const int F[4], int N, int H, int W);
 /* ABI v7.  The same for ONE context and ONE kind of call (`training` as afi_discriminator_fwd takes it): what that call really writes.  The
  * context-free query above is an upper bound for every context and mode -- it reserves the F(4x4) input planes a training forward of blocks 1 and
  * 2 may keep for its backward's weight gradient (36 x tiles x F[n] floats each: 0.6 + 1.25 GB at 2x200x336) -- this one reserves them only
- * where the context's arithmetic, AFI_OPT_WINOGRAD_F4_FORWARD / F16_PRESPLIT / D_FOLD_BN_APPLY and training == 1 make the forward keep them
+ * where the context's arithmetic, AFI_OPT_WINOGRAD_F4_FORWARD / F16_PRESPLIT and training == 1 make the forward keep them
  * (the default context: block 2 only).  Likewise the last block's activation y[2] (P x F[3] floats, the largest tensor of the network) is reserved
  * only where it is written: not under AFI_OPT_D_FUSE_TAIL (ABI v8: 0.55 GB per workspace at 2 x 200 x 336 x 1024).  Every offset that
  * afi_discriminator_ws_layout reports is the same either way (y[2] sits behind the fixed regions, the kept planes behind it), and a workspace
@@ -284,14 +267,11 @@ long long afi_discriminator_bwd_ws_floats(const int F[4], int N, int H, int W);
  * workspace: off12 = { c[0..2] conv outputs [P][F(n+1)], y[0..2] activations, mean[0..2], invstd[0..2] }.  For parity tooling
  * (tests feed the reference's saved activations to the backward; feature_patch_discriminator.py:35-38) and activation checkpoints. */
 int afi_discriminator_ws_layout(const int F[4], int N, int H, int W, long long* off12);
-/* Which activations the forward really writes, as a bit mask (bit n: y[n]).  Under AFI_OPT_D_FOLD_BN_APPLY = 1, where the 3x3 convs run in
- * Winograd form (maps of at least AFI_OPT_D_WINOGRAD_MIN_PIXELS pixels, AFI_OPT_WINOGRAD on), the activations of blocks 0 and 1 are NEVER
- * written: the next block's input
- * transform -- and the backward's weight-gradient input transforms -- read the saved conv output c[n] through the block's BatchNorm affine
- * and LeakyReLU, y = lrelu_0.2(((c - mean) * invstd) * gamma + beta) with every operation rounded to fp32 on its own (the arithmetic the
- * apply pass has; a reader of the workspace reproduces y[n] bit for bit from c[n], mean[n], invstd[n] and the block's gamma / beta that
- * way: tests/d_parity_util.py).  Bits 0 and 1 are clear there and set everywhere else (the default).  Bit 2 (y[2], which only the last conv
- * reads) is clear under AFI_OPT_D_FUSE_TAIL (the default: the mask is 3; 7 with that option off).
+/* Which activations the forward really writes, as a bit mask (bit n: y[n]).  Bits 0 and 1 are always set.  Bit 2 (y[2], which only the last
+ * conv reads) is clear under AFI_OPT_D_FUSE_TAIL (the default: the mask is 3; 7 with that option off): the last conv then reads the saved conv
+ * output c[2] through the block's BatchNorm affine and LeakyReLU, y = lrelu_0.2(((c - mean) * invstd) * gamma + beta) with every operation
+ * rounded to fp32 on its own (the arithmetic the apply pass has; a reader of the workspace reproduces y[2] bit for bit from c[2], mean[2],
+ * invstd[2] and the block's gamma / beta that way: tests/d_parity_util.py).
  * ctx may be NULL (defaults).
  * afi_discriminator_bwd must run under the same options as its forward. */
 int afi_discriminator_saved_activations(const afi_ctx_t* ctx, const int F[4], int N, int H, int W);
@@ -331,8 +311,7 @@ int afi_discriminator_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const af
  * Winograd plane -- a half whose largest magnitude lies 2^k below the other's keeps 22 - k significand bits in the FIRST conv; behind it every
  * BatchNorm has normalised the halves separately.  Pair tensors of like scale, as D(real) / D(fake) under an L1 term are).
  * Workspace sizes are those of the N-image call; `logits` / `dlogits` are [N, H, W]; the parameter gradients of both halves add up, as
- * two backward calls would leave them.  The second half's batch statistics sit behind the layout afi_discriminator_ws_layout reports.
- * Not available under AFI_OPT_D_FOLD_BN_APPLY (AFI_ERR_UNSUPPORTED). */
+ * two backward calls would leave them.  The second half's batch statistics sit behind the layout afi_discriminator_ws_layout reports. */
 int afi_discriminator_fwd_paired(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t x, int N, int H, int W, float* logits, int training,
                                  float* ws, long long ws_floats, void* stream);
 int afi_discriminator_bwd_paired(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc_params_t* grads, afi_view_t x, int N, int H, int W,

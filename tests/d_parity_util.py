@@ -39,7 +39,7 @@ def fwd_ref(x, p, dt):
 def activation_from_saved(c, mean, invstd, gamma, beta, slope=0.2):
     """A block's activation from what the forward keeps: lrelu(((c - mean) * invstd) * gamma + beta), every operation rounded to fp32 on its own
     (csrc/afi_bn.h) -- plain fp32 tensor ops reproduce the library's value bit for bit.  c: [N, C, H, W] (any strides); the vectors [C].
-    Where the 3x3 convs run in Winograd form the library never writes the activations of blocks 0 and 1
+    Under the fused tail the library never writes the activation of block 2
     (include/afigan_hip.h: afi_discriminator_saved_activations) and every reader goes through this."""
     bc = lambda v: v.view(1, -1, 1, 1)
     z = ((c - bc(mean)) * bc(invstd)) * bc(gamma) + bc(beta)

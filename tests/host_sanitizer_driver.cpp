@@ -9,7 +9,7 @@
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "host sanitizer driver: FAILED %s (line %d)\n", #c, __LINE__); return 1; } } while (0)
 
 int main() {
-    CHECK(afi_abi_version() == 8);
+    CHECK(afi_abi_version() == 9);
     CHECK(std::strlen(afi_build_id()) > 0);
     for (int s = -1; s < 8; ++s) CHECK(afi_status_string(s) != nullptr);
     // workspace layouts over a sweep of shapes (small maps, the Winograd thresholds, the benchmark's five levels, odd sizes)

@@ -139,7 +139,7 @@ def test_entry_point_return_codes():
     from afigan_amd import _lib
     lib = _lib.load()
     OK, BAD, UNS = 0, _lib.DEFINES["AFI_ERR_BAD_ARG"], _lib.DEFINES["AFI_ERR_UNSUPPORTED"]
-    assert _lib.ABI_VERSION == 8 and lib.afi_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.afi_abi_version() == 9
     p, odd = 0x1000, 0x1001
     box = lib.afi_coco_box_iou
     assert box(p, p, p, p, p, p, 0, 0, p, None) == OK and box(p, p, p, p, p, p, 3, 0, p, None) == OK          # nothing to do

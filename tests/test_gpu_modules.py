@@ -476,43 +476,6 @@ def test_discriminator_stats_only_forward_has_the_same_side_effects(amd, shape):
     assert not torch.equal(states[2][1], torch.full_like(states[2][1], 7.0)) and torch.equal(states[3][1], torch.full_like(states[3][1], 7.0))
 
 
-def test_generator_chain_kernel_schedule_matches_the_per_link_schedule(amd):
-    """Option g_rdb_chain (off by default): a dense block's chain of 32-channel convs as ONE launch that recomputes tile halos
-    (csrc/smallmap.hip: afi_rdb_chain6_kernel; generator_rdb.py:64-71 and its backward).  Same products as the per-link launches in another
-    order, so at config-1 size every output, the input gradient and all 23 parameter gradients of the two schedules agree to fp32 rounding
-    (measured 6e-7; a LeakyReLU decision that rounding flips would show as ~1e-3: none on this input), forward-only / backward-only included."""
-    import ctypes as C
-    from afigan_amd import _lib, ops
-    lib = _lib.load()
-    N, H, W = 1, 25, 34
-    torch.manual_seed(0)
-    G = amd.Generator(n_residual_dense_blocks=3).cuda()
-    x = ops.pixel_major(torch.randn(N, 256, H, W).cuda())
-    params = G._ordered_params()
-    prm, _keep = G._param_struct(params)
-    nf = lib.afi_generator_fwd_ws_floats(256, 32, 3, N, H, W)
-    nb = lib.afi_generator_bwd_ws_floats(256, 32, 3, N, H, W)
-    dout = ops.new_pixel_major(N, 256, 2 * H, 2 * W, "cuda"); dout.normal_()
-    cx = _lib.Ctx()
-    res = {}
-    with _lib.use_ctx(cx):
-        for mode in (0, 1, 2, 3):
-            cx.set_option("g_rdb_chain", mode)
-            ws, sc = torch.zeros(nf, device="cuda"), torch.zeros(nb, device="cuda")
-            grads = [torch.zeros_like(p) for p in params]
-            gst, _ = G._param_struct(grads, already_packed=True)
-            out = ops.new_pixel_major(N, 256, 2 * H, 2 * W, "cuda"); dx = ops.new_pixel_major(N, 256, H, W, "cuda")
-            st = ops.stream_ptr()
-            _lib.call("afi_generator_fwd", C.byref(prm), ops.view_of(x), N, H, W, ops.view_of(out), C.c_void_p(ws.data_ptr()), nf, st)
-            _lib.call("afi_generator_bwd", C.byref(prm), C.byref(gst), ops.view_of(x), N, H, W, C.c_void_p(ws.data_ptr()), C.c_void_p(dout.data_ptr()),
-                      C.c_void_p(dx.data_ptr()), C.c_void_p(sc.data_ptr()), nb, st)
-            torch.cuda.synchronize()
-            res[mode] = [out.clone(), dx.clone()] + [g.clone() for g in grads]
-    for mode in (1, 2, 3):
-        for i, (a, b) in enumerate(zip(res[mode], res[0])):
-            assert _rel(a, b) < 2e-5, (mode, i)
-
-
 @pytest.mark.parametrize("F0,N,H,W,train", [(256, 2, 13, 21, 1), (256, 2, 50, 84, 1), (256, 1, 32, 40, 0), (16, 2, 9, 11, 1), (96, 1, 17, 5, 1)])
 def test_discriminator_fused_tail_is_the_same_network(amd, F0, N, H, W, train):
     """Option d_fuse_tail (default on): block 2's BatchNorm apply + LeakyReLU, the last conv and their backward without y[2] and without the
@@ -575,11 +538,13 @@ def test_discriminator_fused_tail_is_the_same_network(amd, F0, N, H, W, train):
 
 
 @pytest.mark.parametrize("N,H,W", [(2, 50, 84), (1, 40, 36)])
-def test_discriminator_bn_backward_sums_taken_by_the_data_gradient_are_the_same_network(amd, N, H, W):
-    """Option d_fuse_bwd_sums (off by default: measured, no gain): the Winograd output transform that writes d(loss)/d(activation of block n) also accumulates block
-    n's two BatchNorm-backward sums (mask and normalised value recomputed from the saved conv output, fp64 rows), instead of a separate pass over
-    both tensors (csrc/winograd.hip: AfiPixGemm::bstats; feature_patch_discriminator.py:35-38 is the block).  Against the separate pass:
-    the same masks, sums in another order and width -- every gradient to fp32 rounding.  8400 pixels: F(4x4) data gradients; 1440: F(2x2)."""
+def test_discriminator_winograd_forward_backward_reads_nothing_it_did_not_write(amd, N, H, W):
+    """The default Winograd forward + backward of the discriminator (feature_patch_discriminator.py:35-41) on a forward workspace AND a backward
+    scratch filled with NaN: whatever a pass reads of either, it wrote before -- logits, the input gradient and every parameter gradient come
+    out finite, and the gradients of the conv biases that feed a train-mode BatchNorm are exactly zero (nets.hip: disc_bwd adds nothing to
+    them).  The forward writes the activations of blocks 0 and 1 (afi_discriminator_saved_activations: 3; y[2] is the fused tail's) and the
+    context's own workspace query stays inside the context-free one.  8400 pixels: F(4x4) gradients, block 2's forward planes kept for the
+    backward; 1440: F(2x2)."""
     import ctypes as C
     from afigan_amd import _lib, ops
     lib = _lib.load()
@@ -592,83 +557,35 @@ def test_discriminator_bn_backward_sums_taken_by_the_data_gradient_are_the_same_
     params = net._ordered_params()
     Fa = (C.c_int * 4)(*net.F)
     nf, nb = lib.afi_discriminator_fwd_ws_floats(Fa, N, H, W), lib.afi_discriminator_bwd_ws_floats(Fa, N, H, W)
-    res = {}
-    for flag in (0, 1):
-        cx = _lib.Ctx()
-        cx.set_option("d_fuse_bwd_sums", flag)
-        cx.set_option("deterministic", 1)
-        with _lib.use_ctx(cx):
-            prm, keep = net._param_struct(params)
-            grads = [torch.zeros_like(t) for t in keep]
-            gst, _k2 = net._param_struct(grads, already_packed=True, grads=True)
-            ws, sc = torch.full((nf,), float("nan"), device="cuda"), torch.full((nb,), float("nan"), device="cuda")
-            logits = torch.empty(N * H * W, device="cuda")
-            dx = ops.new_pixel_major(N, 256, H, W, "cuda")
-            st = ops.stream_ptr()
-            _lib.call("afi_discriminator_fwd", C.byref(prm), ops.view_of(x), N, H, W, C.c_void_p(logits.data_ptr()), 1, C.c_void_p(ws.data_ptr()), nf, st)
-            _lib.call("afi_discriminator_bwd", C.byref(prm), C.byref(gst), ops.view_of(x), N, H, W, C.c_void_p(ws.data_ptr()), C.c_void_p(dl.data_ptr()),
-                      C.c_void_p(dx.data_ptr()), C.c_void_p(sc.data_ptr()), nb, st)
-            torch.cuda.synchronize()
-        res[flag] = (dx.clone(), [g.clone() for g in grads])
-    assert bool(torch.isfinite(res[1][0]).all())
-    assert _rel(res[1][0], res[0][0]) < 1e-5, "input gradient"
-    for i, (a, b) in enumerate(zip(res[1][1], res[0][1])):
-        if float(b.abs().max()) == 0.0:
-            assert float(a.abs().max()) == 0.0, i
-        else:
-            assert _rel(a, b) < 2e-5, i
-
-
-@pytest.mark.parametrize("N,H,W", [(1, 32, 40), (2, 50, 84)])
-def test_discriminator_bn_apply_folded_into_its_readers_is_the_same_network(amd, N, H, W):
-    """Option d_fold_bn_apply: under the Winograd path the BatchNorm apply + LeakyReLU of blocks 0 and 1 is evaluated by the READERS of the
-    activation (the next block's input transform, the backward's weight-gradient input transform) on the saved conv output, with the arithmetic
-    of the apply pass -- the activation is never written (feature_patch_discriminator.py:35-38).  Round 6: the activation's largest magnitude,
-    which the f16x3 transforms need BEFORE they run to write their planes split into fp16 pieces, comes from the conv output's per-channel
-    minimum / maximum (accumulated by the output transform beside the fused statistics): the affine is monotonic per channel, so that is the
-    exact value the apply pass would have published -- same scales, same planes.  Logits and the input gradient must come out bit for bit,
-    parameter gradients to the run-to-run spread of the split-K atomics; the workspace query reports which activations exist.  1280 pixels:
-    F(2x2) everywhere; 8400 pixels: the F(4x4) forward of block 2 with its planes kept for the backward, F(4x4) gradients."""
-    import ctypes as C
-    from afigan_amd import _lib, ops
-    lib = _lib.load()
-    torch.manual_seed(3)
-    D = amd.Discriminator(in_filters=256).cuda()
-    D.train()
-    net = D.Discriminators[0]
-    x = ops.pixel_major(torch.randn(N, 256, H, W).cuda())
-    dl = torch.randn(N * H * W, device="cuda")
-    params = net._ordered_params()
-    Fa = (C.c_int * 4)(*net.F)
-    nf, nb = lib.afi_discriminator_fwd_ws_floats(Fa, N, H, W), lib.afi_discriminator_bwd_ws_floats(Fa, N, H, W)
     off = (C.c_longlong * 12)()
     _lib.call("afi_discriminator_ws_layout", Fa, N, H, W, off)
-    res = {}
-    for flag in (0, 1):
-        cx = _lib.Ctx()
-        cx.set_option("d_fold_bn_apply", flag)
-        assert lib.afi_discriminator_saved_activations(cx.handle, Fa, N, H, W) == (0 if flag else 3)      # (bit 2: never, d_fuse_tail)
-        assert lib.afi_discriminator_fwd_ws_floats_ex(cx.handle, Fa, N, H, W, 1) <= nf
-        with _lib.use_ctx(cx):
-            prm, keep = net._param_struct(params)
-            grads = [torch.zeros_like(t) for t in keep]
-            gst, _k2 = net._param_struct(grads, already_packed=True, grads=True)
-            ws, sc = torch.full((nf,), float("nan"), device="cuda"), torch.zeros(nb, device="cuda")
-            logits = torch.empty(N * H * W, device="cuda")
-            dx = ops.new_pixel_major(N, 256, H, W, "cuda")
-            st = ops.stream_ptr()
-            _lib.call("afi_discriminator_fwd", C.byref(prm), ops.view_of(x), N, H, W, C.c_void_p(logits.data_ptr()), 1, C.c_void_p(ws.data_ptr()), nf, st)
-            y0_written = not bool(torch.isnan(ws[off[3]:off[3] + 8]).any())             # (the folded call never touches y0's region)
-            _lib.call("afi_discriminator_bwd", C.byref(prm), C.byref(gst), ops.view_of(x), N, H, W, C.c_void_p(ws.data_ptr()), C.c_void_p(dl.data_ptr()),
-                      C.c_void_p(dx.data_ptr()), C.c_void_p(sc.data_ptr()), nb, st)
-            torch.cuda.synchronize()
-        assert y0_written == (flag == 0)
-        res[flag] = (logits.clone(), dx.clone(), [g.clone() for g in grads])
-    assert lib.afi_discriminator_saved_activations(None, Fa, N, H, W) == (0 if lib.afi_ctx_get_option(None, _lib.OPTIONS["d_fold_bn_apply"]) else 3)
-    assert torch.equal(res[0][0], res[1][0]), "logits"
-    assert torch.equal(res[0][1], res[1][1]), "input gradient"
-    for i, (a, b) in enumerate(zip(res[0][2], res[1][2])):
-        assert _rel(a, b) < 2e-5, i
+    cx = _lib.Ctx()
+    cx.set_option("deterministic", 1)
+    assert lib.afi_discriminator_saved_activations(None, Fa, N, H, W) == 3                              # (bit 2: never, d_fuse_tail)
+    assert lib.afi_discriminator_saved_activations(cx.handle, Fa, N, H, W) == 3
+    assert lib.afi_discriminator_fwd_ws_floats_ex(cx.handle, Fa, N, H, W, 1) <= nf
+    with _lib.use_ctx(cx):
+        prm, keep = net._param_struct(params)
+        grads = [torch.zeros_like(t) for t in keep]
+        gst, _k2 = net._param_struct(grads, already_packed=True, grads=True)
+        ws, sc = torch.full((nf,), float("nan"), device="cuda"), torch.full((nb,), float("nan"), device="cuda")
+        logits = torch.empty(N * H * W, device="cuda")
+        dx = ops.new_pixel_major(N, 256, H, W, "cuda")
+        st = ops.stream_ptr()
+        _lib.call("afi_discriminator_fwd", C.byref(prm), ops.view_of(x), N, H, W, C.c_void_p(logits.data_ptr()), 1, C.c_void_p(ws.data_ptr()), nf, st)
+        y0_written = not bool(torch.isnan(ws[off[3]:off[3] + 8]).any())
+        _lib.call("afi_discriminator_bwd", C.byref(prm), C.byref(gst), ops.view_of(x), N, H, W, C.c_void_p(ws.data_ptr()), C.c_void_p(dl.data_ptr()),
+                  C.c_void_p(dx.data_ptr()), C.c_void_p(sc.data_ptr()), nb, st)
+        torch.cuda.synchronize()
+    assert y0_written
+    assert bool(torch.isfinite(logits).all()), "logits"
+    assert bool(torch.isfinite(dx).all()), "input gradient"
+    for i, g in enumerate(grads):                           # (w, b, gamma, beta) x 3 blocks, then w3, b3
+        assert bool(torch.isfinite(g).all()), i
+        if i in (1, 5, 9):
+            assert float(g.abs().max()) == 0.0, i
+        else:
+            assert float(g.abs().max()) > 0.0, i
 
 
 def test_interpolator_default_gradient_deviation_not_above_torch_fp32(amd):

@@ -292,7 +292,7 @@ def test_entry_points_check_their_arguments_without_a_device():
     from afigan_amd import _lib
     lib = _lib.load()
     BAD, UNS = _lib.DEFINES["AFI_ERR_BAD_ARG"], _lib.DEFINES["AFI_ERR_UNSUPPORTED"]
-    assert _lib.ABI_VERSION == 8 and lib.afi_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.afi_abi_version() == 9
     ws = lib.afi_mask_rle_ws_bytes
     assert ws(1, 8, 8) == 8 * 8 + 32 and ws(1, 1, 9) == 9 * 8 + 40 and ws(3, 65, 5) == 3 * 2 * 5 * 8 + 64 and ws(0, 8, 8) == 0
     assert ws(200, 800, 1333) == 200 * 13 * 1333 * 8 + 200 * 1333 * 4

@@ -3,7 +3,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 import afigan_amd as amd
-opts = [a for a in sys.argv[1:] if "=" in a]             # name=value: context options set first (e.g. g_rdb_chain=1)
+opts = [a for a in sys.argv[1:] if "=" in a]             # name=value: context options set first (e.g. g_smallmap6_max_pixels=0)
 args = [a for a in sys.argv[1:] if "=" not in a]
 for kv in opts:
     amd._lib.current_ctx().set_option(kv.split("=")[0], int(kv.split("=")[1]))
