@@ -294,7 +294,6 @@ static float* wino_wcache_slot(afi_ctx* cx, const float* w, int f4, int mode, in
 // weights its pixel GEMMs read (forward: K-contiguous; data gradients: row-contiguous), gets every image from the context's weight cache
 // when one is registered (built on first use, found again until the cache is invalidated) or builds it into the call's own workspace, all
 // missing ones in ONE launch, and attaches the image to each GEMM descriptor; a descriptor without an image runs on the fp32-MFMA kernel.
-#define AFI_WG6_WIDE 16                                    // wide weight-gradient problems of one small-map backward pass (7 + one per dense block)
 constexpr long long kWk6MaxPixels = 8192;                  // workspaces reserve the image arena for calls up to this many low-res pixels
 constexpr int kWk6MaxReq = 24;
 // One image request: `key` names it in the cache (with b_rc: 0 forward / K-contiguous weights, 1 data gradient / row-contiguous weights); src:
@@ -1113,9 +1112,9 @@ static GenWs gen_ws(int C, int G, int n_rdb, int N, int H, int W) {
 }
 long long afi_generator_fwd_ws_floats(int C, int G, int n_rdb, int N, int H, int W) { return gen_ws(C, G, n_rdb, N, H, W).total; }
 
-// backward scratch layout: [dU 4P*C][gA P*C][gB P*C][dBuf0 P*L][dBuf1 P*L][dWp 36*C*C][red]
+// backward scratch layout: [dU 4P*C][gA P*C][gB P*C][dBuf P*L per RDB][dWp 36*C*C][red]
 struct GenBwdWs {
-    long long o_du, o_ga, o_gb, o_db0, o_db1, o_dwp, o_rdbw, n_rdbw, o_rdbx, n_rdbx, o_red, o_part, n_part, o_wino, n_wino, o_wino2, o_img, n_img, total;
+    long long o_du, o_ga, o_gb, o_db0, o_dwp, o_rdbw, n_rdbw, o_rdbx, n_rdbx, o_red, o_part, n_part, o_wino, n_wino, o_wino2, o_img, n_img, total;
 };
 static GenBwdWs gen_bwd_ws(int C, int G, int n_rdb, int N, int H, int W) {
     GenBwdWs w;
@@ -1125,7 +1124,6 @@ static GenBwdWs gen_bwd_ws(int C, int G, int n_rdb, int N, int H, int W) {
     w.o_ga = o; o += align4(P * C);
     w.o_gb = o; o += align4(P * C);
     w.o_db0 = o; o += align4((long long)n_rdb * P * L);      // one gradient buffer per RDB: no reuse, so the side-stream wgrads never race a later write
-    w.o_db1 = o;
     w.o_dwp = o; o += align4(36LL * C * C);
     w.n_rdbw = align4(4LL * G * 9 * L);                   // packed weight gradient of a dense block's four growth convs (one per block:
     w.o_rdbw = o; o += (long long)n_rdb * w.n_rdbw;       //  the side stream may still be unpacking block r while block r - 1 is filled)
@@ -1150,26 +1148,148 @@ static int gen_check(const afi_gen_params_t* p) {
     return AFI_OK;
 }
 
+// ---- Which schedule an interpolator call runs: every choice either pass makes, decided once from the context's options and arithmetic and the
+// call's shape (DESIGN.md 4 has the table).  generator_fwd and afi_generator_bwd build the plan at their top and read it.  The two passes need
+// not choose alike: every schedule of the forward leaves the same activations in the same layout, whatever the backward then runs.
+struct GenPlan {
+    GenWs ws;          // the forward's workspace (the backward reads the activations and the packed conv-transpose weight from it)
+    GenBwdWs bws;      // the backward's scratch
+    // the final conv on the up-sampled map (4x the pixels) and its data gradient stay on the small-map kernel, on a weight image, where a pass
+    // builds images at all: at config 1 (50 x 68) the Winograd form is five launches of 9 .. 19 us
+    bool hires_wk6;
+    struct Fwd {
+        // the dense block in COLUMN-BATCHED form: conv_k reads cat(x, y1 .. y_{k-1}); instead of five convs whose K grows (and whose four
+        // 32-column outputs are 27 tiles each, for 256 CUs), five steps whose source is ONE slice: step 0 multiplies x into the columns of all
+        // five convs in one grouped launch (384 columns, K = 9*C), step j = 1..4 multiplies y_j (32 channels, K = 288) into the convs that still
+        // need it; a conv's slice accumulates in place (beta = 1) and is activated by the step that completes it.  Same multiply-adds as
+        // generator_rdb.py:64-71, summed in another order (fp32 rounding only).  AFI_OPT_G_SMALLMAP_MAX_PIXELS = 0 (and, under the six-product
+        // arithmetics, AFI_OPT_G_SMALLMAP6_MAX_PIXELS = 0): conv by conv at every size.
+        bool batched;
+        // the batched form ON WEIGHT IMAGES: its GEMMs, the head / trunk convs and the conv-transpose run on the bf16 matrix cores in the
+        // six-product form, on pre-split weight images (csrc/smallmap.hip).  Asks the arithmetic (bf16x6 / f16x3) and shapes the images take
+        // (GenWs::n_img > 0); AFI_OPT_DETERMINISTIC does not matter here.  Not Bwd::six: that one is about the weight gradients
+        bool six;
+        // larger maps: what the four growth convs take from the block input x is ONE conv C -> 4G on the packed weights [4G][3][3][C]
+        // (Winograd-eligible at the reference's widths; the per-conv form runs four 32-column direct GEMMs 2304+ deep), stored as raw partial
+        // sums in their four slices; conv_k then adds what it takes from y_1 .. y_{k-1} ((k-1) G channels) and activates.  Same multiply-adds,
+        // another order.  (4G <= C: the Winograd scratch is sized for C -> C; every shape of the reference has G = 32, C = 256.)
+        // Deliberately not Bwd::batch_growth's test: this one asks P > AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS, that one !Bwd::grouped, so a
+        // deterministic call at or below that size runs conv by conv forward and batched backward
+        bool xbatch;
+        // value 16 of AFI_OPT_WINOGRAD_F4_FORWARD: the interpolator's own Winograd forwards on F(4x4) as well -- measured, off: DESIGN.md 9
+        bool f4;
+    } fwd;
+    struct Bwd {
+        // Small maps (config-1 sizes): every weight / bias gradient is DEFERRED to the end of the pass and runs as ONE grouped launch per tile
+        // shape (csrc/smallmap.hip: whole dW tiles per block, no split over pixels, no atomics, no zero-fill), instead of one 7 .. 36-tile
+        // launch per layer on a side stream.  All their operands (dOut, dU, gA, gB, the per-block gradient buffers and the saved activations)
+        // stay alive until the call returns.  AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS = 0 (and AFI_OPT_G_SMALLMAP6_MAX_PIXELS = 0) restores the
+        // per-layer launches, and so does AFI_OPT_DETERMINISTIC: the grouped stream-K launches add the tiles two runs share by atomics.
+        // Deliberately not Fwd::batched's test: other options, `<=` where that one has `<`, and the forward does not look at `deterministic`
+        bool grouped;
+        // the grouped weight gradients on the bf16 matrix cores in the six-product form (csrc/smallmap.hip): grouped, under bf16x6 / f16x3
+        bool six;
+        // the data-gradient GEMMs on pre-split weight images: `six`, and shapes the images take (GenBwdWs::n_img > 0)
+        bool images;
+        // under `six` the four growth convs' weight gradients of a block run as ONE 4G-row problem dy[C : C + 4G] (x) cat[0 : L] into a packed
+        // [4G][3][3][L] buffer (1.26x their products, on the 128 x 128 tile of that kernel instead of four 32-row problems on the fp32 one),
+        // unpacked after the group launch -- the grouped form of batch_growth
+        bool pack_growth;
+        // larger maps (per-layer form): a block's four growth-conv weight gradients as one packed GEMM, and what their data gradients leave on
+        // the block input as one 4G -> C data gradient (gen_bwd_block)
+        bool batch_growth;
+        // the per-layer weight / bias gradients beside the data-gradient chain, on the context's side stream.  Not in the grouped form: flushing
+        // the deferred problems onto the side stream after the hi-res pair, after each dense block and at the end was measured: the grouped
+        // launches then run beside the chain, every kernel of which gets slower by about what is gained (1.26 vs 1.19 ms eager, and 1.51 ms
+        // replayed from a hipGraph with its six fork/join edges): the chain's kernels already occupy every CU even where they wait on memory
+        bool side_stream;
+        // the packed conv-transpose gradient and the packed growth-conv gradients are neighbours in the scratch: ONE zero fill for both (the
+        // layout's part of the test; the call adds that the conv-transpose gradient is asked for, and the pointer's alignment)
+        bool one_fill;
+    } bwd;
+};
+constexpr int kGenWideMax = 4 + 2 * AFI_MAX_RDB;    // wide weight-gradient problems of one grouped backward pass with packed growth gradients
+static GenPlan gen_plan(const afi_ctx* cx, int C, int G, int R, int N, int H, int W) {
+    GenPlan p;
+    p.ws = gen_ws(C, G, R, N, H, W);
+    p.bws = gen_bwd_ws(C, G, R, N, H, W);
+    const long long P = p.ws.P;
+    const bool dt6 = afi_dtype_smallmap6(cx ? cx->dtype : afi_default_dtype());
+    const bool growth = afi_opt(cx, AFI_OPT_G_BATCH_GROWTH_GRADS) != 0 && (4 * G <= C || p.ws.n_wino == 0);   // (n_wino: the same in both layouts)
+    p.hires_wk6 = 4 * P <= kWk6HiResMaxPixels;
+    const bool img6 = dt6 && p.ws.n_img > 0;
+    p.fwd.batched = P < afi_opt(cx, AFI_OPT_G_SMALLMAP_MAX_PIXELS) || (img6 && P <= afi_opt(cx, AFI_OPT_G_SMALLMAP6_MAX_PIXELS));
+    p.fwd.six = p.fwd.batched && img6;
+    p.fwd.xbatch = !p.fwd.batched && P > afi_opt(cx, AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS) && growth;
+    p.fwd.f4 = (afi_opt(cx, AFI_OPT_WINOGRAD_F4_FORWARD) & 16) != 0;
+    p.bwd.grouped = !afi_det(cx) && (P <= afi_opt(cx, AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS) || (dt6 && p.bws.n_img > 0 && P <= afi_opt(cx, AFI_OPT_G_SMALLMAP6_MAX_PIXELS)));
+    p.bwd.six = p.bwd.grouped && dt6;
+    p.bwd.images = p.bwd.six && p.bws.n_img > 0;
+    p.bwd.pack_growth = p.bwd.six;                         // (its 4 + 2 R wide problems fit the deferred table: kGenWideMax)
+    p.bwd.batch_growth = !p.bwd.grouped && growth;
+    p.bwd.side_stream = !p.bwd.grouped && 4 * P <= kSideStreamMaxPixels;
+    p.bwd.one_fill = p.bwd.pack_growth && p.bws.o_rdbw == p.bws.o_dwp + align4(36LL * C * C) && (p.bws.n_rdbw & 3) == 0;
+    return p;
+}
+// the weight gradient of a 3x3 conv co <- ci in Winograd form: both channel counts and the map large enough, and the scratch (sized by
+// gen_wino_floats for the call's C -> C, L -> C and C -> 4C convs) holds what this one needs
+static bool gen_wino_wgrad_ok(const afi_ctx* cx, const GenPlan& p, int co, int ci, long long pixels, long long need_floats = 0) {
+    return p.bws.n_wino > 0 && p.bws.n_wino >= need_floats && co >= 128 && ci >= 128 && pixels >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD) != 0;
+}
+// One pixel GEMM of a pass (forward conv or data gradient): Winograd where the conv is eligible and no weight image is attached, else the
+// direct kernels with the call's split-K scratch.  wino / part: in the pass's own workspace; f4: GenPlan::Fwd::f4 (the forward only)
+struct GenPix {
+    afi_ctx* cx; float* wino; long long n_wino; float* part; long long n_part; bool f4; hipStream_t st;
+    int operator()(AfiPixGemm g, int b_rc) const {
+        if (!g.Bimg && n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, wino_form(cx, g, b_rc, f4), wino, n_wino, part, n_part, st);
+        g.partial = part; g.partial_floats = n_part;
+        return afi_launch_pix_gemm(g, b_rc, st);
+    }
+};
+// the weight images of a pass on images (Fwd::six / Bwd::images), in wk6_build's order; returns their number (5 R + 4 at most: kWk6MaxReq).
+// wp: the packed fp32 conv-transpose weight, written by further blocks of the image launch (the pack used to be a launch of its own)
+static int gen_fwd_image_reqs(const GenPlan& p, const afi_gen_params_t* prm, float* wp, Wk6Req* rq) {
+    const int C = prm->C, G = prm->G, L = (int)p.ws.L;
+    int nr = 0;
+    rq[nr++] = wk6_req(prm->w0, prm->w0, C, C, 1, 0, 9LL * C, C);
+    for (int r = 0; r < prm->n_rdb; ++r) {
+        for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; rq[nr++] = wk6_req(prm->rdb_w[r][k - 1], prm->rdb_w[r][k - 1], G, cin, 1, 0, 9LL * cin, cin); }
+        rq[nr++] = wk6_req(prm->rdb_w[r][4], prm->rdb_w[r][4], C, L, 1, 0, 9LL * L, L);
+    }
+    rq[nr++] = wk6_req(prm->w7, prm->w7, C, C, 1, 0, 9LL * C, C);
+    rq[nr] = wk6_req(prm->wT, prm->wT, 4 * C, C, 1, 0, 9LL * C, C);    // the conv-transpose image straight from the parameter's own layout
+    rq[nr].convT = 1; rq[nr].pack_dst = wp; ++nr;
+    if (p.hires_wk6) rq[nr++] = wk6_req(prm->w9, prm->w9, C, C, 1, 0, 9LL * C, C);
+    return nr;
+}
+static int gen_bwd_image_reqs(const GenPlan& p, const afi_gen_params_t* prm, bool want_dx, Wk6Req* rq) {
+    const int C = prm->C, G = prm->G, L = (int)p.ws.L;
+    int nr = 0;
+    rq[nr] = wk6_req(prm->wT, prm->wT, C, C, 4, 1, 9LL * C, C);        // conv-transpose data gradient: K = (Cout chunk, phase, tap), straight from the parameter's layout
+    rq[nr].convT = 2; ++nr;
+    rq[nr++] = wk6_req(prm->w7, prm->w7, C, C, 1, 1, 9LL * C, C);
+    for (int r = 0; r < prm->n_rdb; ++r) {
+        rq[nr++] = wk6_req(prm->rdb_w[r][4], prm->rdb_w[r][4], L, C, 1, 1, 9LL * L, L);
+        for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; rq[nr++] = wk6_req(prm->rdb_w[r][k - 1], prm->rdb_w[r][k - 1], cin, G, 1, 1, 9LL * cin, cin); }
+    }
+    if (want_dx) rq[nr++] = wk6_req(prm->w0, prm->w0, C, C, 1, 1, 9LL * C, C);
+    if (p.hires_wk6) rq[nr++] = wk6_req(prm->w9, prm->w9, C, C, 1, 1, 9LL * C, C);
+    return nr;
+}
+
 // out_dtype (AFI_STORE_*): storage of `out` only -- the final conv's epilogue rounds there; everything before it is fp32
-static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, int out_dtype, float* ws,
+static int generator_fwd(afi_ctx_t* cx, const afi_gen_params_t* prm, afi_view_t xv, int N, int H, int W, afi_view_t outv, int out_dtype, float* ws,
                          long long ws_floats, void* stream) {
-    afi_ctx* cx = ctx; (void)cx;
-    AFI_CTX_CHECK(ctx);
+    AFI_CTX_CHECK(cx);
     AFI_TRY(gen_check(prm));
     if (N <= 0 || H <= 0 || W <= 0 || !ws || !xv.p || !outv.p) return AFI_ERR_BAD_ARG;
     if (out_dtype != AFI_STORE_F32 && out_dtype != AFI_STORE_BF16 && out_dtype != AFI_STORE_F16) return AFI_ERR_BAD_ARG;
     const int C = prm->C, G = prm->G, R = prm->n_rdb;
-    const GenWs l = gen_ws(C, G, R, N, H, W);
+    const GenPlan p = gen_plan(cx, C, G, R, N, H, W);
+    const GenWs& l = p.ws;
     if (ws_floats < l.total) return AFI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float* const part_ = ws + l.o_part;
-    const long long part_n_ = l.n_part;
-    auto PG = [&](AfiPixGemm g, int b_rc) {
-        // (value 16 of AFI_OPT_WINOGRAD_F4_FORWARD: the interpolator's own forwards on F(4x4) as well -- measured, off: DESIGN.md 9)
-        if (!g.Bimg && l.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, wino_form(cx, g, b_rc, (afi_opt(cx, AFI_OPT_WINOGRAD_F4_FORWARD) & 16) != 0), ws + l.o_wino, l.n_wino, part_, part_n_, st);
-        g.partial = part_; g.partial_floats = part_n_;
-        return afi_launch_pix_gemm(g, b_rc, st);
-    };
+    const GenPix PG{cx, ws + l.o_wino, l.n_wino, ws + l.o_part, l.n_part, p.fwd.f4, st};
     const int L = (int)l.L;
     const float rs = prm->residual_scale;
     float* wp = ws + l.o_wp;
@@ -1178,27 +1298,11 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
     AfiView t = dense_view(ws + l.o_t, H, W, C), a7 = dense_view(ws + l.o_a7, H, W, C);
     AfiView u = dense_view(ws + l.o_u, 2 * H, 2 * W, C);
 
-    // Small maps: the dense block in COLUMN-BATCHED form (below); under the default arithmetic its GEMMs, the head / trunk convs and the
-    // conv-transpose run on the bf16 matrix cores in the six-product form, on pre-split weight images (csrc/smallmap.hip)
-    const bool six = l.n_img > 0 && afi_dtype_smallmap6(cx ? cx->dtype : afi_default_dtype());
-    const bool batched = l.P < afi_opt(cx, AFI_OPT_G_SMALLMAP_MAX_PIXELS) || (six && l.P <= afi_opt(cx, AFI_OPT_G_SMALLMAP6_MAX_PIXELS));
     Wk6Images im;
     bool packed = false;                                   // the packed conv-transpose weight `wp` (the backward reads it from this workspace) exists
-    if (batched && six) {
+    if (p.fwd.six) {
         Wk6Req rq[kWk6MaxReq];
-        int nr = 0;
-        rq[nr++] = wk6_req(prm->w0, prm->w0, C, C, 1, 0, 9LL * C, C);
-        for (int r = 0; r < R; ++r) {
-            for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; rq[nr++] = wk6_req(prm->rdb_w[r][k - 1], prm->rdb_w[r][k - 1], G, cin, 1, 0, 9LL * cin, cin); }
-            rq[nr++] = wk6_req(prm->rdb_w[r][4], prm->rdb_w[r][4], C, (int)l.L, 1, 0, 9LL * l.L, l.L);
-        }
-        rq[nr++] = wk6_req(prm->w7, prm->w7, C, C, 1, 0, 9LL * C, C);
-        // the conv-transpose image straight from the parameter's own layout, its packed form written by further blocks of the same launch
-        // (the pack used to be a launch of its own in front of this one)
-        rq[nr] = wk6_req(prm->wT, prm->wT, 4 * C, C, 1, 0, 9LL * C, C);
-        rq[nr].convT = 1; rq[nr].pack_dst = wp; ++nr;
-        if (4 * l.P <= kWk6HiResMaxPixels) rq[nr++] = wk6_req(prm->w9, prm->w9, C, C, 1, 0, 9LL * C, C);
-        AFI_TRY(wk6_build(cx, im, rq, nr, ws + l.o_img, l.n_img, st, nullptr, nullptr, &packed));
+        AFI_TRY(wk6_build(cx, im, rq, gen_fwd_image_reqs(p, prm, wp, rq), ws + l.o_img, l.n_img, st, nullptr, nullptr, &packed));
     }
     if (!packed) {   // packed conv-transpose weight: from the caller's weight cache when one is registered (BiFPN: 28 calls on one set of weights)
         bool hit = false;
@@ -1216,26 +1320,25 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
         im.attach(g, prm->w0);
         AFI_TRY(PG(g, 0));
     }
-    // Small maps: the dense block in COLUMN-BATCHED form.  conv_k reads cat(x, y1 .. y_{k-1}); instead of five convs whose K grows
-    // (and whose four 32-column outputs are 27 tiles each, for 256 CUs), five steps whose source is ONE slice: step 0 multiplies x into
-    // the columns of all five convs in one grouped launch (384 columns, K = 9*C), step j = 1..4 multiplies y_j (32 channels, K = 288)
-    // into the convs that still need it; a conv's slice accumulates in place (beta = 1) and is activated by the step that completes
-    // it.  Same multiply-adds as generator_rdb.py:64-71, summed in another order (fp32 rounding only).  AFI_OPT_G_SMALLMAP_MAX_PIXELS = 0:
-    // conv by conv at every size.
-    // (4G <= C: the Winograd scratch is sized for C -> C; every shape of the reference has G = 32, C = 256)
-    const bool xbatch = !batched && l.P > afi_opt(cx, AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS) && afi_opt(cx, AFI_OPT_G_BATCH_GROWTH_GRADS) != 0 &&
-                        (4 * G <= C || l.n_wino == 0);
     for (int r = 0; r < R; ++r) {   // ResidualDenseBlock.forward (generator_rdb.py:64-71); the dense buffer replaces torch.cat
         AfiView b = buf(r);
         const bool last = (r == R - 1);
-        auto conv5_desc = [&](int c_lo, int nch) {      // conv5 restricted to input channels [c_lo, c_lo + nch)
+        // conv5 restricted to input channels [c_lo, c_lo + nch); on the channels from c_lo = 0 ride the residual terms (no activation follows conv5):
+        // x + rs * conv5, and behind the last block ResidualInResidual.forward (:27-30): rs*(x + rs*conv5) + a0
+        auto conv5_desc = [&](int c_lo, int nch) {
             AfiPixGemm g = conv_fwd_desc(ch_off(b, c_lo), N, H, W, nch, prm->rdb_w[r][4] + c_lo, nullptr, C, last ? t : buf(r + 1));
             g.b_sRow = 9LL * L; g.b_sTap = L;
             g.alpha = last ? rs * rs : rs;
+            if (c_lo == 0) {
+                g.R1 = b; g.r1_lo = 0; g.r1_hi = C; g.r1s = last ? rs : 1.f;
+                if (last) { g.R2 = buf(0); g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C; }
+            } else {
+                g.beta = 1.f;
+            }
             im.attach(g, prm->rdb_w[r][4], c_lo);
             return g;
         };
-        if (batched) {
+        if (p.fwd.batched) {
             for (int j = 0; j <= 4; ++j) {              // source slice j: x (j = 0) or y_j
                 const int c_lo = j == 0 ? 0 : C + (j - 1) * G, nch = j == 0 ? C : G;
                 AfiPixGemm probs[5];
@@ -1249,25 +1352,14 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
                     im.attach(g, prm->rdb_w[r][k - 1], c_lo);
                     probs[n++] = g;
                 }
-                AfiPixGemm g5 = conv5_desc(c_lo, nch);
-                if (j == 0) {                           // residual terms ride on the first step (no activation follows conv5)
-                    g5.R1 = b; g5.r1_lo = 0; g5.r1_hi = C; g5.r1s = last ? rs : 1.f;
-                    if (last) { g5.R2 = buf(0); g5.r2s = 1.f; g5.r2_lo = 0; g5.r2_hi = C; }
-                } else {
-                    g5.beta = 1.f;
-                }
-                probs[n++] = g5;
+                probs[n++] = conv5_desc(c_lo, nch);
                 const int rc = afi_launch_pix_gemm_group(probs, n, 0, st);
                 if (rc == AFI_ERR_UNSUPPORTED) { for (int i = 0; i < n; ++i) AFI_TRY(PG(probs[i], 0)); }   // same step, one launch per conv
                 else AFI_TRY(rc);
             }
             continue;
         }
-        if (xbatch) {
-            // larger maps: what the four growth convs take from the block input x is ONE conv C -> 4G on the packed weights [4G][3][3][C]
-            // (Winograd-eligible at the reference's widths; the per-conv form runs four 32-column direct GEMMs 2304+ deep), stored as raw
-            // partial sums in their four slices; conv_k then adds what it takes from y_1 .. y_{k-1} ((k-1) G channels) and activates.
-            // Same multiply-adds as generator_rdb.py:64-71, summed in another order.
+        if (p.fwd.xbatch) {
             const float* const wk[4] = {prm->rdb_w[r][0], prm->rdb_w[r][1], prm->rdb_w[r][2], prm->rdb_w[r][3]};
             float* Wx = ws + l.o_rdbx + (long long)r * l.n_rdbx;
             bool hit = false, scratch_b = true;
@@ -1291,15 +1383,7 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
             g.lrelu = 1;
             AFI_TRY(PG(g, 0));
         }
-        AfiPixGemm g = conv_fwd_desc(b, N, H, W, L, prm->rdb_w[r][4], nullptr, C, last ? t : buf(r + 1));
-        g.R1 = b; g.r1_lo = 0; g.r1_hi = C;
-        if (!last) {            // x + rs * conv5
-            g.alpha = rs; g.r1s = 1.f;
-        } else {                // ResidualInResidual.forward (:27-30): rs*(x + rs*conv5) + a0
-            g.alpha = rs * rs; g.r1s = rs;
-            g.R2 = buf(0); g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
-        }
-        AFI_TRY(PG(g, 0));
+        AFI_TRY(PG(conv5_desc(0, L), 0));
     }
     {   // trunk conv + LReLU (:97-99)
         AfiPixGemm g = conv_fwd_desc(t, N, H, W, C, prm->w7, prm->b7, C, a7);
@@ -1317,7 +1401,7 @@ static int generator_fwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_view_t
         AfiPixGemm g = conv_fwd_desc(u, N, 2 * H, 2 * W, C, prm->w9, prm->b9, C, V(outv));
         g.R1 = x; g.r1s = 1.f; g.r1_lo = 0; g.r1_hi = C; g.r1_bilinear = 1;
         g.o_dtype = out_dtype;
-        im.attach(g, prm->w9);                              // (small maps only: no image was requested otherwise)
+        im.attach(g, prm->w9);                              // (GenPlan::hires_wk6 only: no image was requested otherwise)
         AFI_TRY(PG(g, 0));
     }
     return AFI_OK;
@@ -1333,278 +1417,252 @@ int afi_generator_fwd_out16(afi_ctx_t* ctx, const afi_gen_params_t* prm, afi_vie
     return generator_fwd(ctx, prm, xv, N, H, W, outv, out_dtype, ws, ws_floats, stream);
 }
 
-int afi_generator_bwd(afi_ctx_t* ctx, const afi_gen_params_t* prm, const afi_gen_params_t* gr, afi_view_t xv, int N, int H, int W, const float* ws,
+// The weight / bias gradients a grouped backward (GenPlan::Bwd::grouped) puts off to its end: one grouped launch per tile shape, then ONE tail
+// launch for the bias gradients, the conv-transpose gradient's unpack and every packed growth-conv gradient.  All on the caller's stream.
+struct GenDeferred {
+    AfiWgradGemm wide[kGenWideMax], narrow[4 * AFI_MAX_RDB];
+    AfiColsumProb cs[8];                                   // (the pass has four biases)
+    int n_wide = 0, n_narrow = 0, n_cs = 0;
+    bool convT = false;                                    // the conv-transpose gradient (packed, in GenBwdWs::o_dwp) is among them
+    unsigned packed_mask = 0;                              // dense blocks whose packed growth-conv gradient (GenBwdWs::o_rdbw) is among them
+    int defer(const afi_ctx* cx, const AfiWgradGemm& g, hipStream_t st) {
+        if (g.Mrows <= 32 && n_narrow < 4 * AFI_MAX_RDB) { narrow[n_narrow++] = g; return AFI_OK; }
+        if (g.Mrows > 32 && n_wide < kGenWideMax) { wide[n_wide++] = g; return AFI_OK; }
+        return wgrad_launch(cx, g, st);                    // table full (unusual shapes): launch it on its own
+    }
+    void defer(const float* g, long long rows, int Cc, long long ld, float* db) { cs[n_cs++] = AfiColsumProb{g, db, rows, ld, Cc, 1.f}; }
+    int flush(const GenPlan& p, const afi_gen_params_t* prm, const afi_gen_params_t* gr, float* scratch, hipStream_t st) {
+        if (n_wide + n_narrow + n_cs == 0 && !convT) return AFI_OK;
+        const int rc6 = p.bwd.six ? afi_launch_wgrad_gemm_group6(wide, n_wide, st) : AFI_ERR_UNSUPPORTED;     // (unsupported: nothing was launched)
+        AFI_TRY(rc6 == AFI_ERR_UNSUPPORTED ? afi_launch_wgrad_gemm_group(wide, n_wide, 1, st) : rc6);
+        AFI_TRY(afi_launch_wgrad_gemm_group(narrow, n_narrow, 0, st));
+        const int C = prm->C, R = prm->n_rdb;
+        float* dws[AFI_MAX_RDB][4];                        // (a block that was not packed: null targets)
+        for (int r = 0; r < R; ++r)
+            for (int k = 0; k < 4; ++k) dws[r][k] = (packed_mask >> r & 1) ? gr->rdb_w[r][k] : nullptr;
+        return afi_launch_g_bwd_tail(cs, n_cs, convT ? scratch + p.bws.o_dwp : nullptr, gr->wT, C, C, scratch + p.bws.o_rdbw, p.bws.n_rdbw, dws, packed_mask ? R : 0,
+                                     C, prm->G, 1.f, st);
+    }
+};
+// what the steps of one backward call share
+struct GenBwd {
+    afi_ctx* cx; const GenPlan& p; const afi_gen_params_t *prm, *gr; int N, H, W; const float* ws; float* scratch; hipStream_t st;
+    GenPix PG;
+    Fork fk;                                               // fk.side: weight / bias gradients of the per-layer form (Bwd::side_stream; else the main stream)
+    GenDeferred df;
+    Wk6Images im;                                          // weight images of the data-gradient GEMMs (row-contiguous weights)
+    // (a constructor, not aggregate initialisation: that would zero the deferred tables, 8 KB per call)
+    GenBwd(afi_ctx* cx_, const GenPlan& p_, const afi_gen_params_t* prm_, const afi_gen_params_t* gr_, int N_, int H_, int W_, const float* ws_, float* scratch_, hipStream_t st_)
+        : cx(cx_), p(p_), prm(prm_), gr(gr_), N(N_), H(H_), W(W_), ws(ws_), scratch(scratch_), st(st_),
+          PG{cx_, scratch_ + p_.bws.o_wino, p_.bws.n_wino, scratch_ + p_.bws.o_part, p_.bws.n_part, false, st_}, fk(cx_, st_, p_.bwd.side_stream) {}
+    AfiView buf(int r) const { return dense_view(ws + p.ws.o_buf + (long long)r * p.ws.P * p.ws.L, H, W, p.ws.L); }               // saved dense buffer of RDB r
+    AfiView dbuf(int r) const { return dense_view(scratch + p.bws.o_db0 + (long long)r * p.ws.P * p.ws.L, H, W, p.ws.L); }        // its gradient
+    // weight gradient of a 3x3 conv (h x w: the low-res or the up-sampled map): deferred, or Winograd F(3x3,2x2) where gen_wino_wgrad_ok, or direct
+    int wgrad(AfiView dy, AfiView xin, int h, int w, int co, int ci, float* dw, float alpha) {
+        if (p.bwd.grouped) return df.defer(cx, conv_wgrad_desc(dy, xin, N, h, w, co, ci, dw, alpha), st);
+        if (gen_wino_wgrad_ok(cx, p, co, ci, (long long)N * h * w)) return wino_wgrad(cx, dy, xin, N, h, w, co, ci, dw, alpha, scratch + p.bws.o_wino2, p.bws.n_wino, fk.side);
+        return wgrad_launch(cx, conv_wgrad_desc(dy, xin, N, h, w, co, ci, dw, alpha), fk.side);
+    }
+    int colsum(const float* g, long long rows, int Cc, long long ld, float* db) {      // bias gradient
+        if (p.bwd.grouped) { df.defer(g, rows, Cc, ld, db); return AFI_OK; }
+        return afi_launch_colsum_accum(g, rows, Cc, ld, 1.f, db, scratch + p.bws.o_red, fk.side);
+    }
+};
+// One dense block backwards (generator_rdb.py:64-71).  Gt: the incoming gradient tensor, true gradient = gs * Gt; gB = dT, the RRDB skip, which
+// block 0 adds.  Channels [0,C) of dbuf(r) leave as the gradient with respect to the block's input
+static int gen_bwd_block(GenBwd& c, int r, AfiView Gt, float gs, AfiView gB) {
+    const GenPlan& p = c.p;
+    const afi_gen_params_t *prm = c.prm, *gr = c.gr;
+    const int N = c.N, H = c.H, W = c.W, C = prm->C, G = prm->G, L = (int)p.ws.L;
+    const float rs = prm->residual_scale;
+    AfiView b = c.buf(r), d = c.dbuf(r);
+    const bool want_growth = gr->rdb_w[r][0] || gr->rdb_w[r][1] || gr->rdb_w[r][2] || gr->rdb_w[r][3];
+    float* const packed = c.scratch + p.bws.o_rdbw + (long long)r * p.bws.n_rdbw;     // [4G][3][3][L]: pack_growth / batch_growth
+    // conv5: out = x + rs*conv5(cat)
+    c.fk.after_main();                                                     // Gt is complete
+    if (gr->rdb_w[r][4]) AFI_TRY(c.wgrad(Gt, b, H, W, C, L, gr->rdb_w[r][4], rs * gs));
+    {
+        AfiPixGemm g = conv_dgrad_desc(Gt, N, H, W, C, prm->rdb_w[r][4], L, d);
+        g.alpha = rs * gs;
+        g.R1 = Gt; g.r1s = gs; g.r1_lo = 0; g.r1_hi = C;               // identity path of the block
+        g.Z = b; g.z_lo = C + 3 * G; g.z_hi = L;                       // conv4's LReLU: its slice is final after this kernel
+        c.im.attach(g, prm->rdb_w[r][4]);
+        AFI_TRY(c.PG(g, 1));
+    }
+    for (int k = 4; k >= 1; --k) {
+        const int cin = C + (k - 1) * G;
+        AfiView dyk = ch_off(d, cin);                                   // d(pre-activation of conv_k), G channels
+        c.fk.after_main();                                                 // dyk's slice was finalised by the previous dgrad
+        if (gr->rdb_w[r][k - 1] && !p.bwd.batch_growth && !p.bwd.pack_growth) {
+            const AfiWgradGemm wd = conv_wgrad_desc(dyk, b, N, H, W, G, cin, gr->rdb_w[r][k - 1], 1.f);
+            AFI_TRY(p.bwd.grouped ? c.df.defer(c.cx, wd, c.st) : wgrad_launch(c.cx, wd, c.fk.side));
+        }
+        if (p.bwd.batch_growth) {
+            // only the part of conv_k's data gradient that lands on y_1 .. y_{k-1} (channels [C, cin): (k-1) G columns) runs here, in chain
+            // order -- each finalises the slice the next one reads; the parts that land on the block input x (channels [0, C)) of all four
+            // convs are ONE data gradient from the 4G adjacent channels dy_1 .. dy_4 after the chain (below)
+            if (k == 1) continue;
+            AfiPixGemm g = conv_dgrad_desc(dyk, N, H, W, G, prm->rdb_w[r][k - 1] + C, cin - C, ch_off(d, C));
+            g.b_sRow = 9LL * cin; g.b_sTap = cin;                       // (a column range of the [G][3][3][cin] weight)
+            g.beta = 1.f;
+            g.Z = ch_off(b, C); g.z_lo = cin - C - G; g.z_hi = cin - C;          // conv_{k-1}'s slice becomes final
+            AFI_TRY(c.PG(g, 1));
+            continue;
+        }
+        AfiPixGemm g = conv_dgrad_desc(dyk, N, H, W, G, prm->rdb_w[r][k - 1], cin, d);
+        g.beta = 1.f;                                                   // dense connections: accumulate
+        if (k >= 2) { g.Z = b; g.z_lo = cin - G; g.z_hi = cin; }        // conv_{k-1}'s slice becomes final
+        if (k == 1 && r == 0) {                                         // RRDB skip (+dT) and the head conv's LReLU
+            g.R2 = gB; g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
+            g.Z = b; g.z_lo = 0; g.z_hi = C;
+        }
+        c.im.attach(g, prm->rdb_w[r][k - 1]);
+        AFI_TRY(c.PG(g, 1));
+    }
+    // (every slice of d[C : C + 4G] is final now; each conv reads a prefix of b: rows of the packed gradient paired with channels behind their
+    //  conv's input are computed and never read by the unpack)
+    if (p.bwd.pack_growth && want_growth) {
+        AFI_TRY(c.df.defer(c.cx, conv_wgrad_desc(ch_off(d, C), b, N, H, W, 4 * G, L, packed, 1.f), c.st));
+        c.df.packed_mask |= 1u << r;
+    }
+    if (p.bwd.batch_growth) {
+        // d[0:C) += sum_k W_k[:, :, :, 0:C]^T (*) dy_k: a 4G -> C data gradient on the packed weights [4G][3][3][C] -- Winograd-eligible at the
+        // reference's widths (128 -> 256 channels) where the four per-conv ones (32 -> 256 .. 352) were direct GEMMs 288 deep
+        const float* const wk[4] = {prm->rdb_w[r][0], prm->rdb_w[r][1], prm->rdb_w[r][2], prm->rdb_w[r][3]};
+        float* Wx = c.scratch + p.bws.o_rdbx + (long long)r * p.bws.n_rdbx;
+        bool hit = false, scratch_b = true;
+        if (float* slot = wino_wcache_slot(c.cx, prm->rdb_w[r][0], /*tag: growth x-part pack*/ 3, 0, 4 * G, C, p.bws.n_rdbx, hit)) { Wx = slot; scratch_b = false; }
+        if (!hit) AFI_TRY(afi_launch_rdb_xpart_pack(wk, Wx, C, G, c.st));
+        AfiPixGemm g = conv_dgrad_desc(ch_off(d, C), N, H, W, 4 * G, Wx, C, d);
+        g.beta = 1.f;
+        g.no_wcache = scratch_b ? 1 : 0;
+        if (r == 0) {                                                   // RRDB skip (+dT) and the head conv's LReLU
+            g.R2 = gB; g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
+            g.Z = b; g.z_lo = 0; g.z_hi = C;
+        }
+        AFI_TRY(c.PG(g, 1));
+    }
+    if (p.bwd.batch_growth && want_growth) {
+        // the four growth convs' weight gradients as ONE product dy[C : C + 4G] (x) cat[0 : L]: a 4G-row GEMM -- Winograd F(3x3,4x4) on the bf16
+        // matrix cores when 4G and L reach 128 channels -- instead of four G-row ones on the 32 x 128 fp32 tile, 1.26x their products at several
+        // times their rate
+        c.fk.after_main();
+        hipStream_t sd = c.fk.side;
+        if (hipMemsetAsync(packed, 0, sizeof(float) * 4LL * G * 9 * L, sd) != hipSuccess) return AFI_ERR_LAUNCH;
+        const AfiView dy4 = ch_off(d, C);
+        WinoWgradOpt o;
+        o.accumulate = false;
+        if (gen_wino_wgrad_ok(c.cx, p, 4 * G, L, p.ws.P, wino_ws_floats(N, H, W, L, 4 * G)))
+            AFI_TRY(wino_wgrad(c.cx, dy4, b, N, H, W, 4 * G, L, packed, 1.f, c.scratch + p.bws.o_wino2, p.bws.n_wino, sd, o));
+        else AFI_TRY(wgrad_launch(c.cx, conv_wgrad_desc(dy4, b, N, H, W, 4 * G, L, packed, 1.f), sd));
+        float* const dws[4] = {gr->rdb_w[r][0], gr->rdb_w[r][1], gr->rdb_w[r][2], gr->rdb_w[r][3]};
+        AFI_TRY(afi_launch_rdb_wgrad_unpack(packed, dws, C, G, 1.f, sd));
+    }
+    return AFI_OK;
+}
+
+int afi_generator_bwd(afi_ctx_t* cx, const afi_gen_params_t* prm, const afi_gen_params_t* gr, afi_view_t xv, int N, int H, int W, const float* ws,
                       const float* dout, float* dx, float* scratch, long long scratch_floats, void* stream) {
-    afi_ctx* cx = ctx; (void)cx;
-    AFI_CTX_CHECK(ctx);
+    AFI_CTX_CHECK(cx);
     AFI_TRY(gen_check(prm));
     if (!gr || N <= 0 || H <= 0 || W <= 0 || !ws || !dout || !scratch) return AFI_ERR_BAD_ARG;
-    const int C = prm->C, G = prm->G, R = prm->n_rdb;
-    const GenWs l = gen_ws(C, G, R, N, H, W);
-    const GenBwdWs s = gen_bwd_ws(C, G, R, N, H, W);
+    const int C = prm->C, R = prm->n_rdb;
+    const GenPlan p = gen_plan(cx, C, prm->G, R, N, H, W);
+    const GenWs& l = p.ws;
+    const GenBwdWs& s = p.bws;
     if (scratch_floats < s.total) return AFI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float* const part_ = scratch + s.o_part;
-    const long long part_n_ = s.n_part;
-    auto PG = [&](AfiPixGemm g, int b_rc) {
-        if (!g.Bimg && s.n_wino > 0 && wino_eligible(cx, g, b_rc)) return wino_run(cx, g, wino_form(cx, g, b_rc), scratch + s.o_wino, s.n_wino, part_, part_n_, st);
-        g.partial = part_; g.partial_floats = part_n_;
-        return afi_launch_pix_gemm(g, b_rc, st);
-    };
-    // Small maps (config-1 sizes): every weight / bias gradient is DEFERRED to the end of the pass and runs as ONE grouped launch
-    // per tile shape (csrc/smallmap.hip: whole dW tiles per block, no split over pixels, no atomics, no zero-fill), instead of one
-    // 7 .. 36-tile launch per layer on a side stream.  All their operands (dOut, dU, gA, gB, the per-block gradient buffers and the
-    // saved activations) stay alive until the call returns.  AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS = 0 restores the per-layer launches.
-    const bool bf6 = afi_dtype_smallmap6(cx ? cx->dtype : afi_default_dtype());
-    // (AFI_OPT_DETERMINISTIC: the grouped stream-K launches add the tiles two runs share by atomics -- the per-layer launches instead)
-    const bool grouped = !afi_det(cx) && (l.P <= afi_opt(cx, AFI_OPT_G_GROUPED_WGRAD_MAX_PIXELS) || (bf6 && s.n_img > 0 && l.P <= afi_opt(cx, AFI_OPT_G_SMALLMAP6_MAX_PIXELS)));
-    const bool batch_growth = !grouped && afi_opt(cx, AFI_OPT_G_BATCH_GROWTH_GRADS) != 0 && (4 * G <= C || s.n_wino == 0);   // larger maps: a block's four growth-conv weight gradients as one packed GEMM (below)
-    // Small maps under the default arithmetic: the data-gradient GEMMs on pre-split weight images and the grouped weight gradients on the
-    // bf16 matrix cores in the six-product form (csrc/smallmap.hip).  The four growth convs' weight gradients of a block then run as ONE
-    // 4G-row problem dy[C : C + 4G] (x) cat[0 : L] into a packed [4G][3][3][L] buffer (1.26x their products, on the 128 x 128 tile of that
-    // kernel instead of four 32-row problems on the fp32 one), unpacked after the group launch -- the large-map form of the same gradients.
-    const bool six = grouped && bf6;
-    const bool pack_growth6 = six && (4 * G) % 4 == 0 && R + 7 <= AFI_WG6_WIDE;
-    constexpr int kWide = 20;
-    static_assert(kWide >= AFI_WG6_WIDE, "table of deferred wide problems");
-    AfiWgradGemm wg_wide[kWide], wg_narrow[4 * AFI_MAX_RDB];
-    AfiColsumProb cs[8];
-    int n_wide = 0, n_narrow = 0, n_cs = 0;
-    bool n_wide_has_convT = false;
-    auto defer = [&](const AfiWgradGemm& g) {
-        if (g.Mrows <= 32 && n_narrow < 4 * AFI_MAX_RDB) { wg_narrow[n_narrow++] = g; return AFI_OK; }
-        if (g.Mrows > 32 && n_wide < kWide) { wg_wide[n_wide++] = g; return AFI_OK; }
-        return wgrad_launch(cx, g, (hipStream_t)stream);       // table full (unusual shapes): launch it on its own
-    };
-    // weight gradient of a 3x3 conv: Winograd F(3x3,2x2) when both channel counts and the map are large enough, else direct
-    auto WG = [&](AfiView dyv, AfiView xin, int n_, int h_, int w_, int co, int ci, float* dw, float alpha, hipStream_t s_) {
-        if (grouped) return defer(conv_wgrad_desc(dyv, xin, n_, h_, w_, co, ci, dw, alpha));
-        if (s.n_wino > 0 && co >= 128 && ci >= 128 && (long long)n_ * h_ * w_ >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD))
-            return wino_wgrad(cx, dyv, xin, n_, h_, w_, co, ci, dw, alpha, scratch + s.o_wino2, s.n_wino, s_);
-        return wgrad_launch(cx, conv_wgrad_desc(dyv, xin, n_, h_, w_, co, ci, dw, alpha), s_);
-    };
-    auto CS = [&](const float* g, long long rows, int Cc, long long ld, float* db, hipStream_t s_) {
-        if (grouped) { cs[n_cs++] = AfiColsumProb{g, db, rows, ld, Cc, 1.f}; return AFI_OK; }
-        return afi_launch_colsum_accum(g, rows, Cc, ld, 1.f, db, scratch + s.o_red, s_);
-    };
+    GenBwd c(cx, p, prm, gr, N, H, W, ws, scratch, st);
     const int L = (int)l.L;
     const long long P = l.P;
-    const float rs = prm->residual_scale;
-    const float* wp = ws + l.o_wp;
     AfiView x = V(xv);
-    auto buf = [&](int r) { return dense_view(ws + l.o_buf + (long long)r * P * L, H, W, L); };
     AfiView t = dense_view(ws + l.o_t, H, W, C), a7 = dense_view(ws + l.o_a7, H, W, C);
     AfiView u = dense_view(ws + l.o_u, 2 * H, 2 * W, C);
     AfiView dOut = dense_view(dout, 2 * H, 2 * W, C);
     AfiView dU = dense_view(scratch + s.o_du, 2 * H, 2 * W, C);
     AfiView gA = dense_view(scratch + s.o_ga, H, W, C), gB = dense_view(scratch + s.o_gb, H, W, C);
-    auto dBuf = [&](int r) { return dense_view(scratch + s.o_db0 + (long long)r * P * L, H, W, L); };
-    float* dwp = scratch + s.o_dwp;
-    // grouped form: ONE stream by default (flush at the end).  Flushing the deferred problems onto the side stream after the hi-res pair,
-    // after each dense block and at the end was measured: the grouped launches then run beside the data-gradient chain, every kernel of
-    // which gets slower by about what is gained (1.26 vs 1.19 ms eager, and 1.51 ms replayed from a hipGraph with its six fork/join
-    // edges): the chain's kernels already occupy every CU even where they wait on memory.  The fork is for the per-layer form only.
-    Fork fk(cx, st, 4 * P <= kSideStreamMaxPixels && !grouped);
-    hipStream_t sd = fk.side;                              // weight / bias gradients
-    bool unpack_pending = false;
-    int packed_blocks = 0;                                 // dense blocks whose packed growth-conv gradient is in wg_wide (unpacked behind the group)
-    unsigned packed_mask = 0;
-    auto flush = [&](bool last) {                          // launch what has been deferred so far (its operands are complete on `st`)
-        if (!grouped || (!last && !fk.on)) return AFI_OK;
-        if (n_wide + n_narrow + n_cs == 0 && !(last && unpack_pending)) return AFI_OK;
-        fk.after_main();
-        int rc6 = AFI_ERR_UNSUPPORTED;
-        if (six && n_wide > 0) rc6 = afi_launch_wgrad_gemm_group6(wg_wide, n_wide, sd);
-        if (rc6 == AFI_ERR_UNSUPPORTED) AFI_TRY(afi_launch_wgrad_gemm_group(wg_wide, n_wide, 1, sd));
-        else AFI_TRY(rc6);
-        AFI_TRY(afi_launch_wgrad_gemm_group(wg_narrow, n_narrow, 0, sd));
-        {   // bias gradients, the conv-transpose gradient's unpack and every packed growth-conv gradient of the pass (a block that was not packed:
-            // null targets) in ONE launch
-            const bool ct = unpack_pending && gr->wT && n_wide_has_convT;
-            float* dws[AFI_MAX_RDB][4];
-            for (int r = 0; r < R; ++r)
-                for (int k = 0; k < 4; ++k) dws[r][k] = (packed_mask & (1u << r)) ? gr->rdb_w[r][k] : nullptr;
-            AFI_TRY(afi_launch_g_bwd_tail(cs, n_cs, ct ? dwp : nullptr, gr->wT, C, C, scratch + s.o_rdbw, s.n_rdbw, dws, packed_blocks > 0 ? R : 0, C, G, 1.f, sd));
-            if (ct) unpack_pending = false;
-            packed_mask = 0; packed_blocks = 0;
-        }
-        n_wide = n_narrow = n_cs = 0; n_wide_has_convT = false;
-        return AFI_OK;
-    };
-    Wk6Images im;                                          // weight images of the data-gradient GEMMs (row-contiguous weights)
-    // (the packed conv-transpose gradient and the packed growth-conv gradients are neighbours in the scratch: ONE fill for both)
-    const bool one_fill = pack_growth6 && gr->wT && s.o_rdbw == s.o_dwp + align4(36LL * C * C) && (s.n_rdbw & 3) == 0;
+    float* dwp = scratch + s.o_dwp;                        // the conv-transpose gradient in packed form
+    // zero fill of the packed gradients the grouped launches add into: dwp and the blocks' packed growth gradients in one piece where they are
+    // neighbours (Bwd::one_fill) and dwp is wanted, else the growth gradients here and dwp at its use
+    const bool one_fill = p.bwd.one_fill && gr->wT;
+    const long long n_dwp = align4(36LL * C * C), n_fill = (one_fill ? n_dwp : 0) + (long long)R * s.n_rdbw;
+    float* const fill = scratch + s.o_rdbw - (one_fill ? n_dwp : 0);
     bool filled = false, skip_grad_done = false;
-    if (six && s.n_img > 0) {
+    if (p.bwd.images) {
         Wk6Req rq[kWk6MaxReq];
-        int nr = 0;
-        rq[nr] = wk6_req(prm->wT, prm->wT, C, C, 4, 1, 9LL * C, C);            // conv-transpose data gradient: K = (Cout chunk, phase, tap), straight from the parameter's layout
-        rq[nr].convT = 2; ++nr;
-        rq[nr++] = wk6_req(prm->w7, prm->w7, C, C, 1, 1, 9LL * C, C);
-        for (int r = 0; r < R; ++r) {
-            rq[nr++] = wk6_req(prm->rdb_w[r][4], prm->rdb_w[r][4], L, C, 1, 1, 9LL * L, L);
-            for (int k = 1; k <= 4; ++k) { const int cin = C + (k - 1) * G; rq[nr++] = wk6_req(prm->rdb_w[r][k - 1], prm->rdb_w[r][k - 1], cin, G, 1, 1, 9LL * cin, cin); }
-        }
-        if (dx) rq[nr++] = wk6_req(prm->w0, prm->w0, C, C, 1, 1, 9LL * C, C);
-        if (4 * P <= kWk6HiResMaxPixels) rq[nr++] = wk6_req(prm->w9, prm->w9, C, C, 1, 1, 9LL * C, C);
-        // riders of that launch (they depend on nothing this pass computes): the zero fill below and the skip path's gradient into dx
+        // riders of the image launch (they depend on nothing this pass computes): that zero fill and the skip path's gradient into dx
         AfiWk6Side side;
         memset(&side, 0, sizeof(side));
-        if (one_fill && (((uintptr_t)(scratch + s.o_dwp)) & 15) == 0) { side.zero_p = scratch + s.o_dwp; side.zero_n4 = (align4(36LL * C * C) + (long long)R * s.n_rdbw) / 4; }
+        if (one_fill && (((uintptr_t)fill) & 15) == 0) { side.zero_p = fill; side.zero_n4 = n_fill / 4; }
         if (dx && (C & 3) == 0) { side.bl_dout = dout; side.bl_dx = dx; side.bl_N = N; side.bl_H = H; side.bl_W = W; side.bl_C = C; }
         bool rode = false;
-        AFI_TRY(wk6_build(cx, im, rq, nr, scratch + s.o_img, s.n_img, st, &side, &rode));
+        AFI_TRY(wk6_build(cx, c.im, rq, gen_bwd_image_reqs(p, prm, dx != nullptr, rq), scratch + s.o_img, s.n_img, st, &side, &rode));
         filled = rode && side.zero_p;
         skip_grad_done = rode && side.bl_dx;
     }
-    if (filled) {}
-    else if (one_fill) { if (hipMemsetAsync(scratch + s.o_dwp, 0, sizeof(float) * (size_t)(align4(36LL * C * C) + (long long)R * s.n_rdbw), st) != hipSuccess) return AFI_ERR_LAUNCH; }
-    else if (pack_growth6 && hipMemsetAsync(scratch + s.o_rdbw, 0, sizeof(float) * (size_t)R * s.n_rdbw, st) != hipSuccess) return AFI_ERR_LAUNCH;
+    if (p.bwd.pack_growth && !filled && hipMemsetAsync(fill, 0, sizeof(float) * (size_t)n_fill, st) != hipSuccess) return AFI_ERR_LAUNCH;
 
     // ---- final conv (generator_rdb.py:107-108)
-    if (gr->w9) AFI_TRY(WG(dOut, u, N, 2 * H, 2 * W, C, C, gr->w9, 1.f, sd));
-    if (gr->b9) AFI_TRY(CS(dout, 4 * P, C, C, gr->b9, sd));
+    if (gr->w9) AFI_TRY(c.wgrad(dOut, u, 2 * H, 2 * W, C, C, gr->w9, 1.f));
+    if (gr->b9) AFI_TRY(c.colsum(dout, 4 * P, C, C, gr->b9));
     {
         AfiPixGemm g = conv_dgrad_desc(dOut, N, 2 * H, 2 * W, C, prm->w9, C, dU);
         g.Z = u; g.z_lo = 0; g.z_hi = C;                       // through the LReLU after the conv-transpose
-        im.attach(g, prm->w9);                                 // (small maps: the small-map kernel instead of the five Winograd launches)
-        AFI_TRY(PG(g, 1));
+        c.im.attach(g, prm->w9);                               // (GenPlan::hires_wk6: the small-map kernel instead of the five Winograd launches)
+        AFI_TRY(c.PG(g, 1));
     }
     // ---- conv-transpose (:101-105)
-    if (!grouped) fk.after_main();                                       // dU is complete
+    c.fk.after_main();                                                      // dU is complete
     if (gr->wT) {
+        hipStream_t sd = c.fk.side;
         if (!one_fill && hipMemsetAsync(dwp, 0, sizeof(float) * 36LL * C * C, sd) != hipSuccess) return AFI_ERR_LAUNCH;
-        if (grouped) {
-            AFI_TRY(defer(convT_wgrad_desc(dU, a7, N, H, W, C, C, dwp, 1.f)));
-            n_wide_has_convT = true; unpack_pending = true;
-        } else if (s.n_wino > 0 && C >= 128 && P >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD)) {    // the four phases as channel blocks of one Winograd weight gradient
+        if (p.bwd.grouped) {
+            AFI_TRY(c.df.defer(cx, convT_wgrad_desc(dU, a7, N, H, W, C, C, dwp, 1.f), st));
+            c.df.convT = true;
+        } else if (gen_wino_wgrad_ok(cx, p, 4 * C, C, P)) {              // the four phases as channel blocks of one Winograd weight gradient
             WinoWgradOpt o;
             o.dy_phases = 4; o.accumulate = false;
             AFI_TRY(wino_wgrad(cx, dU, a7, N, H, W, 4 * C, C, dwp, 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
         } else {
             AFI_TRY(wgrad_launch(cx, convT_wgrad_desc(dU, a7, N, H, W, C, C, dwp, 1.f), sd));
         }
-        if (!grouped) AFI_TRY(afi_launch_convT_unpack_grad(dwp, gr->wT, C, C, sd));
+        if (!p.bwd.grouped) AFI_TRY(afi_launch_convT_unpack_grad(dwp, gr->wT, C, C, sd));
     }
-    if (gr->bT) AFI_TRY(CS(dU.p, 4 * P, C, C, gr->bT, sd));
+    if (gr->bT) AFI_TRY(c.colsum(dU.p, 4 * P, C, C, gr->bT));
     {
-        AfiPixGemm g = convT_dgrad_desc(dU, N, H, W, C, wp, C, gA);
+        AfiPixGemm g = convT_dgrad_desc(dU, N, H, W, C, ws + l.o_wp, C, gA);
         g.Z = a7; g.z_lo = 0; g.z_hi = C;
-        im.attach(g, prm->wT);
-        AFI_TRY(PG(g, 1));
+        c.im.attach(g, prm->wT);
+        AFI_TRY(c.PG(g, 1));
     }
     // ---- trunk conv (:97-99): gA = d(pre-activation of a7)
-    if (!grouped) fk.after_main();                                       // gA is complete
-    if (gr->w7) AFI_TRY(WG(gA, t, N, H, W, C, C, gr->w7, 1.f, sd));
-    if (gr->b7) AFI_TRY(CS(gA.p, P, C, C, gr->b7, sd));
-    AFI_TRY(flush(false));                                 // final conv, conv-transpose and trunk gradients: all their operands exist now
+    c.fk.after_main();                                                      // gA is complete
+    if (gr->w7) AFI_TRY(c.wgrad(gA, t, H, W, C, C, gr->w7, 1.f));
+    if (gr->b7) AFI_TRY(c.colsum(gA.p, P, C, C, gr->b7));
     {
         AfiPixGemm g = conv_dgrad_desc(gA, N, H, W, C, prm->w7, C, gB);  // gB = dT
-        im.attach(g, prm->w7);
-        AFI_TRY(PG(g, 1));
+        c.im.attach(g, prm->w7);
+        AFI_TRY(c.PG(g, 1));
     }
     // ---- ResidualInResidual (:27-30) and the RDB chain (:64-71), last block first
-    AfiView Gt = gB;        // incoming gradient tensor, true gradient = gs * Gt
-    float gs = rs;
+    AfiView Gt = gB;
     for (int r = R - 1; r >= 0; --r) {
-        AfiView b = buf(r), d = dBuf(r);
-        // conv5: out = x + rs*conv5(cat)
-        if (!grouped) fk.after_main();                                   // Gt is complete
-        if (gr->rdb_w[r][4]) AFI_TRY(WG(Gt, b, N, H, W, C, L, gr->rdb_w[r][4], rs * gs, sd));
-        {
-            AfiPixGemm g = conv_dgrad_desc(Gt, N, H, W, C, prm->rdb_w[r][4], L, d);
-            g.alpha = rs * gs;
-            g.R1 = Gt; g.r1s = gs; g.r1_lo = 0; g.r1_hi = C;           // identity path of the block
-            g.Z = b; g.z_lo = C + 3 * G; g.z_hi = L;                   // conv4's LReLU: its slice is final after this kernel
-            im.attach(g, prm->rdb_w[r][4]);
-            AFI_TRY(PG(g, 1));
-        }
-        for (int k = 4; k >= 1; --k) {
-            const int cin = C + (k - 1) * G;
-            AfiView dyk = ch_off(d, cin);                               // d(pre-activation of conv_k), G channels
-            if (!grouped) fk.after_main();                               // dyk's slice was finalised by the previous dgrad
-            if (gr->rdb_w[r][k - 1] && !batch_growth && !pack_growth6) {
-                const AfiWgradGemm wd = conv_wgrad_desc(dyk, b, N, H, W, G, cin, gr->rdb_w[r][k - 1], 1.f);
-                AFI_TRY(grouped ? defer(wd) : wgrad_launch(cx, wd, sd));
-            }
-            if (batch_growth) {
-                // larger maps: only the part of conv_k's data gradient that lands on y_1 .. y_{k-1} (channels [C, cin): (k-1) G columns) runs
-                // here, in chain order -- each finalises the slice the next one reads; the parts that land on the block input x (channels
-                // [0, C)) of all four convs are ONE data gradient from the 4G adjacent channels dy_1 .. dy_4 after the chain (below)
-                if (k == 1) continue;
-                AfiPixGemm g = conv_dgrad_desc(dyk, N, H, W, G, prm->rdb_w[r][k - 1] + C, cin - C, ch_off(d, C));
-                g.b_sRow = 9LL * cin; g.b_sTap = cin;                   // (a column range of the [G][3][3][cin] weight)
-                g.beta = 1.f;
-                g.Z = ch_off(b, C); g.z_lo = cin - C - G; g.z_hi = cin - C;      // conv_{k-1}'s slice becomes final
-                AFI_TRY(PG(g, 1));
-                continue;
-            }
-            AfiPixGemm g = conv_dgrad_desc(dyk, N, H, W, G, prm->rdb_w[r][k - 1], cin, d);
-            g.beta = 1.f;                                               // dense connections: accumulate
-            if (k >= 2) { g.Z = b; g.z_lo = cin - G; g.z_hi = cin; }    // conv_{k-1}'s slice becomes final
-            if (k == 1 && r == 0) {                                     // RRDB skip (+dT) and the head conv's LReLU
-                g.R2 = gB; g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
-                g.Z = b; g.z_lo = 0; g.z_hi = C;
-            }
-            im.attach(g, prm->rdb_w[r][k - 1]);
-            AFI_TRY(PG(g, 1));
-        }
-        if (pack_growth6 && (gr->rdb_w[r][0] || gr->rdb_w[r][1] || gr->rdb_w[r][2] || gr->rdb_w[r][3])) {
-            // (every slice of d[C : C + 4G] is final now; each conv reads a prefix of b: rows paired with channels behind their conv's
-            //  input are computed and never read by the unpack)
-            AFI_TRY(defer(conv_wgrad_desc(ch_off(d, C), b, N, H, W, 4 * G, L, scratch + s.o_rdbw + (long long)r * s.n_rdbw, 1.f)));
-            packed_mask |= 1u << r; ++packed_blocks;
-        }
-        if (batch_growth) {
-            // d[0:C) += sum_k W_k[:, :, :, 0:C]^T (*) dy_k: a 4G -> C data gradient on the packed weights [4G][3][3][C] -- Winograd-eligible at the
-            // reference's widths (128 -> 256 channels) where the four per-conv ones (32 -> 256 .. 352) were direct GEMMs 288 deep
-            const float* const wk[4] = {prm->rdb_w[r][0], prm->rdb_w[r][1], prm->rdb_w[r][2], prm->rdb_w[r][3]};
-            float* Wx = scratch + s.o_rdbx + (long long)r * s.n_rdbx;
-            bool hit = false, scratch_b = true;
-            if (float* slot = wino_wcache_slot(cx, prm->rdb_w[r][0], /*tag: growth x-part pack*/ 3, 0, 4 * G, C, s.n_rdbx, hit)) { Wx = slot; scratch_b = false; }
-            if (!hit) AFI_TRY(afi_launch_rdb_xpart_pack(wk, Wx, C, G, st));
-            AfiPixGemm g = conv_dgrad_desc(ch_off(d, C), N, H, W, 4 * G, Wx, C, d);
-            g.beta = 1.f;
-            g.no_wcache = scratch_b ? 1 : 0;
-            if (r == 0) {                                               // RRDB skip (+dT) and the head conv's LReLU
-                g.R2 = gB; g.r2s = 1.f; g.r2_lo = 0; g.r2_hi = C;
-                g.Z = b; g.z_lo = 0; g.z_hi = C;
-            }
-            AFI_TRY(PG(g, 1));
-        }
-        if (batch_growth && (gr->rdb_w[r][0] || gr->rdb_w[r][1] || gr->rdb_w[r][2] || gr->rdb_w[r][3])) {
-            // the four growth convs' weight gradients as ONE product dy[C : C + 4G] (x) cat[0 : L] (their gradients are adjacent slices of d, all
-            // final now; each conv reads a prefix of b): a 4G-row GEMM -- Winograd F(3x3,4x4) on the bf16 matrix cores when 4G and L reach 128
-            // channels -- instead of four G-row ones on the 32 x 128 fp32 tile, 1.26x their products at several times their rate
-            fk.after_main();
-            float* packed = scratch + s.o_rdbw + (long long)r * s.n_rdbw;
-            if (hipMemsetAsync(packed, 0, sizeof(float) * 4LL * G * 9 * L, sd) != hipSuccess) return AFI_ERR_LAUNCH;
-            const AfiView dy4 = ch_off(d, C);
-            const bool wino_ok = s.n_wino > 0 && 4 * G >= 128 && L >= 128 && P >= wino_g_minpix(cx) && afi_opt(cx, AFI_OPT_WINOGRAD) &&
-                                 s.n_wino >= wino_ws_floats(N, H, W, L, 4 * G);
-            WinoWgradOpt o;
-            o.accumulate = false;
-            if (wino_ok) AFI_TRY(wino_wgrad(cx, dy4, b, N, H, W, 4 * G, L, packed, 1.f, scratch + s.o_wino2, s.n_wino, sd, o));
-            else AFI_TRY(wgrad_launch(cx, conv_wgrad_desc(dy4, b, N, H, W, 4 * G, L, packed, 1.f), sd));
-            float* const dws[4] = {gr->rdb_w[r][0], gr->rdb_w[r][1], gr->rdb_w[r][2], gr->rdb_w[r][3]};
-            AFI_TRY(afi_launch_rdb_wgrad_unpack(packed, dws, C, G, 1.f, sd));
-        }
-        AFI_TRY(flush(false));                                          // this block's five weight gradients
-        Gt = d; gs = 1.f;                                               // channels [0,C) of d = gradient w.r.t. the block input
+        AFI_TRY(gen_bwd_block(c, r, Gt, r == R - 1 ? prm->residual_scale : 1.f, gB));
+        Gt = c.dbuf(r);
     }
     // ---- head conv (:91-93): Gt[0:C] = d(pre-activation of a0)
-    if (!grouped) fk.after_main();
-    if (gr->w0) AFI_TRY(WG(Gt, x, N, H, W, C, C, gr->w0, 1.f, sd));
-    if (gr->b0) AFI_TRY(CS(Gt.p, P, C, L, gr->b0, sd));
+    c.fk.after_main();
+    if (gr->w0) AFI_TRY(c.wgrad(Gt, x, H, W, C, C, gr->w0, 1.f));
+    if (gr->b0) AFI_TRY(c.colsum(Gt.p, P, C, L, gr->b0));
     if (dx) {
         if (!skip_grad_done) AFI_TRY(afi_launch_bilinear2x_bwd(dout, N, H, W, C, 0.f, dx, st));           // skip path (:125)
         AfiPixGemm g = conv_dgrad_desc(Gt, N, H, W, C, prm->w0, C, dense_view(dx, H, W, C));
         g.beta = 1.f;
-        im.attach(g, prm->w0);
-        AFI_TRY(PG(g, 1));
+        c.im.attach(g, prm->w0);
+        AFI_TRY(c.PG(g, 1));
     }
-    AFI_TRY(flush(true));                                  // head conv (and, without the side stream, everything deferred so far)
-    fk.join();
+    AFI_TRY(c.df.flush(p, prm, gr, scratch, st));          // everything a grouped pass deferred
+    c.fk.join();
     return AFI_OK;
 }
 

@@ -110,6 +110,29 @@ def test_host_only_queries():
     assert lib.afi_discriminator_fwd_ws_floats(F, 1, 50, 68) > 3400 * (2 * 512 + 4 * 1024)
 
 
+def test_generator_workspace_sizes_are_pinned():
+    """afi_generator_fwd_ws_floats / afi_generator_bwd_ws_floats over (C, G, R, N, H, W) rows on both sides of every threshold the layouts depend on
+    (1024, 4096 and 8192 low-res pixels, C below and at 128, G not a multiple of 32).  The literals were read from the library built from commit
+    0c98d88, the parent of the change that moved both layouts into GenPlan (csrc/nets.hip), not from the code under test: a caller that sized its
+    buffers by an older build keeps working."""
+    _build()
+    from afigan_amd import _lib
+    lib = _lib.load()
+    want = {
+        (256, 32, 3, 1, 25, 34): (32614720, 44821376),
+        (256, 32, 3, 2, 25, 34): (56018496, 87099520),
+        (256, 32, 3, 1, 64, 64): (78957632, 116723328),
+        (256, 32, 3, 1, 91, 90): (140285760, 211605888),
+        (256, 32, 3, 1, 100, 168): (258248768, 400872064),
+        (128, 32, 2, 1, 36, 32): (18966592, 28535168),
+        (64, 32, 2, 1, 60, 56): (8699904, 9207936),
+        (32, 8, 2, 1, 80, 64): (6412288, 6481984),
+        (16, 4, 3, 1, 5, 7): (58688, 88928),
+    }
+    for shape, (fwd, bwd) in want.items():
+        assert (lib.afi_generator_fwd_ws_floats(*shape), lib.afi_generator_bwd_ws_floats(*shape)) == (fwd, bwd), shape
+
+
 def test_context_api_rejects_bad_arguments_without_a_gpu():
     """afi_ctx_* are host functions: NULL handling is checked here; creation needs a current device and is covered by the GPU tests."""
     _build()

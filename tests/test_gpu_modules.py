@@ -446,6 +446,54 @@ def test_generator_batched_growth_gradients_match_the_per_conv_form(amd, C, g, h
         assert _rel(res[1][1][k], res[0][1][k]) < 2e-5, k
 
 
+@pytest.fixture(scope="module")
+def schedule_case():
+    """One small interpolator for test_generator_every_schedule_matches_the_oracle and its CPU-oracle results, computed once: C = 128, growth 32, two
+    dense blocks on 1 x 128 x 36 x 32 -- 1152 low-res pixels, the smallest map above the 1024-pixel floor of the Winograd scratch sizing with C and
+    G still multiples of 32 (the weight images' rule)."""
+    C, g = 128, 32
+    gp = orc.closed_form_generator_params(C, 2, g)
+    x = torch.randn((1, C, 36, 32), generator=torch.Generator().manual_seed(22))
+    pr = {k: v.clone().requires_grad_(True) for k, v in gp.items()}
+    xr = x.clone().requires_grad_(True)
+    ref = orc.generator_forward(xr, pr, n_rdb=2)
+    (ref * torch.linspace(-1, 1, ref.numel()).view_as(ref)).sum().backward()
+    return gp, x, ref.detach(), xr.grad, {k: v.grad for k, v in pr.items()}
+
+
+_LARGE_MAP_FORMS = dict(g_smallmap6_max_pixels=0, g_smallmap_max_pixels=0, g_grouped_wgrad_max_pixels=0, g_winograd_min_pixels=1024)
+
+
+@pytest.mark.parametrize("dtype,options", [
+    (None, {}),                                                                 # (a) defaults: batched forward on weight images, grouped backward
+    (None, _LARGE_MAP_FORMS),                                                   # (b) batched-growth forms with Winograd, side stream on
+    (None, dict(_LARGE_MAP_FORMS, g_batch_growth_grads=0)),                     # (c) conv by conv
+    (None, dict(_LARGE_MAP_FORMS, g_batch_growth_grads=0, winograd=0)),         # (d) direct kernels only
+    (None, dict(deterministic=1)),                                              # (e) forward on images, backward per layer
+    ("fp32", {}),                                                               # (f) the small-map schedule without images
+], ids=["defaults", "batched_growth_winograd", "conv_by_conv", "direct_only", "deterministic", "fp32_small_map"])
+def test_generator_every_schedule_matches_the_oracle(amd, schedule_case, dtype, options):
+    """Every schedule gen_plan() (csrc/nets.hip; table in DESIGN.md 4) can choose for one interpolator call, each under a fresh context, against
+    the CPU oracle: output, input gradient, every parameter gradient."""
+    from afigan_amd import _lib
+    gp, x, ref, dx_ref, grads_ref = schedule_case
+    cx = _lib.Ctx(dtype)
+    for k, v in options.items():
+        cx.set_option(k, v)
+    G = amd.Generator(in_channels=128, n_residual_dense_blocks=2, growth_rate=32).cuda()
+    G.load_state_dict(gp)
+    xg = x.cuda().requires_grad_(True)
+    with _lib.use_ctx(cx):
+        out = G(xg)
+        (out * torch.linspace(-1, 1, out.numel(), device="cuda").view_as(out)).sum().backward()
+    errs = {"out": _rel(out, ref), "dx": _rel(xg.grad, dx_ref)}
+    errs.update({k: _rel(_logical(p.grad), grads_ref[k]) for k, p in G.named_parameters()})
+    print(f"schedule {dtype} {options}: worst {max(errs, key=errs.get)} {max(errs.values()):.2e}")
+    assert set(grads_ref) <= set(errs)
+    for k, e in errs.items():
+        assert e < 1e-3, (k, e)
+
+
 @pytest.mark.parametrize("shape", [(2, 26, 42), (1, 13, 21)])
 def test_discriminator_stats_only_forward_has_the_same_side_effects(amd, shape):
     """afi_discriminator_fwd(training = 3) -- the G phase's D(real) call of stage1_trainer.py:401-403, whose logits nothing reads -- leaves the
