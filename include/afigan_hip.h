@@ -132,7 +132,10 @@ int afi_ctx_get_compute_dtype(const afi_ctx_t* ctx);
                                                  1.45e-3 / 1.91e-3; = 12 with the local sums: 0.88e-3 / 1.26e-3 | 1.04e-3 / 1.33e-3; = 1 with them: 1.32e-3 / 1.79e-3 |
                                                  1.40e-3 / 1.76e-3.  tests/test_gpu_d_parity.py holds the default to that bar.
                                                  Bit 16: the interpolator's own forwards too (off: 15x the deviation on its worst parameter gradient for 1 ms) */
-#define AFI_OPT_BN_STATS_FP64 3               /* 1 (default): BatchNorm batch statistics accumulated in fp64 (torch's CPU accumulation type) */
+#define AFI_OPT_BN_STATS_FP64 3               /* 1 (default): BatchNorm batch statistics accumulated in fp64 (torch's CPU accumulation type).
+                                               * 0: the fp32 one-pass form shifted by row 0, which loses the order of 1 % of the variance when row 0
+                                               * is an outlier of 1e3 standard deviations, as the shift then removes nothing (emulated in fp32 on
+                                               * the CPU in the kernels' summation order: 0.3 % at 8400 rows, 3.6 % at 134400). */
 #define AFI_OPT_D_WINOGRAD_MIN_PIXELS 4       /* 1024: discriminator calls of fewer pixels stay direct (values below 1024 act as 1024) */
 #define AFI_OPT_G_WINOGRAD_MIN_PIXELS 5       /* 2048: the same for a convolution of the interpolator */
 #define AFI_OPT_G_SMALLMAP_MAX_PIXELS 6       /* 2048: below, the dense blocks run in column-batched form (5 grouped launches per block); 0: never */

@@ -74,6 +74,40 @@ def test_forward_statistics_and_mask_flips(amd, N, H, W, seed):
     assert sum(fg) <= sum(fc) + FLIP_SLACK, (fg, fc)
 
 
+def test_batch_statistics_in_both_accumulation_types(amd):
+    """Option bn_stats_fp64: 1 (default) accumulates the batch statistics in fp64 (afi_bn_stats_partial_kernel), 0 takes the fp32 one-pass
+    form (afi_colred_partial_kernel<0> + afi_bn_stats_finalize_kernel), which nothing else in the suite runs.  Each block's saved mean /
+    invstd against float64 statistics of the conv output THE SAME FORWARD saved (so the convolutions' own rounding is not in the figure).
+    fp64: the fp32 rounding of the reference or its neighbour.  fp32 (P = 546 rows summed): mean within C_MAX sqrt(P) 2^-24 std, variance
+    within C_MAX sqrt(P) 2^-24 relative (C_MAX = 2, the reduction bar of tests/test_gpu_pixgemm.py; csrc/elementwise.hip reports 0.9-1.6e-6
+    in var for this form).  The variance is read back from the saved invstd, 1 / invstd^2 - eps."""
+    import elementwise_f64 as E
+    from oracle import afigan_oracle as orc
+    saved = {}
+    for flag in (0, 1):
+        pr = DProbe(amd, 2, 13, 21, 1, in_filters=64, options={"bn_stats_fp64": flag})
+        P = pr.P
+        bar = E.C_MAX * P ** 0.5 * E.EPS
+        saved[flag] = []
+        for n in range(3):
+            c, _, mean, invstd = pr.saved(n)
+            ref = E.bn_stats(c.permute(0, 2, 3, 1).reshape(P, -1).cpu(), orc.BN_EPS)
+            saved[flag].append((mean.clone(), invstd.clone()))
+            if flag:
+                um, ui = float(E.ulps_from(mean, ref["mean"]).max()), float(E.ulps_from(invstd, ref["invstd"]).max())
+                print(f"bn_stats_fp64=1 block {n}: mean {um} ulp, invstd {ui} ulp")
+                assert um <= 1.0 and ui <= 1.0, (n, um, ui)
+            else:
+                em = float(((mean.double().cpu() - ref["mean"]).abs() / ref["var"].sqrt()).max())
+                var = 1.0 / invstd.double().cpu() ** 2 - E.f32(orc.BN_EPS)
+                ev = float(((var - ref["var"]).abs() / ref["var"]).max())
+                print(f"bn_stats_fp64=0 block {n}: mean {em:.2e} std, var {ev:.2e} relative (bar {bar:.2e})")
+                assert em <= bar and ev <= bar, (n, em, ev, bar)
+        del pr
+    # the option reached the kernels: the two accumulation types do not round every statistic alike
+    assert any(not torch.equal(a, b) for s0, s1 in zip(saved[0], saved[1]) for a, b in zip(s0, s1))
+
+
 @pytest.mark.parametrize("f4", F4_SETTINGS)
 def test_forward_statistics_and_mask_flips_on_the_winograd_forwards(amd, f4):
     """The flip-visible test at the size where the F(4x4) forward runs: the library's OWN forward, masks compared with

@@ -524,7 +524,11 @@ def test_discriminator_stats_only_forward_has_the_same_side_effects(amd, shape):
     assert not torch.equal(states[2][1], torch.full_like(states[2][1], 7.0)) and torch.equal(states[3][1], torch.full_like(states[3][1], 7.0))
 
 
-@pytest.mark.parametrize("F0,N,H,W,train", [(256, 2, 13, 21, 1), (256, 2, 50, 84, 1), (256, 1, 32, 40, 0), (16, 2, 9, 11, 1), (96, 1, 17, 5, 1)])
+@pytest.mark.parametrize("F0,N,H,W,train", [(256, 2, 13, 21, 1), (256, 2, 50, 84, 1), (256, 1, 32, 40, 0), (16, 2, 9, 11, 1), (96, 1, 17, 5, 1),
+                                            # the forward's channel loop (batches of four 16-channel steps, then a remainder loop): F3 = 48 is three
+                                            # remainder steps and no batch, 80 one batch + one step, 112 one batch + three; P = 50400 is 788 row tiles
+                                            # (> 768 blocks: a block walks two) and the backward sums at their 512-chunk cap
+                                            (12, 2, 9, 11, 1), (20, 1, 17, 5, 1), (28, 2, 9, 11, 1), (16, 1, 224, 225, 1)])
 def test_discriminator_fused_tail_is_the_same_network(amd, F0, N, H, W, train):
     """Option d_fuse_tail (default on): block 2's BatchNorm apply + LeakyReLU, the last conv and their backward without y[2] and without the
     gradient w.r.t. it in memory (feature_patch_discriminator.py:38-41; csrc/elementwise.hip, afi_launch_disc_tail_*).  Against the separate
