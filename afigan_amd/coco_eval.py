@@ -6,7 +6,10 @@ COCOeval restated: the per-(image, category) IoU matrices and the greedy matchin
 afi_coco_rle_area, afi_coco_rle_iou, afi_coco_match), the precision / recall accumulation and the twelve statistics here in numpy.  There is no
 CPU fallback for the device stages.  DESIGN.md section 19 states the semantics; tests/coco_eval_f64.py is the plain-loop checker.
 
-Not here: keypoints (OKS), proposal AR, polygon ground truth for ``segm`` (it must be RLE), gathering predictions across processes, result files."""
+Polygon ground truth for ``segm`` (what every COCO instances file holds) is rasterised on the GPU with ``rasterize_polygons=True``
+(ops.polygons_rle, csrc/poly_rle.hip: pycocotools' annToRLE restated), all annotations in one batched call at construction.
+
+Not here: keypoints (OKS), proposal AR, polygon segmentations in the RESULTS (they must be RLE), gathering predictions across processes, result files."""
 from collections import OrderedDict
 
 import numpy as np
@@ -88,7 +91,8 @@ def _starts(seg, what):
     """(ascending run starts int32, H W) of an RLE segmentation: a compressed string, or an uncompressed counts list, with ``size``."""
     if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
         raise AfiError(f"COCOEvaluator: {what}: the `segm` task needs an RLE segmentation ({{'size': [H, W], 'counts': str or list}}); a polygon "
-                       "is not rasterised here -- convert it to RLE first")
+                       "is not rasterised here -- pass rasterize_polygons=True to COCOEvaluator for polygon ground truth, or convert it to RLE "
+                       "first (afigan_amd.polygons_to_rle)")
     c = seg["counts"]
     c = rle.from_string(c) if isinstance(c, (str, bytes)) else np.asarray(c, dtype=np.int64).reshape(-1)
     n = int(seg["size"][0]) * int(seg["size"][1])
@@ -100,9 +104,12 @@ def _starts(seg, what):
 class COCOEvaluator:
     """``gt``: a COCO annotation dict (``images``, ``annotations``, ``categories``).  ``tasks``: of "bbox", "segm".  ``class_names``: with more than
     one entry (one per category, in category-id order), ``evaluate()`` adds ``AP-<name>`` per category.  After ``evaluate()``, ``self.stats[task]``
-    [12], ``self.precision[task]`` [T, R, K, A, M] and ``self.recall[task]`` [T, K, A, M] hold what pycocotools' ``COCOeval.stats`` / ``.eval`` hold."""
+    [12], ``self.precision[task]`` [T, R, K, A, M] and ``self.recall[task]`` [T, K, A, M] hold what pycocotools' ``COCOeval.stats`` / ``.eval`` hold.
+    ``rasterize_polygons``: for ``segm``, a ground truth whose ``segmentation`` is a polygon list is rasterised on the GPU at the ``height`` /
+    ``width`` of its image entry (pycocotools' annToRLE), all of them in one batched call here; RLE ground truth (crowds) is taken as it is.
+    False (the default) refuses a polygon."""
 
-    def __init__(self, gt, tasks=("bbox",), class_names=None):
+    def __init__(self, gt, tasks=("bbox",), class_names=None, rasterize_polygons=False):
         for k in ("images", "annotations", "categories"):
             if k not in gt:
                 raise AfiError(f"COCOEvaluator: the annotation dict has no `{k}`")
@@ -123,9 +130,31 @@ class COCOEvaluator:
         order = np.argsort(key, kind="mergesort")                               # annotation order inside a group
         self._gt = [anns[i] for i in order]
         self._gt_key = key[order]
-        # segm: the ground truth's run starts, once (a polygon is refused here, by _starts)
-        self._gt_starts = [_starts(a.get("segmentation"), f"annotation {a.get('id')}") for a in self._gt] if "segm" in tasks else None
+        # segm: the ground truth's run starts, once (a polygon is refused by _starts unless rasterize_polygons)
+        self._gt_starts = None
+        if "segm" in tasks:
+            is_poly = [rasterize_polygons and isinstance(a.get("segmentation"), (list, tuple)) for a in self._gt]
+            self._gt_starts = [None if p else _starts(a.get("segmentation"), f"annotation {a.get('id')}") for a, p in zip(self._gt, is_poly)]
+            if any(is_poly):
+                self._rasterize([i for i, p in enumerate(is_poly) if p], {im["id"]: im for im in gt["images"]})
         self.reset()
+
+    def _rasterize(self, idx, images):
+        """The run starts of the polygon ground truths ``idx`` of self._gt: one batched ops.polygons_rle call and one read back."""
+        polys, sizes = [], []
+        for i in idx:
+            a = self._gt[i]
+            im = images[a["image_id"]]
+            if "height" not in im or "width" not in im:
+                raise AfiError(f"COCOEvaluator: annotation {a.get('id')}: image {a['image_id']!r} has no `height` / `width`, which a polygon is rasterised at")
+            polys.append(a["segmentation"])
+            sizes.append((int(im["height"]), int(im["width"])))
+        sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+        ops.polygons_batch(polys, sizes)                                        # every refusal before the device is touched
+        starts, off, hw = ops.polygons_rle(polys, sizes)
+        starts, off, hw = starts.cpu().numpy(), off.cpu().numpy(), hw.cpu().numpy()
+        for k, i in enumerate(idx):
+            self._gt_starts[i] = (starts[off[k]:off[k + 1]].astype(np.int32), int(hw[k]))
 
     def reset(self):
         self._predictions = []

@@ -18,8 +18,10 @@ afigan_utils.py:379-406) is mirrored AS WRITTEN -- including that only ``image``
 resized to half of the cropped image's resized size (dataset_mapper.py:98-105; no reference yaml enables the crop).
 
 Out of scope (not on the path): file reading / JPEG decode (``dataset_dict["image"]`` must hold the decoded uint8
-HWC array), bitmask / RLE masks (rasterised by pycocotools, a third-party package the reference does not vendor), keypoints, proposals,
-semantic segmentation.  Random draws come from ``numpy.random``'s global state in the reference's order (crop size, crop instance,
+HWC array), RLE / array segmentations, ``INPUT.MASK_FORMAT = "bitmask"`` together with ``INPUT.CROP`` (the reference takes tight boxes from
+``BitMasks.get_bounding_boxes()`` there, whose behaviour in its detectron2 version is not established here), keypoints, proposals, semantic
+segmentation.  ``mask_format="bitmask"`` rasterises the transformed polygons on the GPU (ops.polygons_rle + ops.rle_decode: pycocotools'
+frPyObjects + merge + decode, which detectron2's ``polygons_to_bitmask`` calls) at the output size of each instances list.  Random draws come from ``numpy.random``'s global state in the reference's order (crop size, crop instance,
 crop origin, size, flip, then the two discarded draws of the x0.5 list), so a seeded run picks the same crops, sizes and flips as the
 reference mapper.
 """
@@ -112,7 +114,32 @@ class PolygonMasks:
         return out
 
 
-def _instances(annos, tfms, image_size, device, mask_on=False, tight_boxes=False):
+class BitMasks:
+    """The part of detectron2.structures.BitMasks this path touches: ``tensor`` bool [N, H, W] on the device; ``nonempty()`` = any pixel set."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+    def __getitem__(self, keep):
+        if isinstance(keep, int):
+            return BitMasks(self.tensor[keep][None])
+        keep = torch.as_tensor(keep)
+        return BitMasks(self.tensor[keep.to(self.tensor.device)])
+
+    def nonempty(self):
+        return self.tensor.flatten(1).any(dim=1)
+
+    @staticmethod
+    def from_polygon_masks(polygons, height, width):
+        """polygons: per instance a list of flat coordinate arrays (PolygonMasks.polygons).  One rasteriser call for all instances."""
+        starts, off, _ = ops.polygons_rle(polygons, (height, width))
+        return BitMasks(ops.rle_decode(starts, off, (height, width)))
+
+
+def _instances(annos, tfms, image_size, device, mask_on=False, tight_boxes=False, bitmask=False):
     """transform_instance_annotations (afigan_utils.py:140-183) + annotations_to_instances (:234-262) + filter_empty_instances (:328-354)
     for boxes, classes and polygon masks.  tight_boxes: the boxes re-formed from the masks, as the mapper does when it crops."""
     new_h, new_w = image_size
@@ -127,14 +154,14 @@ def _instances(annos, tfms, image_size, device, mask_on=False, tight_boxes=False
         for a in keep:
             segm = a["segmentation"]
             if not isinstance(segm, list):
-                raise _lib.AfiError("only polygon segmentations are supported on this path (RLE / bitmask masks need pycocotools)")
+                raise _lib.AfiError("only polygon segmentations are supported on this path (an RLE / array segmentation is not rasterised or transformed here)")
             polys.append([_apply_coords(np.asarray(q).reshape(-1, 2), tfms).reshape(-1) for q in segm])
-        masks = PolygonMasks(polys)
+        masks = BitMasks.from_polygon_masks(polys, new_h, new_w) if bitmask else PolygonMasks(polys)
         if tight_boxes:
             b = masks.get_bounding_boxes()                   # dataset_mapper.py:156-157,174-175
     ne = ((b[:, 2] - b[:, 0]) > 0) & ((b[:, 3] - b[:, 1]) > 0)                # Boxes.nonempty
     if masks is not None:
-        ne = ne & masks.nonempty()
+        ne = ne & masks.nonempty().cpu()
     inst = SimpleNamespace(image_size=(new_h, new_w), gt_boxes=b[ne].to(device), gt_classes=cls[ne].to(device))
     if masks is not None:
         inst.gt_masks = masks[ne]
@@ -200,8 +227,13 @@ class DualScaleMapper:
         self.scale_ratio, self.is_train, self.flip_prob, self.device = tuple(scale_ratio), is_train, flip_prob, torch.device(device)
         self.share_flip = share_flip
         assert self.scale_ratio == (0.5,), "the reference hard-codes the 0.5 ratio in its transform list (transform_gen.py:542-543)"
-        if mask_on and mask_format != "polygon":
-            raise _lib.AfiError('INPUT.MASK_FORMAT "bitmask" rasterises polygons with pycocotools (not vendored by the reference); "polygon" only')
+        if mask_on and mask_format not in ("polygon", "bitmask"):
+            raise _lib.AfiError(f'INPUT.MASK_FORMAT must be "polygon" or "bitmask", got {mask_format!r}')
+        self.bitmask = bool(mask_on and mask_format == "bitmask")
+        if self.bitmask and self.device.type != "cuda":
+            raise _lib.AfiError('INPUT.MASK_FORMAT "bitmask" rasterises the polygons on the GPU (csrc/poly_rle.hip); there is no CPU rasteriser: device="cuda"')
+        if self.bitmask and crop is not None:
+            raise _lib.AfiError('INPUT.MASK_FORMAT "bitmask" together with INPUT.CROP is not supported (the tight boxes of BitMasks.get_bounding_boxes)')
         self.mask_on = mask_on
         self.crop_gen = RandomCrop(*crop) if (crop is not None and is_train) else None
 
@@ -270,8 +302,8 @@ class DualScaleMapper:
         if "annotations" in d:
             annos = d.pop("annotations")
             tight = self.crop_gen is not None
-            d["instances"] = _instances(annos, pl.tf, pl.size, self.device, self.mask_on, tight)
-            d[f"instances_x{ratio}"] = _instances(annos, pl.tf_r, pl.size_r, self.device, self.mask_on, tight)
+            d["instances"] = _instances(annos, pl.tf, pl.size, self.device, self.mask_on, tight, self.bitmask)
+            d[f"instances_x{ratio}"] = _instances(annos, pl.tf_r, pl.size_r, self.device, self.mask_on, tight, self.bitmask)
         return d
 
 

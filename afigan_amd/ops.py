@@ -8,6 +8,7 @@ import contextlib
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1282,6 +1283,106 @@ def coco_match(iou, dt_off, gt_off, iou_off, dt_area, gt_area, iscrowd, area_rng
          _p(_coco_arg("iou_thr", iou_thr, torch.float64)), T, ngt if max_g is None else int(max_g), _p(_coco_arg("dt_match", dtm, torch.int32)), _p(_coco_arg("dt_ignore", dti, torch.uint8)),
          _p(_coco_arg("gt_ignore", gti, torch.uint8)), _p(ws), ws.numel() * ws.element_size(), stream_ptr())
     return dtm, dti, gti
+
+
+# ------------------------------------------------------------------------------------------------ COCO polygons as run starts (rle.py, coco_eval.py)
+def polygons_batch(polygons, sizes):
+    """The host side of polygons_rle: checks the annotations (AfiError before anything is uploaded) and packs them as afi_poly_rle_count reads
+    them.  Returns numpy arrays (xy float64 [V, 2], vert_off int64 [P + 1], poly_off int64 [N + 1], hw int32 [N, 2], cap_off int64 [P + 1])."""
+    N = len(polygons)
+    sz = np.asarray(sizes, dtype=np.int64)
+    if sz.ndim == 1 and sz.size == 2:
+        sz = np.broadcast_to(sz, (N, 2))
+    if sz.ndim != 2 or sz.shape != (N, 2):
+        raise _lib.AfiError(f"polygons_rle: sizes must be (H, W) or one pair per annotation, got shape {tuple(np.shape(sizes))} for {N} annotations")
+    if N and ((sz <= 0).any() or (sz[:, 0] * sz[:, 1] >= 1 << 31).any()):
+        raise _lib.AfiError("polygons_rle: every canvas needs H, W > 0 and H W < 2^31")
+    flat, nvert, npoly = [], [], []
+    for i, ann in enumerate(polygons):
+        if isinstance(ann, dict) or isinstance(ann, (str, bytes)):
+            raise _lib.AfiError(f"polygons_rle: annotation {i} is not a list of polygons (an RLE is not rasterised)")
+        npoly.append(len(ann))
+        for poly in ann:
+            c = np.asarray(poly, dtype=np.float64).reshape(-1)
+            if c.size == 0 or c.size & 1:
+                raise _lib.AfiError(f"polygons_rle: annotation {i}: a polygon of {c.size} coordinates (a non-empty list of x, y pairs expected)")
+            flat.append(c)
+            nvert.append(c.size // 2)
+    xy = np.concatenate(flat).reshape(-1, 2) if flat else np.zeros((0, 2), np.float64)
+    if not np.isfinite(xy).all():
+        raise _lib.AfiError("polygons_rle: a non-finite coordinate")
+    if (np.abs(5 * xy + .5) >= float(1 << 30)).any():
+        raise _lib.AfiError("polygons_rle: a coordinate c with |5 c + .5| >= 2^30")
+    vert_off = np.concatenate(([0], np.cumsum(nvert))).astype(np.int64)
+    poly_off = np.concatenate(([0], np.cumsum(npoly))).astype(np.int64)
+    # the capacity of a polygon: sum over its edges of (dx / 5 + 2), dx in upsampled units (the kernel's X = (int)(5 x + .5), same fp64 steps)
+    X = np.trunc(5 * xy[:, 0] + .5).astype(np.int64)
+    nxt = np.arange(1, X.size + 1, dtype=np.int64)
+    if X.size:
+        nxt[vert_off[1:] - 1] = vert_off[:-1]                                   # the last vertex of a polygon is followed by its first
+    cap_edge = np.abs(X[nxt] - X) // 5 + 2 if X.size else np.zeros(0, np.int64)
+    cap_off = np.concatenate(([0], np.cumsum(cap_edge)))[vert_off].astype(np.int64)
+    if int(cap_off[-1]) >= 1 << 31:
+        raise _lib.AfiError(f"polygons_rle: {int(cap_off[-1])} crossings at most in one call (< 2^31): split the batch")
+    return xy, vert_off, poly_off, np.ascontiguousarray(sz, dtype=np.int32), cap_off
+
+
+def polygons_rle(polygons, sizes, device="cuda", ws=None):
+    """COCO polygon annotations as run starts (pycocotools' frPyObjects + merge): ``polygons`` a list of N annotations, each a list of flat
+    coordinate sequences [x0, y0, x1, y1, ...]; ``sizes`` (H, W) or one pair per annotation.  Returns (starts int32 [S], start_off int64 [N + 1],
+    hw int32 [N] = H W) on the GPU: the (starts, start_off, hw) of coco_rle_area / coco_rle_iou.  An annotation without a polygon, or whose
+    polygons cover no pixel centre column, is an empty mask.  Count, ONE host read of the N counts, their running sum, emit (afi_poly_rle_count,
+    afi_poly_rle_emit).  ws: a dense GPU buffer to use instead of a fresh workspace."""
+    xy, vert_off, poly_off, hw2, cap_off = polygons_batch(polygons, sizes)
+    N, cap_total = len(polygons), int(cap_off[-1])
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.AfiError("polygons_rle: the rasteriser runs on the GPU only; there is no CPU fallback")
+    hw = torch.from_numpy(hw2[:, 0] * hw2[:, 1]).to(dev)
+    if N == 0:
+        return torch.empty((0,), device=dev, dtype=torch.int32), torch.zeros((1,), device=dev, dtype=torch.int64), hw
+    n = _lib.load().afi_poly_rle_ws_bytes(cap_total)
+    if n < 0:
+        raise _lib.AfiError(f"polygons_rle: unsupported capacity {cap_total}")
+    if ws is None:
+        ws = new_workspace((n + 3) // 4 + 2, dev)
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < n or ws.data_ptr() % 8:
+        raise _lib.AfiError(f"polygons_rle: ws must be a dense, 8-byte aligned GPU buffer of at least {n} bytes")
+    wsb = ws.numel() * ws.element_size()
+    up = lambda a: torch.from_numpy(a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)).to(dev)      # noqa: E731  (no null pointer)
+    d_xy, d_voff, d_poff, d_hw2, d_cap = up(xy), up(vert_off), up(poly_off), up(hw2), up(cap_off)
+    nst = torch.empty((N,), device=dev, dtype=torch.int32)
+    call("afi_poly_rle_count", _p(d_xy), _p(d_voff), _p(d_poff), _p(d_hw2), _p(d_cap), N, cap_total, _p(ws), wsb, _p(nst), stream_ptr())
+    nstarts = nst.cpu().to(torch.int64)                     # the one host read
+    if bool((nstarts < 0).any()):
+        raise _lib.AfiError("polygons_rle: a mask's crossings exceeded its capacity bound (internal error: the bound is sum of dx / 5 + 2 per edge)")
+    start_off = torch.cat((torch.zeros((1,), dtype=torch.int64), torch.cumsum(nstarts, 0)))
+    total = int(start_off[-1])
+    starts = torch.empty((total,), device=dev, dtype=torch.int32)
+    start_off = start_off.to(dev)
+    if total:
+        call("afi_poly_rle_emit", _p(d_poff), _p(d_cap), N, cap_total, _p(ws), wsb, _p(start_off), _p(starts), stream_ptr())
+    return starts, start_off, hw
+
+
+def rle_decode(starts, start_off, hw, out=None):
+    """The bool [N, H, W] masks of N run-start lists on one common canvas ``hw`` = (H, W): starts int32 [S], start_off int64 [N + 1] on the GPU
+    (polygons_rle's, mask_paste_rle's after a running sum); pixel (y, x) is set iff the number of starts <= x H + y is odd (afi_rle_decode)."""
+    H, W = int(hw[0]), int(hw[1])
+    if H <= 0 or W <= 0 or H * W >= 1 << 31:
+        raise _lib.AfiError(f"rle_decode: a canvas with H, W > 0 and H W < 2^31 expected, got {(H, W)}")
+    N = start_off.numel() - 1
+    if N < 0:
+        raise _lib.AfiError("rle_decode: start_off of N + 1 elements expected, got an empty tensor")
+    so = _coco_arg("start_off", start_off, torch.int64)
+    st = _coco_arg("starts", starts, torch.int32)
+    if out is None:
+        out = torch.empty((N, H, W), device=so.device, dtype=torch.uint8)
+    elif not out.is_cuda or out.dtype not in (torch.uint8, torch.bool) or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
+        raise _lib.AfiError(f"rle_decode: out must be a dense uint8 / bool [{N}, {H}, {W}] tensor on the GPU")
+    if N:
+        call("afi_rle_decode", _p(st), _p(so), N, H, W, _p(out), stream_ptr())
+    return out.view(torch.bool)
 
 
 # ------------------------------------------------------------------------------------------------ bandwidth ops

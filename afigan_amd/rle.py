@@ -7,7 +7,8 @@ group follows", each group + 48 as one character; the value ends at the first gr
 An RLE is ``{"size": [H, W], "counts": str}``; ``decode`` and ``area`` also take the uncompressed form (``counts`` a sequence of ints).
 
 The device side (ops.mask_paste_rle) returns the starts; ``counts_from_starts`` and ``to_strings`` turn a whole image's detections into
-strings without a Python loop per run."""
+strings without a Python loop per run.  ``from_polygons`` is pycocotools' polygon-to-RLE conversion, rasterised on the device
+(ops.polygons_rle, csrc/poly_rle.hip)."""
 import numpy as np
 
 
@@ -118,6 +119,17 @@ def decode(rle):
 def area(rle):
     """The number of set pixels."""
     return int(_counts_of(rle)[1::2].sum())
+
+
+def from_polygons(polygons, sizes):
+    """pycocotools' frPyObjects + merge for polygon annotations, on the GPU (ops.polygons_rle): ``polygons`` a list of N annotations, each a list
+    of flat coordinate sequences; ``sizes`` (H, W) or one pair per annotation.  A list of N ``{"size": [H, W], "counts": str}``."""
+    from . import ops
+    _, _, _, hw2, _ = ops.polygons_batch(polygons, sizes)                  # (checked here too, so that nothing is uploaded for a bad input)
+    starts, start_off, _ = ops.polygons_rle(polygons, sizes)
+    starts, off = starts.cpu().numpy().astype(np.int64), start_off.cpu().numpy()
+    counts = [np.diff(starts[off[i]:off[i + 1]], prepend=0, append=int(hw2[i, 0]) * int(hw2[i, 1])) for i in range(len(polygons))]
+    return [{"size": [int(h), int(w)], "counts": s} for (h, w), s in zip(hw2.tolist(), to_strings(counts))]
 
 
 def to_rle(counts, hw):

@@ -720,6 +720,41 @@ int afi_coco_match(const double* iou, const long long* dt_off, const long long* 
                    const double* area_rng, int A, const double* iou_thr, int T, int max_g, int* dt_match, unsigned char* dt_ignore,
                    unsigned char* gt_ignore, void* ws, long long ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ COCO polygons as run-length starts, and their decode (csrc/poly_rle.hip)
+ * pycocotools' rleFrPoly, the union of one annotation's polygons (frPyObjects + merge) and decode, in the starts format above, so that
+ * polygon ground truth feeds afi_coco_rle_area / afi_coco_rle_iou directly.  A polygon is k >= 1 vertices (x, y) on a canvas of H x W pixels;
+ * all arithmetic is fp64, operation by operation as written (no contraction); (int) truncates toward zero:
+ *   X[j] = (int)(5 x_j + .5), Y[j] likewise, X[k] = X[0].  Edge j runs from (xs, ys) = (X[j], Y[j]) to (xe, ye) = (X[j + 1], Y[j + 1]); dx = |xe - xs|,
+ *   dy = |ye - ys|; flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye) swaps the two ends; s = dx >= dy ? (double)(ye - ys) / dx :
+ *   (double)(xe - xs) / dy; for d = 0 .. max(dx, dy), t = flip ? max(dx, dy) - d : d, the point is (u, v) = (t + xs, (int)(ys + s t + .5)) if
+ *   dx >= dy, else ((int)(xs + s t + .5), t + ys); an edge with dx = dy = 0 is the one point (xs, ys).  For consecutive points p - 1, p of the
+ *   list of all edges' points with u[p] != u[p - 1]: xd = u[p] < u[p - 1] ? u[p] : u[p] - 1, xd = (xd + .5) / 5 - .5, kept if xd is an integer in
+ *   0 .. W - 1; yd = min(v[p], v[p - 1]), yd = (yd + .5) / 5 - .5, clamped to [0, H], yd = ceil(yd); the crossing is a = (int)xd H + (int)yd.
+ *   The starts of a polygon are its crossings of odd multiplicity below H W, ascending.  A mask of several polygons is their union: the start of
+ *   rank r in its polygon counts +1 (r even) or -1 (r odd), and a position is a start of the union iff the running depth is zero on exactly
+ *   one side of the events at that position.  A mask without a polygon, or whose polygons give no start, is empty.
+ * The batch: xy [V][2] (double), vert_off [P + 1] and poly_off [N + 1] (long long: the vertices of polygon p, the polygons of mask m), hw [N][2]
+ *   = (H, W) of every mask (int32; masks of one call may differ in size; H W < 2^31 and |5 c + .5| < 2^30 for every coordinate c are the
+ *   CALLER's to check, as is that every polygon has a vertex), cap_off [P + 1] (long long) = the exclusive prefix of a per-polygon bound on the
+ *   crossings, sum over its edges of (dx / 5 + 2) with dx in upsampled units; cap_total = cap_off[P] < 2^31.  Every pointer is a device pointer.
+ * afi_poly_rle_ws_bytes(cap_total): the workspace of one call pair (8-byte sort keys and int32 starts per bounded crossing); -1: unsupported.
+ *   A smaller ws_bytes is AFI_ERR_BAD_ARG.  The workspace is read only after being written.
+ * afi_poly_rle_count: nstarts [N] (int32) = the number of starts of every mask, -1 for a mask whose crossings exceed its capacity (nothing is
+ *   written past a mask's slice).  One block per mask; a mask of at most AFI_POLY_RLE_LDS_CAP crossings is sorted in LDS, a larger one in its
+ *   slice of the workspace.
+ * afi_poly_rle_emit: after the caller scanned nstarts into start_off [N + 1] (long long): the starts of mask m, ascending, at
+ *   starts[start_off[m] ..] (int32).  ws: unchanged since afi_poly_rle_count with the same poly_off, cap_off, N, cap_total.
+ * afi_rle_decode: N masks of one common H x W as starts / start_off [N + 1]; out [N][H][W] bytes, row-major: pixel (y, x) = 1 iff the number of
+ *   starts <= x H + y is odd, else 0; every byte is written.
+ * N = 0 is accepted and launches nothing.  No atomics, no host synchronisation; bit-identical between runs. */
+#define AFI_POLY_RLE_LDS_CAP 4096
+long long afi_poly_rle_ws_bytes(long long cap_total);
+int afi_poly_rle_count(const double* xy, const long long* vert_off, const long long* poly_off, const int* hw, const long long* cap_off, int N,
+                       long long cap_total, void* ws, long long ws_bytes, int* nstarts, void* stream);
+int afi_poly_rle_emit(const long long* poly_off, const long long* cap_off, int N, long long cap_total, const void* ws, long long ws_bytes,
+                      const long long* start_off, int* starts, void* stream);
+int afi_rle_decode(const int* starts, const long long* start_off, int N, int H, int W, unsigned char* out, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
