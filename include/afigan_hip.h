@@ -357,7 +357,8 @@ int afi_conv3x3_wino_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int 
 int afi_conv3x3_wino_fwd_out16(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w_ohwi, const float* bias_or_null, int Cout,
                                afi_view_t out, int out_dtype, float* ws, long long ws_floats, void* stream);
 /* inference form: out = act(conv + bias), act 0 none / 1 LeakyReLU(0.2) / 2 ReLU; no backward will follow, so maps of >= 8192 pixels
- * take the F(4x4,3x3) tiling (4x fewer multiplies, ~3e-5 relative rounding) */
+ * take the F(4x4,3x3) tiling (4x fewer multiplies; max-norm rounding 3e-6 .. 6e-6 of the output scale at 128 .. 256 channels against F(2x2)'s
+ * 5e-7 .. 8e-7, what a plain fp32 evaluation of the same transforms loses: tests/test_gpu_wino.py) */
 int afi_conv3x3_wino_infer(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const float* w_ohwi, const float* bias_or_null, int Cout,
                            afi_view_t out, int act, float* ws, long long ws_floats, void* stream);
 int afi_conv3x3_wino_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w_ohwi, int Cin, afi_view_t dx,
