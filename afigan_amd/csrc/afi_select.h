@@ -1,5 +1,5 @@
-// What the selection stages of the RPN (rpn.hip) and of the ROI heads' box branch (roi.hip) share: the block prefix sum and the greedy NMS of
-// a sorted list of <= 1024 boxes, with or without classes.
+// What the selection stages of the RPN (rpn.hip), its training-side sampler (rpn_loss.hip) and the ROI heads' box branch (roi.hip) share: the
+// block prefix sum, the digit search of the radix select, and the greedy NMS of a sorted list of <= 1024 boxes, with or without classes.
 #pragma once
 #include "afi_common.h"
 
@@ -27,6 +27,27 @@ __device__ __forceinline__ int rpn_block_scan(int v, int* wtot, int* total) {
     }
     *total = tot;
     return inc + base;
+}
+
+// The digit d of a histogram (nbins a multiple of blockDim) that holds the need-th element counted from the top bin down, and the count of
+// the bins above it: res[0] = d, res[1] = above.  1 <= need <= sum(hist).  Ends with a barrier; hist is left as it was.  (The radix select of
+// afi_rpn_topk and of afi_rpn_sample.)
+__device__ __forceinline__ void rpn_find_digit(const int* hist, int nbins, int need, int* wtot, int* res) {
+    const int per = nbins / (int)blockDim.x, top = nbins - 1 - (int)threadIdx.x * per;
+    int own = 0;
+    for (int j = 0; j < per; ++j) own += hist[top - j];
+    if (threadIdx.x == 0) { res[0] = 0; res[1] = 0; }
+    int total;
+    const int inc = rpn_block_scan(own, wtot, &total);
+    int cum = inc - own;
+    if (cum < need && need <= inc) {
+        for (int j = 0; j < per; ++j) {
+            const int c = hist[top - j];
+            if (cum + c >= need) { res[0] = top - j; res[1] = cum; break; }
+            cum += c;
+        }
+    }
+    __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------ NMS

@@ -49,26 +49,6 @@ __device__ __forceinline__ const float* rpn_at(const AfiView& v, int img, int i,
 
 __device__ __forceinline__ u64 rpn_word(float v, int i) { return ((u64)rpn_key(v) << RPN_IDX_BITS) | (u64)((~(unsigned)i) & RPN_IDX_MASK); }
 
-// The digit d of a histogram (nbins a multiple of blockDim) that holds the need-th element counted from the top bin down, and the count of
-// the bins above it: res[0] = d, res[1] = above.  1 <= need <= sum(hist).  Ends with a barrier; hist is left as it was.
-__device__ __forceinline__ void rpn_find_digit(const int* hist, int nbins, int need, int* wtot, int* res) {
-    const int per = nbins / (int)blockDim.x, top = nbins - 1 - (int)threadIdx.x * per;
-    int own = 0;
-    for (int j = 0; j < per; ++j) own += hist[top - j];
-    if (threadIdx.x == 0) { res[0] = 0; res[1] = 0; }
-    int total;
-    const int inc = rpn_block_scan(own, wtot, &total);
-    int cum = inc - own;
-    if (cum < need && need <= inc) {
-        for (int j = 0; j < per; ++j) {
-            const int c = hist[top - j];
-            if (cum + c >= need) { res[0] = top - j; res[1] = cum; break; }
-            cum += c;
-        }
-    }
-    __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------------ top-k: grid histogram and filter (large maps)
 __global__ __launch_bounds__(256) void afi_rpn_zero_kernel(int* __restrict__ p, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;

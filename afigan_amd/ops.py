@@ -959,6 +959,112 @@ def rpn_merge(boxes, vals, keep, level_off, post_k):
     return ob, ol, counts
 
 
+# ------------------------------------------------------------------------------------------------ RPN training (rpn.py: RPN.losses)
+RPN_MAX_TOTAL_ANCHORS = 1 << 22             # anchors of one image over all levels: an index is 22 bits of a select word
+RPN_MAX_GT = 1024                           # ground-truth boxes per image (four LDS tiles of 256)
+RPN_MAX_BATCH = 4096                        # BATCH_SIZE_PER_IMAGE
+
+
+def _rpn_train_levels(name, level_hw, strides, cell_anchors, A):
+    """The checks rpn_match and rpn_loss share; returns (L, R, host level_hw array, host strides array, dense cell anchors)."""
+    L = len(level_hw)
+    if not 0 < L <= RPN_MAX_LEVELS or len(strides) != L:
+        raise _lib.AfiError(f"{name}: 1..{RPN_MAX_LEVELS} levels with one stride each, got {L} maps and {len(strides)} strides")
+    if not 0 < A <= RPN_MAX_ANCHORS or any(int(h) <= 0 or int(w) <= 0 for h, w in level_hw) or any(int(s) <= 0 for s in strides):
+        raise _lib.AfiError(f"{name}: A {A} (1..{RPN_MAX_ANCHORS}), positive map sizes and strides expected, got {list(level_hw)}, {list(strides)}")
+    R = sum(int(h) * int(w) * A for h, w in level_hw)
+    if R > RPN_MAX_TOTAL_ANCHORS:
+        raise _lib.AfiError(f"{name}: {R} anchors per image; at most {RPN_MAX_TOTAL_ANCHORS} (2^22) are supported")
+    if tuple(cell_anchors.shape) != (L, A, 4):
+        raise _lib.AfiError(f"{name}: cell anchors [{L}, {A}, 4] expected, got {tuple(cell_anchors.shape)}")
+    hw = (C.c_int * (2 * L))(*[int(s) for p in level_hw for s in p])
+    st = (C.c_int * L)(*[int(s) for s in strides])
+    return L, R, hw, st
+
+
+def _rpn_gt(name, gt, counts, cell_anchors):
+    """Shapes and limits first, then devices and dtypes (so that a limit is named whatever the tensors live on); returns (N, Gmax)."""
+    if gt.dim() != 3 or gt.shape[2] != 4 or gt.shape[1] < 1 or not gt.is_contiguous() or tuple(counts.shape) != (gt.shape[0],) or not counts.is_contiguous():
+        raise _lib.AfiError(f"{name}: dense ground truth [N, Gmax >= 1, 4] and counts [N] expected, got {tuple(gt.shape)} and {tuple(counts.shape)}")
+    if gt.shape[1] > RPN_MAX_GT:
+        raise _lib.AfiError(f"{name}: {gt.shape[1]} ground-truth boxes per image; at most {RPN_MAX_GT} are supported")
+    _check_cuda(gt, cell_anchors)
+    _check_i32(counts)
+    return gt.shape[0], gt.shape[1]
+
+
+def rpn_match(level_hw, strides, cell_anchors, A, gt, counts, thresholds=(0.3, 0.7)):
+    """Anchor labels of detectron2's RPN (Matcher with IOU_LABELS [0, -1, 1] and low-quality matches) over all levels: level_hw = [(H, W), ...],
+    cell_anchors [L, A, 4], gt [N, Gmax, 4] fp32 with counts [N] int32.  Returns (labels [N, R] int8, matched_idx [N, R] int32), R the anchors
+    of an image in level order, index (y W + x) A + a inside a level (afi_rpn_match)."""
+    L, R, hw, st = _rpn_train_levels("rpn_match", level_hw, strides, cell_anchors, A)
+    N, Gmax = _rpn_gt("rpn_match", gt, counts, cell_anchors)
+    cell = cell_anchors.contiguous()
+    t0, t1 = (float(t) for t in thresholds)
+    if not t0 <= t1:
+        raise _lib.AfiError(f"rpn_match: thresholds {thresholds} must ascend")
+    labels = torch.empty((N, R), device=gt.device, dtype=torch.int8)
+    midx = torch.empty((N, R), device=gt.device, dtype=torch.int32)
+    ws = new_workspace(N * Gmax, gt.device)
+    call("afi_rpn_match", hw, st, L, int(A), _p(cell), N, _p(gt), _p(counts), Gmax, t0, t1, _p(labels), _p(midx), _p(ws), N * Gmax, stream_ptr())
+    return labels, midx
+
+
+def rpn_sample(labels, keys, batch_per_image, positive_fraction):
+    """subsample_labels with caller-supplied randomness: of labels [N, R] int8, the min(#positives, int(batch_per_image positive_fraction))
+    positives and the min(#negatives, batch_per_image - num_pos) negatives with the smallest (key, anchor index) stay, every other label
+    becomes -1.  keys [N, R]: 32 bits per anchor (int32 or uint32 storage), compared unsigned.  Returns (labels [N, R] int8 -- a new tensor --,
+    sampled_idx [N, batch_per_image] int32: positives in ascending index, then negatives, then -1; n_pos [N], n_neg [N] int32) (afi_rpn_sample)."""
+    for t in (labels, keys):
+        if not t.is_cuda:
+            raise _lib.AfiError("the RPN sampling runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if labels.dtype != torch.int8 or keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise _lib.AfiError(f"rpn_sample: int8 labels and 32-bit integer keys expected, got {labels.dtype} and {keys.dtype}")
+    if labels.dim() != 2 or keys.shape != labels.shape or not labels.is_contiguous() or not keys.is_contiguous():
+        raise _lib.AfiError(f"rpn_sample: dense labels and keys [N, R] expected, got {tuple(labels.shape)} and {tuple(keys.shape)}")
+    N, R = labels.shape
+    B = int(batch_per_image)
+    if R > RPN_MAX_TOTAL_ANCHORS:
+        raise _lib.AfiError(f"rpn_sample: {R} anchors per image; at most {RPN_MAX_TOTAL_ANCHORS} (2^22) are supported")
+    if not 0 < B <= RPN_MAX_BATCH or not 0.0 <= float(positive_fraction) <= 1.0:
+        raise _lib.AfiError(f"rpn_sample: batch size per image {batch_per_image} (1..{RPN_MAX_BATCH}), positive fraction {positive_fraction} (0..1)")
+    out = torch.empty_like(labels)
+    sidx = torch.empty((N, B), device=labels.device, dtype=torch.int32)
+    n_pos = torch.empty((N,), device=labels.device, dtype=torch.int32)
+    n_neg = torch.empty((N,), device=labels.device, dtype=torch.int32)
+    call("afi_rpn_sample", _p(labels), _p(keys), N, R, B, int(B * float(positive_fraction)), _p(out), _p(sidx), _p(n_pos), _p(n_neg), stream_ptr())
+    return out, sidx, n_pos, n_neg
+
+
+def rpn_loss(heads, strides, cell_anchors, A, gt, counts, matched_idx, sampled_idx, n_pos, n_neg, weights=(1.0, 1.0, 1.0, 1.0), beta=0.0,
+             scale_cls=1.0, scale_loc=1.0):
+    """rpn_losses over the sampled anchors: heads = the pixel-major head outputs [N, Cpad, H_l, W_l] (channel a the logit, A + 4 a + c the
+    deltas).  Returns (loss [2] fp32 on the device: scale_cls * sum of the objectness terms, scale_loc * sum of the smooth-L1 terms of the
+    positives; grads: per level a dense pixel-major tensor like the head output holding d loss[0] / d logit and d loss[1] / d delta, exactly
+    zero outside the sample) (afi_rpn_loss)."""
+    L, R, hw, st = _rpn_train_levels("rpn_loss", [tuple(h.shape[2:]) for h in heads], strides, cell_anchors, A)
+    N, Gmax = _rpn_gt("rpn_loss", gt, counts, cell_anchors)
+    _check_cuda(*heads)
+    cell = cell_anchors.contiguous()
+    _check_i32(matched_idx, sampled_idx, n_pos, n_neg)
+    if any(h.dim() != 4 or h.shape[0] != N or h.shape[1] < 5 * A for h in heads):
+        raise _lib.AfiError(f"rpn_loss: every head output must be [N = {N}, >= {5 * A}, H, W], got {[tuple(h.shape) for h in heads]}")
+    B = sampled_idx.shape[1] if sampled_idx.dim() == 2 else 0
+    if tuple(matched_idx.shape) != (N, R) or tuple(sampled_idx.shape) != (N, B) or tuple(n_pos.shape) != (N,) or tuple(n_neg.shape) != (N,) \
+            or not (matched_idx.is_contiguous() and sampled_idx.is_contiguous() and n_pos.is_contiguous() and n_neg.is_contiguous()):
+        raise _lib.AfiError(f"rpn_loss: dense matched_idx [{N}, {R}], sampled_idx [{N}, B], n_pos / n_neg [{N}] expected, got "
+                            f"{tuple(matched_idx.shape)}, {tuple(sampled_idx.shape)}, {tuple(n_pos.shape)}, {tuple(n_neg.shape)}")
+    if not 0 < B <= RPN_MAX_BATCH or len(weights) != 4 or min(weights) <= 0 or not beta >= 0:
+        raise _lib.AfiError(f"rpn_loss: batch size per image {B} (1..{RPN_MAX_BATCH}), four positive weights and beta >= 0 expected")
+    grads = [new_pixel_major(*h.shape, h.device, zero=True) for h in heads]
+    loss = torch.empty((2,), device=gt.device, dtype=torch.float32)
+    hv = (View * L)(*[view_of(h) for h in heads])
+    gv = (View * L)(*[view_of(g) for g in grads])
+    call("afi_rpn_loss", hv, gv, hw, st, L, int(A), _p(cell), N, _p(gt), Gmax, _p(matched_idx), _p(sampled_idx), B, _p(n_pos), _p(n_neg),
+         *[float(w) for w in weights], float(beta), float(scale_cls), float(scale_loc), _p(loss), stream_ptr())
+    return loss, grads
+
+
 # ------------------------------------------------------------------------------------------------ ROI heads, box branch (roi_heads.py)
 ROI_MAX_CANDIDATES = 1024                   # M: the per-image candidate list afi_roi_nms holds in LDS
 ROI_MAX_POOLED = 14

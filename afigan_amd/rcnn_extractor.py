@@ -54,7 +54,7 @@ class GeneralizedRCNN_AFExtractor(nn.Module):
         try:
             from detectron2.modeling.proposal_generator import build_proposal_generator
         except Exception:
-            from .rpn import build_proposal_generator                  # the frozen, inference-only RPN of this package
+            from .rpn import build_proposal_generator                  # this package's RPN (frozen until RPN.trainable_(); losses: DESIGN 21)
         proposal_generator = build_proposal_generator(cfg, backbone.output_shape())
         try:
             from detectron2.modeling.roi_heads import build_roi_heads

@@ -593,6 +593,35 @@ int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld
 int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
                   float* out_logits, int* counts, void* stream);
 
+/* ------------------------------------------------------------------ RPN training: labels, sampling, losses (afigan_amd/rpn.py: RPN.losses)
+ * detectron2 v0.1.1's RPNOutputs._get_ground_truth (Matcher with low-quality matches), subsample_labels, Box2BoxTransform.get_deltas and
+ * rpn_losses.  The levels of an image are concatenated in the order given: level_hw = HOST array {H_0, W_0, H_1, ...}, strides = HOST array of L
+ * ints, cell_anchors = DEVICE [L][A][4]; global anchor index = the level's offset + (y W + x) A + a, the anchor box cell anchor a + (x, y) * stride
+ * (one fp32 addition per coordinate).  R = sum H_l W_l A <= 2^22, A <= 16, L <= 8, N <= 65535.  Ground truth: gt [N][Gmax][4] fp32 (x1, y1, x2, y2)
+ * with counts [N] (device int32; counts[n] is clamped to 0 .. Gmax), Gmax <= 1024.  No host synchronisation; bit-identical between runs.
+ * afi_rpn_match: IoU in fp32, every operation rounded once (area = (x2 - x1)(y2 - y1), w = max(min(x2) - max(x1), 0), inter = w h,
+ *   iou = inter > 0 ? inter / (area_gt + area_anchor - inter) : 0).  matched_idx [N][R] = the lowest box index that reaches the anchor's maximum
+ *   IoU; labels [N][R] (int8) = 0 below t0, -1 in [t0, t1), 1 from t1 up; then label 1 for every anchor whose IoU with a box equals that box's
+ *   maximum over all anchors (a box that overlaps nothing has maximum 0 and promotes every anchor with IoU 0: the reference's behaviour).
+ *   counts[n] = 0: every label 0, matched_idx 0.  ws: N * Gmax floats.
+ * afi_rpn_sample: keys [N][R] (32 bits each, compared unsigned).  num_pos = min(#label 1, num_pos_max), num_neg = min(#label 0,
+ *   batch_per_image - num_pos): the num_pos positives and num_neg negatives with the smallest (key, anchor index) keep their label in labels_out
+ *   (which must not be labels), every other label becomes -1.  sampled_idx [N][batch_per_image]: the sampled positives in ascending anchor
+ *   index, then the negatives likewise, then -1; n_pos / n_neg [N].  batch_per_image <= 4096.
+ * afi_rpn_loss: heads / grads = HOST arrays of L pixel-major views [N][H_l][W_l][>= 5 A]: channel a the logit, A + 4 a + c the deltas.  Over the
+ *   sampled anchors: objectness max(z, 0) - z t + log1p(exp(-|z|)) (t = 1 for the first n_pos entries of an image's list), and for the positives
+ *   smooth L1 (beta; |d| when beta < 1e-5) of delta - get_deltas(anchor, gt[matched_idx]) with weights (wx, wy, ww, wh), the target evaluated in
+ *   fp64 and rounded once; terms in fp32, sums in fp64.  loss[0] = scale_cls * sum, loss[1] = scale_loc * sum (device fp32); grads receives
+ *   d loss[0] / d logit and d loss[1] / d delta at the sampled anchors and is not touched elsewhere (the caller zero-fills it). */
+int afi_rpn_match(const int* level_hw, const int* strides, int L, int A, const float* cell_anchors, int N, const float* gt, const int* counts,
+                  int Gmax, float t0, float t1, signed char* labels, int* matched_idx, float* ws, long long ws_floats, void* stream);
+int afi_rpn_sample(const signed char* labels, const unsigned int* keys, int N, long long R, int batch_per_image, int num_pos_max,
+                   signed char* labels_out, int* sampled_idx, int* n_pos, int* n_neg, void* stream);
+int afi_rpn_loss(const afi_view_t* heads, const afi_view_t* grads, const int* level_hw, const int* strides, int L, int A,
+                 const float* cell_anchors, int N, const float* gt, int Gmax, const int* matched_idx, const int* sampled_idx, int batch_per_image,
+                 const int* n_pos, const int* n_neg, float wx, float wy, float ww, float wh, float beta, double scale_cls, double scale_loc,
+                 float* loss, void* stream);
+
 /* ------------------------------------------------------------------ frozen box branch of StandardROIHeads (afigan_amd/roi_heads.py)
  * detectron2 v0.1.1's ROIPooler (ROIAlignV2, aligned = True) and fast_rcnn_inference; the box head's FCs and the predictor between them run on
  * afi_conv1x1_fwd over the R = N P rows as pixels.  Boxes of an image are rows of a padded [N][P][4] list with counts[N] (device int32): the
