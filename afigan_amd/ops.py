@@ -1213,6 +1213,117 @@ def roi_pick(cand, keep, D):
     return ob, os_, oc, counts, trunc
 
 
+# ------------------------------------------------------------------------------------------------ ROI heads, box branch in training (roi_heads.py)
+def _roi_train_lists(name, proposals, counts_p, gt, counts_g):
+    """Shapes and limits first, then devices and dtypes (as _rpn_gt does); returns (N, P, Gmax)."""
+    if proposals.dim() != 3 or proposals.shape[2] != 4 or proposals.shape[1] < 1 or not proposals.is_contiguous() or gt.dim() != 3 \
+            or gt.shape[2] != 4 or gt.shape[1] < 1 or gt.shape[0] != proposals.shape[0] or not gt.is_contiguous() \
+            or tuple(counts_p.shape) != (gt.shape[0],) or tuple(counts_g.shape) != (gt.shape[0],) or not counts_p.is_contiguous() \
+            or not counts_g.is_contiguous():
+        raise _lib.AfiError(f"{name}: dense proposals [N, P >= 1, 4], ground truth [N, Gmax >= 1, 4] and two counts [N] expected, got "
+                            f"{tuple(proposals.shape)}, {tuple(gt.shape)}, {tuple(counts_p.shape)}, {tuple(counts_g.shape)}")
+    if gt.shape[1] > RPN_MAX_GT:
+        raise _lib.AfiError(f"{name}: {gt.shape[1]} ground-truth boxes per image; at most {RPN_MAX_GT} are supported")
+    if proposals.shape[1] + gt.shape[1] > RPN_MAX_TOTAL_ANCHORS:
+        raise _lib.AfiError(f"{name}: {proposals.shape[1] + gt.shape[1]} candidates per image; at most {RPN_MAX_TOTAL_ANCHORS} (2^22) are supported")
+    _check_cuda(proposals, gt)
+    _check_i32(counts_p, counts_g)
+    return proposals.shape[0], proposals.shape[1], gt.shape[1]
+
+
+def roi_label(proposals, counts_p, gt, counts_g, iou_thresh=0.5, append_gt=True):
+    """Proposal labels of detectron2's ROIHeads (Matcher with one threshold and IOU_LABELS [0, 1], no low-quality matches) over the padded
+    candidate list of every image: its counts_p proposals, then (append_gt) its counts_g ground-truth boxes.  proposals [N, P, 4], gt
+    [N, Gmax, 4] fp32, counts int32.  Returns (labels [N, P + Gmax] int8: 1 / 0 / -1 for padding, matched_idx [N, P + Gmax] int32)
+    (afi_roi_label)."""
+    N, P, Gmax = _roi_train_lists("roi_label", proposals, counts_p, gt, counts_g)
+    labels = torch.empty((N, P + Gmax), device=gt.device, dtype=torch.int8)
+    midx = torch.empty((N, P + Gmax), device=gt.device, dtype=torch.int32)
+    call("afi_roi_label", _p(proposals), _p(counts_p), N, P, _p(gt), _p(counts_g), Gmax, int(bool(append_gt)), float(iou_thresh), _p(labels),
+         _p(midx), stream_ptr())
+    return labels, midx
+
+
+def roi_gather_samples(proposals, counts_p, gt, gt_classes, counts_g, matched_idx, sampled_idx, n_pos, n_neg, K, append_gt=True):
+    """The padded training list of rpn_sample's sample of roi_label's candidates: (boxes [N, B, 4], counts [N] = n_pos + n_neg, gt_classes
+    [N, B] int32 -- the matched box's class for the n_pos first rows, K (background) for the other sampled rows, -1 past the count --,
+    gt_boxes [N, B, 4]: the matched box, zeros when the image has none) (afi_roi_gather_samples)."""
+    N, P, Gmax = _roi_train_lists("roi_gather_samples", proposals, counts_p, gt, counts_g)
+    _check_i32(gt_classes, matched_idx, sampled_idx, n_pos, n_neg)
+    B = sampled_idx.shape[1] if sampled_idx.dim() == 2 else 0
+    if tuple(gt_classes.shape) != (N, Gmax) or tuple(matched_idx.shape) != (N, P + Gmax) or tuple(sampled_idx.shape) != (N, B) \
+            or tuple(n_pos.shape) != (N,) or tuple(n_neg.shape) != (N,) \
+            or not all(t.is_contiguous() for t in (gt_classes, matched_idx, sampled_idx, n_pos, n_neg)):
+        raise _lib.AfiError(f"roi_gather_samples: dense gt_classes [{N}, {Gmax}], matched_idx [{N}, {P + Gmax}], sampled_idx [{N}, B], n_pos / "
+                            f"n_neg [{N}] expected, got {tuple(gt_classes.shape)}, {tuple(matched_idx.shape)}, {tuple(sampled_idx.shape)}, "
+                            f"{tuple(n_pos.shape)}, {tuple(n_neg.shape)}")
+    if not 0 < B <= RPN_MAX_BATCH or not 0 < int(K) <= ROI_MAX_CLASSES:
+        raise _lib.AfiError(f"roi_gather_samples: batch size per image {B} (1..{RPN_MAX_BATCH}) and K {K} (1..{ROI_MAX_CLASSES}) expected")
+    dev = gt.device
+    boxes = torch.empty((N, B, 4), device=dev, dtype=torch.float32)
+    gboxes = torch.empty((N, B, 4), device=dev, dtype=torch.float32)
+    counts = torch.empty((N,), device=dev, dtype=torch.int32)
+    cls = torch.empty((N, B), device=dev, dtype=torch.int32)
+    call("afi_roi_gather_samples", _p(proposals), _p(counts_p), N, P, _p(gt), _p(gt_classes), _p(counts_g), Gmax, int(bool(append_gt)),
+         _p(matched_idx), _p(sampled_idx), _p(n_pos), _p(n_neg), B, int(K), _p(boxes), _p(counts), _p(cls), _p(gboxes), stream_ptr())
+    return boxes, counts, cls, gboxes
+
+
+def roi_box_loss(pred, K, agnostic, boxes, counts, gt_classes, gt_boxes, weights=(10.0, 10.0, 5.0, 5.0), beta=0.0):
+    """FastRCNNOutputs' two losses over the padded training list: pred = the predictor's output [N B, >= K + 1 + 4 Kb] with dense rows (K + 1
+    logits, background at K, then the deltas), boxes / gt_boxes [N, B, 4], counts [N], gt_classes [N, B] int32.  Returns (loss [2] fp32 on the
+    device: cross-entropy and smooth L1, each divided by Rtot = sum(counts); dpred like pred: d loss[0] / d logit and d loss[1] / d delta, every
+    other entry zero) (afi_roi_box_loss)."""
+    K, Kb = int(K), 1 if agnostic else int(K)
+    N, B = boxes.shape[:2] if boxes.dim() == 3 else (0, 0)
+    p2 = pred.reshape(pred.shape[0], -1) if pred.dim() == 4 and pred.shape[2:] == (1, 1) and pred.stride(1) == 1 else pred
+    if p2.dim() != 2 or p2.shape[0] != N * B or p2.shape[1] < K + 1 + 4 * Kb or p2.stride(1) != 1 or not 0 < K <= ROI_MAX_CLASSES \
+            or tuple(boxes.shape) != (N, B, 4) or tuple(gt_boxes.shape) != (N, B, 4) or tuple(counts.shape) != (N,) \
+            or tuple(gt_classes.shape) != (N, B) or not all(t.is_contiguous() for t in (boxes, gt_boxes, counts, gt_classes)):
+        raise _lib.AfiError(f"roi_box_loss: pred [{N * B}, >= {K + 1 + 4 * Kb}] with dense rows, dense boxes and gt_boxes [N, B, 4], counts [N], "
+                            f"gt_classes [N, B] and 1 <= K <= {ROI_MAX_CLASSES} expected, got {tuple(pred.shape)}, {tuple(boxes.shape)}, "
+                            f"{tuple(gt_boxes.shape)}, {tuple(counts.shape)}, {tuple(gt_classes.shape)}, K {K}")
+    if not 0 < B <= RPN_MAX_BATCH or len(weights) != 4 or min(weights) <= 0 or not beta >= 0:
+        raise _lib.AfiError(f"roi_box_loss: batch size per image {B} (1..{RPN_MAX_BATCH}), four positive weights and beta >= 0 expected")
+    _check_cuda(pred, boxes, gt_boxes)
+    _check_i32(counts, gt_classes)
+    ld = p2.stride(0)
+    dpred = new_workspace(N * B * ld, pred.device).view(N * B, ld)
+    loss = torch.empty((2,), device=pred.device, dtype=torch.float32)
+    nws = int(_lib.load().afi_roi_box_loss_ws_floats())
+    ws = new_workspace(nws, pred.device)
+    call("afi_roi_box_loss", _p(p2), ld, N, B, K, int(bool(agnostic)), _p(boxes), _p(counts), _p(gt_classes), _p(gt_boxes),
+         *[float(w) for w in weights], float(beta), _p(loss), _p(dpred), _p(ws), nws, stream_ptr())
+    return loss, dpred[:, :p2.shape[1]]
+
+
+def roi_align_bwd(dpooled, level_shapes, min_level, boxes, counts, sampling_ratio=0):
+    """The backward of roi_align: dpooled = dense pixel-major [N B, C, S, S], level_shapes = [(H_l, W_l), ...], boxes [N, B, 4] with counts [N]
+    int32.  Returns one dense pixel-major gradient [N, C, H_l, W_l] per level, every element written (zero where no box reaches)
+    (afi_roi_align_bwd: one block per 8 x 8 tile of a level, no atomics)."""
+    L = len(level_shapes)
+    if not 0 < L <= RPN_MAX_LEVELS or any(int(h) <= 0 or int(w) <= 0 for h, w in level_shapes):
+        raise _lib.AfiError(f"roi_align_bwd: 1..{RPN_MAX_LEVELS} levels of positive size, got {list(level_shapes)}")
+    N, B = boxes.shape[:2] if boxes.dim() == 3 else (0, 0)
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or B < 1 or not boxes.is_contiguous() or tuple(counts.shape) != (N,) or not counts.is_contiguous():
+        raise _lib.AfiError(f"roi_align_bwd: dense boxes [N, B, 4] and counts [N] expected, got {tuple(boxes.shape)} and {tuple(counts.shape)}")
+    if dpooled.dim() != 4 or dpooled.shape[0] != N * B or dpooled.shape[2] != dpooled.shape[3] or not is_dense_pm(dpooled) or dpooled.shape[1] % 4:
+        raise _lib.AfiError(f"roi_align_bwd: a dense pixel-major [{N * B}, C % 4 == 0, S, S] gradient expected, got {tuple(dpooled.shape)}")
+    C_, S = dpooled.shape[1:3]
+    if not 0 < S <= ROI_MAX_POOLED or sampling_ratio < 0:
+        raise _lib.AfiError(f"roi_align_bwd: pooled size {S} (1..{ROI_MAX_POOLED}), sampling_ratio {sampling_ratio} (>= 0)")
+    _check_cuda(dpooled, boxes)
+    _check_i32(counts)
+    grads = [new_pixel_major(N, C_, int(h), int(w), boxes.device) for h, w in level_shapes]
+    views = (View * L)(*[view_of(g) for g in grads])
+    hw = (C.c_int * (2 * L))(*[int(s) for p in level_shapes for s in p])
+    nws = int(_lib.load().afi_roi_align_bwd_ws_floats(N, B))
+    ws = new_workspace(nws, boxes.device)
+    call("afi_roi_align_bwd", _p(dpooled), views, hw, L, int(min_level), N, C_, _p(boxes), _p(counts), B, int(S), int(sampling_ratio), _p(ws), nws,
+         stream_ptr())
+    return grads
+
+
 # ------------------------------------------------------------------------------------------------ ROI heads, mask branch (roi_heads.py)
 MASK_MAX_SIDE = 64                          # M: the mask afi_mask_paste holds in LDS
 

@@ -19,7 +19,13 @@ Per image, on the padded proposal list boxes [N, P, 4] with counts [N] (``RPN.fo
     change the result (greedy NMS in score order is decided by the list's prefix up to the last kept box).  ``forward`` raises then.
 
 Keys: ``box_head.fc{i}.{weight, bias}``, ``box_predictor.{cls_score, bbox_pred}.{weight, bias}`` -- detectron2's, so a detector checkpoint's
-``roi_heads.box_*`` keys load with strict=True.  Every parameter has requires_grad False.
+``roi_heads.box_*`` keys load with strict=True.  Every parameter has requires_grad False until ``trainable_()``.
+
+Training, box branch (``StandardROIHeads.losses``, and ``forward`` in training mode with ``targets``): ROIHeads.label_and_sample_proposals,
+get_deltas, softmax_cross_entropy_loss and smooth_l1_loss on afi_roi_label / afi_rpn_sample / afi_roi_gather_samples / afi_roi_box_loss
+(csrc/roi_loss.hip), the pooler and head forward on the kernels above, their backward on afi_conv1x1_dgrad / afi_conv1x1_wgrad / afi_relu_bwd
+and afi_roi_align_bwd (``_ROIBoxLossFn``).  The sample is decided by 32-bit keys, as in ``RPN.losses``.  One IOU_THRESHOLDS entry with
+IOU_LABELS [0, 1]; the mask loss, cascade training, crowd handling and TRAIN_ON_PRED_BOXES are out of scope (AfiError).
 
 Kernels: afi_roi_align; the FCs and the predictor are afi_conv1x1_fwd over the R = N P rows as pixels (fc1 reads the pooled [R][S][S][C]
 memory in place, its weight permuted once from [out][C][S][S] to [out][S][S][C]; cls_score and bbox_pred are ONE weight, zero-padded to a
@@ -57,11 +63,11 @@ import math
 import torch
 import torch.nn as nn
 
-from . import ops, rle
+from . import _lib, ops, rle
 from ._lib import AfiError
 from .frozen import FROZEN_BN_EPS, FrozenBatchNorm2d, cfg_get, check_feature, conv3x3, fold_conv, prepared
 from .registry import detectron2_or_local
-from .rpn import SCALE_CLAMP, Boxes
+from .rpn import SCALE_CLAMP, Boxes, Proposals
 
 ROI_MAX_CANDIDATES = ops.ROI_MAX_CANDIDATES
 
@@ -353,9 +359,113 @@ def _reg_weights(key, w):
     return out
 
 
+class _ROIBoxLossFn(torch.autograd.Function):
+    """(loss_cls, loss_box_reg) of the features and the parameters of the FCs and the predictor.  Forward: afi_roi_label, afi_rpn_sample,
+    afi_roi_gather_samples, then the pooler and ``_run_head`` -- the very kernels inference runs -- on the sampled boxes, then afi_roi_box_loss,
+    which also leaves d loss / d predictor output.  Backward: the two upstream scalars as one per-column multiply of that gradient;
+    afi_conv1x1_dgrad / afi_conv1x1_wgrad and the bias column sums for the predictor and every FC, afi_relu_bwd between them (cls_score /
+    bbox_pred split back out of the concatenated weight, fc1's weight gradient permuted from [out][S][S][C] back to [out][C S S]); then
+    afi_roi_align_bwd.  Proposals, labels and regression targets are not differentiable."""
+    NARGS = 8                              # the non-differentiable leading arguments of forward
+
+    @staticmethod
+    @_lib.ctx_forward
+    def forward(ctx, heads, pboxes, pcounts, gt, gcls, gcounts, keys, nlev, *ts):
+        xs = [ops.pixel_major(x.detach()) for x in ts[:nlev]]
+        head, pr, pool = heads.box_head, heads.box_predictor, heads.box_pooler
+        K, B = heads.num_classes, heads.batch_size_per_image
+        labels, midx = ops.roi_label(pboxes, pcounts, gt, gcounts, heads.iou_threshold, heads.proposal_append_gt)
+        if keys is None:                                     # every 32-bit pattern equally likely, from torch's generator for this device
+            keys = torch.randint(-2 ** 31, 2 ** 31, labels.shape, device=labels.device, dtype=torch.int32)
+        labels, sidx, n_pos, n_neg = ops.rpn_sample(labels, keys, B, heads.positive_fraction)
+        boxes, counts, cls, gboxes = ops.roi_gather_samples(pboxes, pcounts, gt, gcls, gcounts, midx, sidx, n_pos, n_neg, K,
+                                                            heads.proposal_append_gt)
+        pooled = pool(xs, boxes, counts)
+        w1, wp, bp = heads._prepare()
+        pred, _, acts = heads._run_head(head, [], (w1, wp, bp), pooled)
+        loss, dpred = ops.roi_box_loss(pred, K, pr.cls_agnostic_bbox_reg, boxes, counts, cls, gboxes, heads.box_weights, heads.smooth_l1_beta)
+        ctx.save_for_backward(w1, wp, *[fc.weight.detach() for fc in head.fcs[1:]], pooled, *acts, dpred, boxes, counts)
+        ctx.nlev, ctx.nfc, ctx.nc, ctx.nb = nlev, len(head.fcs), pr.cls_score.weight.shape[0], pr.bbox_pred.weight.shape[0]
+        ctx.level_shapes, ctx.min_level, ctx.sampling_ratio = [tuple(x.shape[2:]) for x in xs], pool.min_level, pool.sampling_ratio
+        heads.last_assignment = {"labels": labels, "matched_idx": midx, "sampled_idx": sidx, "n_pos": n_pos, "n_neg": n_neg, "boxes": boxes,
+                                 "counts": counts, "gt_classes": cls, "gt_boxes": gboxes, "pred": pred}
+        return loss[0], loss[1]
+
+    @staticmethod
+    @_lib.ctx_backward
+    def backward(ctx, dcls, dbox):
+        sv, L, F, nc, nb = ctx.saved_tensors, ctx.nlev, ctx.nfc, ctx.nc, ctx.nb
+        w1, wp, fcw = sv[0], sv[1], sv[2:1 + F]
+        pooled, acts = sv[1 + F], sv[2 + F:2 + 2 * F]
+        dpred, boxes, counts = sv[2 + 2 * F:]
+        na = _ROIBoxLossFn.NARGS
+        need = ctx.needs_input_grad
+        need_x, need_w = any(need[na:na + L]), any(need[na + L:])
+        R, Cp = dpred.shape
+        dev = dpred.device
+        # the kernel left d loss_cls / d logit in columns 0..K and d loss_box_reg / d delta behind them: the two upstream scalars, per column
+        s = torch.zeros(Cp, device=dev, dtype=torch.float32)
+        s[:nc], s[nc:nc + nb] = dcls.float(), dbox.float()
+        g = _rows_as_pixels(dpred * s)
+        x0 = pooled.permute(0, 2, 3, 1).reshape(R, -1)                      # fc1's input rows, in the pooled memory's [S][S][C] order
+        ins = [_rows_as_pixels(x0)] + [_rows_as_pixels(a) for a in acts]    # ins[k]: the input of FC k; ins[F]: the predictor's
+        pgrads = []
+
+        def layer_grads(dy, x):
+            """(weight gradient [Cout, Cin], bias gradient [Cout]) of one FC seen as a 1x1 conv over the R rows."""
+            cout, cin = dy.shape[1], x.shape[1]
+            dw = torch.zeros((cout, cin), device=dev, dtype=torch.float32)
+            _lib.call("afi_conv1x1_wgrad", ops.view_of(dy), ops.view_of(x), 1, 1, R, cout, cin, ops._p(dw), 1.0, ops.stream_ptr())
+            db = torch.zeros((cout,), device=dev, dtype=torch.float32)
+            ops.colsum_accum(_pixels_as_rows(dy), db)
+            return dw, db
+        if need_w:
+            dwp, dbp = layer_grads(g, ins[F])
+            pgrads = [dwp[:nc], dbp[:nc], dwp[nc:nc + nb], dbp[nc:nc + nb]]
+        dx, fgrads = ops.conv1x1_dgrad(g, wp), []
+        for k in reversed(range(F)):
+            du = ops.relu_bwd(dx, ins[k + 1])
+            if need_w:
+                dw, db = layer_grads(du, ins[k])
+                if k == 0:                                                   # back to the parameter's [out][C][S][S] order
+                    C_, S = pooled.shape[1], pooled.shape[2]
+                    dw = dw.view(-1, S, S, C_).permute(0, 3, 1, 2).reshape(dw.shape[0], -1)
+                fgrads = [dw, db] + fgrads
+            if k > 0 or need_x:
+                dx = ops.conv1x1_dgrad(du, fcw[k - 1] if k > 0 else w1)
+        dxs = [None] * L
+        if need_x:
+            C_, S = pooled.shape[1], pooled.shape[2]
+            dpooled = _pixels_as_rows(dx).view(R, S, S, C_).permute(0, 3, 1, 2)
+            dxs = ops.roi_align_bwd(dpooled, ctx.level_shapes, ctx.min_level, boxes, counts, ctx.sampling_ratio)
+            dxs = [d if n else None for d, n in zip(dxs, need[na:na + L])]
+        h = fgrads + pgrads if need_w else [None] * (2 * F + 4)
+        return (*[None] * na, *dxs, *[v if n else None for v, n in zip(h, need[na + L:])])
+
+
+def _make_sampled(image_size, boxes, gt_classes, gt_boxes):
+    """One image's sampled proposals in training: ``proposal_boxes``, ``gt_classes`` (int64, NUM_CLASSES = background) and ``gt_boxes``."""
+    try:
+        from detectron2.structures import Boxes as D2Boxes, Instances
+    except Exception:
+        r = Proposals(tuple(image_size), Boxes(boxes), None)
+        r.gt_classes, r.gt_boxes = gt_classes, Boxes(gt_boxes)
+        return r
+    r = Instances(tuple(image_size))
+    r.proposal_boxes = D2Boxes(boxes)
+    r.gt_classes = gt_classes
+    r.gt_boxes = D2Boxes(gt_boxes)
+    return r
+
+
+def _target_field(t, name):
+    v = t.get(name) if isinstance(t, dict) else getattr(t, name, None)
+    return getattr(v, "tensor", v)
+
+
 @ROI_HEADS_REGISTRY.register()
 class StandardROIHeads(nn.Module):
-    conv_norm_heads = False            # the conv box head and the normed mask head: CascadeROIHeads only
+    conv_norm_heads = False           # the conv box head and the normed mask head: CascadeROIHeads only
 
     def _refuse_name(self, name):
         return AfiError(f"roi_heads: MODEL.ROI_HEADS.NAME {name!r} is not supported (StandardROIHeads only; CascadeROIHeads is out of scope)")
@@ -414,6 +524,32 @@ class StandardROIHeads(nn.Module):
                                                       cfg_get(mh, "NORM", ""), bool(cfg_get(mh, "CLS_AGNOSTIC_MASK", False)), norms=self.conv_norm_heads)
         for p in self.parameters():
             p.requires_grad_(False)
+        # ---- the training side (losses): read here, so that a config it cannot honour fails at construction
+        thr = [float(t) for t in cfg_get(rh, "IOU_THRESHOLDS", [0.5])]
+        if len(thr) != 1:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.IOU_THRESHOLDS {thr} is not supported (one threshold only)")
+        if [int(v) for v in cfg_get(rh, "IOU_LABELS", [0, 1])] != [0, 1]:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.IOU_LABELS {list(rh.IOU_LABELS)} is not supported ([0, 1] only)")
+        self.iou_threshold = thr[0]
+        self.batch_size_per_image = int(cfg_get(rh, "BATCH_SIZE_PER_IMAGE", 512))
+        self.positive_fraction = float(cfg_get(rh, "POSITIVE_FRACTION", 0.25))
+        if not 0 < self.batch_size_per_image <= ops.RPN_MAX_BATCH:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE {self.batch_size_per_image} is outside 1..{ops.RPN_MAX_BATCH}")
+        if not 0.0 <= self.positive_fraction <= 1.0:
+            raise AfiError(f"roi_heads: MODEL.ROI_HEADS.POSITIVE_FRACTION {self.positive_fraction} is outside 0..1")
+        self.proposal_append_gt = bool(cfg_get(rh, "PROPOSAL_APPEND_GT", True))
+        self.smooth_l1_beta = float(cfg_get(bh, "SMOOTH_L1_BETA", 0.0))
+        if not self.smooth_l1_beta >= 0:
+            raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA {self.smooth_l1_beta} must not be negative")
+        self.last_assignment = None
+
+    def trainable_(self, flag=True):
+        """Turn the parameters of the box head and the box predictor into trainable ones (or back).  The prepared weights follow the
+        parameters' versions (frozen.prepared), so an optimizer step is seen by the next call."""
+        for mod in (self.box_head, self.box_predictor):
+            for p in mod.parameters():
+                p.requires_grad_(bool(flag))
+        return self
 
     def _make_box_head(self, bh):
         """One FastRCNNConvFCHead and its FastRCNNOutputLayers from MODEL.ROI_BOX_HEAD."""
@@ -468,8 +604,9 @@ class StandardROIHeads(nn.Module):
         return prepared(self, "mask_prep", ts, build)
 
     # ------------------------------------------------------------------ checks
-    def _check(self, features, boxes=None, counts=None):
-        if self.training and torch.is_grad_enabled():
+    def _check(self, features, boxes=None, counts=None, train=False):
+        """train: the call computes losses (targets were given), so gradients may flow; every other call is forward-only."""
+        if not train and self.training and torch.is_grad_enabled():
             raise AfiError("roi_heads: the ROI heads are inference-only (frozen): call .eval(), or run them under torch.no_grad(); the detection "
                            "losses and training are out of scope")
         missing = [f for f in self.in_features if f not in features]
@@ -481,7 +618,7 @@ class StandardROIHeads(nn.Module):
             _check_feature("roi_heads", f"feature {f}", x)
             if x.dim() != 4 or x.shape[1] != C_ or x.shape[0] != xs[0].shape[0]:
                 raise AfiError(f"roi_heads: feature {f} has shape {tuple(x.shape)}; [N, {C_}, H, W] expected")
-            if torch.is_grad_enabled() and x.requires_grad:
+            if not train and torch.is_grad_enabled() and x.requires_grad:
                 raise AfiError("roi_heads: the ROI heads are forward-only: run them under torch.no_grad() or detach their inputs")
         if boxes is not None:
             _check_feature("roi_heads", "boxes", boxes)
@@ -595,16 +732,10 @@ class StandardROIHeads(nn.Module):
         out = (r["boxes"], r["scores"], r["classes"], r["counts"], r["truncated"])
         return out + (masks,) if self.mask_on else out
 
-    def forward(self, images, features, proposals, targets=None):
-        """detectron2's StandardROIHeads.forward at inference: (one result per image -- image_size, pred_boxes, scores, pred_classes (int64),
-        sorted by score --, {}).  One device-to-host read, of counts and truncated."""
-        if targets is not None:
-            raise AfiError("roi_heads: targets given -- the detection losses and label assignment are out of scope (inference only)")
-        xs = self._check(features)
-        sizes = [(int(h), int(w)) for h, w in images.image_sizes]
-        N, dev = xs[0].shape[0], xs[0].device
-        if len(sizes) != N or len(proposals) != N:
-            raise AfiError(f"roi_heads: {len(sizes)} image sizes and {len(proposals)} proposal lists for a batch of {N}")
+    # ------------------------------------------------------------------ training (the box branch)
+    @staticmethod
+    def _padded_proposals(proposals, N, dev):
+        """The images' ``proposal_boxes`` as one padded [N, P, 4] tensor and counts [N] int32; the counts come from the shapes."""
         pbs = []
         for p in proposals:
             b = p.proposal_boxes
@@ -615,7 +746,100 @@ class StandardROIHeads(nn.Module):
         boxes = torch.zeros((N, P, 4), device=dev, dtype=torch.float32)
         for n, b in enumerate(pbs):
             boxes[n, :b.shape[0]] = b
-        counts = torch.tensor([int(b.shape[0]) for b in pbs], dtype=torch.int32).to(dev)
+        return boxes, torch.tensor([int(b.shape[0]) for b in pbs], dtype=torch.int32).to(dev)
+
+    def _targets(self, targets, N, device):
+        """The images' boxes and classes as padded [N, Gmax, 4] fp32 / [N, Gmax] int32 tensors and counts [N] int32 on the device.  Every target
+        carries ``gt_boxes`` (a Boxes or a [G, 4] tensor) and ``gt_classes`` [G], as attributes or as dict entries."""
+        if len(targets) != N:
+            raise AfiError(f"roi_heads: {len(targets)} targets for a batch of {N}")
+        boxes, classes = [], []
+        for t in targets:
+            b, c = _target_field(t, "gt_boxes"), _target_field(t, "gt_classes")
+            if not torch.is_tensor(b) or b.dim() != 2 or b.shape[1] != 4 or not torch.is_tensor(c) or c.dim() != 1 or c.shape[0] != b.shape[0]:
+                raise AfiError("roi_heads: every target needs gt_boxes (a Boxes or a [G, 4] tensor) and gt_classes [G]")
+            if c.is_floating_point() or c.dtype == torch.bool:
+                raise AfiError(f"roi_heads: gt_classes must be integers, got {c.dtype}")
+            boxes.append(b)
+            classes.append(c)
+        gmax = max(b.shape[0] for b in boxes)
+        if gmax > ops.RPN_MAX_GT:
+            raise AfiError(f"roi_heads: {gmax} ground-truth boxes in one image; at most {ops.RPN_MAX_GT} are supported")
+        allc = torch.cat([c.reshape(-1).to(torch.int64) for c in classes]) if gmax else None
+        if allc is not None and allc.numel():
+            lo, hi = torch.stack([allc.min(), allc.max()]).tolist()         # (the one host read of a call whose classes live on the device)
+            if lo < 0 or hi >= self.num_classes:
+                raise AfiError(f"roi_heads: gt_classes must lie in 0..{self.num_classes - 1} (MODEL.ROI_HEADS.NUM_CLASSES {self.num_classes}), "
+                               f"got {lo}..{hi}")
+        gt = torch.zeros((N, max(gmax, 1), 4), device=device, dtype=torch.float32)
+        gc = torch.zeros((N, max(gmax, 1)), device=device, dtype=torch.int32)
+        for n, (b, c) in enumerate(zip(boxes, classes)):
+            if b.shape[0]:
+                gt[n, :b.shape[0]] = b.detach().to(device=device, dtype=torch.float32)
+                gc[n, :b.shape[0]] = c.detach().to(device=device, dtype=torch.int32)
+        return gt, gc, torch.tensor([b.shape[0] for b in boxes], dtype=torch.int32).to(device)
+
+    def _refuse_training(self):
+        if isinstance(self.box_head, nn.ModuleList):
+            raise AfiError("roi_heads: CascadeROIHeads is inference-only (frozen): cascade training is out of scope")
+        if self.mask_on:
+            raise AfiError("roi_heads: these heads were built with masks=True and the mask loss is not built yet: train heads built without "
+                           "the mask branch (box losses only)")
+
+    def losses_padded(self, features, boxes, counts, gt, gt_classes, gt_counts, keys=None):
+        """``losses`` on padded device tensors: proposals boxes [N, P, 4] / counts [N] (``RPN.forward_padded``'s layout), ground truth gt
+        [N, Gmax, 4] fp32, gt_classes [N, Gmax] int32, gt_counts [N] int32.  No host read."""
+        self._refuse_training()
+        xs = self._check(features, boxes, counts, train=True)
+        _check_feature("roi_heads", "gt boxes", gt)
+        h, pr = self.box_head, self.box_predictor
+        params = [t for fc in h.fcs for t in (fc.weight, fc.bias)] + [pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias]
+        out = _ROIBoxLossFn.apply(self, boxes.detach().contiguous(), counts.contiguous(), gt.contiguous(), gt_classes.contiguous(),
+                                  gt_counts.contiguous(), keys, len(xs), *xs, *params)
+        return {"loss_cls": out[0], "loss_box_reg": out[1]}
+
+    def losses(self, images, features, proposals, targets, keys=None):
+        """{"loss_cls", "loss_box_reg"} of detectron2's StandardROIHeads in training (box branch), differentiable in the features and, after
+        ``trainable_()``, the parameters of the box head and predictor.  proposals: one object with ``proposal_boxes`` per image; targets: one
+        object (or dict) with ``gt_boxes`` and ``gt_classes`` per image.  keys: [N, P + Gmax] 32-bit integers on the device that decide the
+        sample (the candidates with the smallest (key, index) are taken; a candidate is a proposal or, behind them, an appended ground-truth
+        box); drawn from torch's generator when None.  The assignment, the sample and the training list of the call stay in
+        ``last_assignment``.  Works in either mode."""
+        self._refuse_training()
+        xs = self._check(features, train=True)
+        N, dev = xs[0].shape[0], xs[0].device
+        if len(proposals) != N:
+            raise AfiError(f"roi_heads: {len(proposals)} proposal lists for a batch of {N}")
+        boxes, counts = self._padded_proposals(proposals, N, dev)
+        gt, gc, gn = self._targets(targets, N, dev)
+        return self.losses_padded(features, boxes, counts, gt, gc, gn, keys)
+
+    def _forward_train(self, images, features, proposals, targets, keys=None):
+        """(the sampled proposals per image with ``gt_classes`` and ``gt_boxes``, losses), as detectron2's StandardROIHeads.forward in training.
+        One device-to-host read, of the sample's counts."""
+        losses = self.losses(images, features, proposals, targets, keys)
+        a = self.last_assignment
+        out = []
+        for n, (p, c) in enumerate(zip(proposals, a["counts"].tolist())):
+            size = tuple(getattr(p, "image_size", None) or images.image_sizes[n])
+            out.append(_make_sampled(size, a["boxes"][n, :c], a["gt_classes"][n, :c].to(torch.int64), a["gt_boxes"][n, :c]))
+        return out, losses
+
+    def forward(self, images, features, proposals, targets=None, keys=None):
+        """detectron2's StandardROIHeads.forward.  At inference: (one result per image -- image_size, pred_boxes, scores, pred_classes (int64),
+        sorted by score --, {}); one device-to-host read, of counts and truncated.  In training mode with targets: (the sampled proposals with
+        their labels, ``losses()``' dict; keys: as there)."""
+        if targets is not None:
+            if not self.training:
+                raise AfiError("roi_heads: targets given to a module in eval mode -- call .train() for (proposals, losses), or "
+                               "StandardROIHeads.losses() for the losses alone")
+            return self._forward_train(images, features, proposals, targets, keys)
+        xs = self._check(features)
+        sizes = [(int(h), int(w)) for h, w in images.image_sizes]
+        N, dev = xs[0].shape[0], xs[0].device
+        if len(sizes) != N or len(proposals) != N:
+            raise AfiError(f"roi_heads: {len(sizes)} image sizes and {len(proposals)} proposal lists for a batch of {N}")
+        boxes, counts = self._padded_proposals(proposals, N, dev)
         hw = torch.tensor(sizes, dtype=torch.float32).to(dev)
         ob, os_, oc, cn, trunc, *mk = self.forward_padded(hw, features, boxes, counts)
         host = torch.stack([cn, trunc]).tolist()

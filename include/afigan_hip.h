@@ -670,6 +670,43 @@ int afi_roi_nms(const float* boxes, const int* cls, const int* valid, int N, int
 int afi_roi_pick(const float* cand_boxes, const float* cand_scores, const int* cand_cls, const int* keep, const int* n_over, int N, int M, int D,
                  float* out_boxes, float* out_scores, int* out_classes, int* counts, int* truncated, void* stream);
 
+/* ------------------------------------------------------------------ box branch of StandardROIHeads in training (roi_heads.py: StandardROIHeads.losses)
+ * detectron2 v0.1.1's ROIHeads.label_and_sample_proposals, Box2BoxTransform.get_deltas, FastRCNNOutputs.softmax_cross_entropy_loss and
+ * smooth_l1_loss, and the backward of afi_roi_align.  Proposals [N][P][4] with counts_p [N], ground truth gt [N][Gmax][4] (Gmax <= 1024) with
+ * gt_classes [N][Gmax] (int32) and counts_g [N] (device int32, clamped to 0 .. P / Gmax).  The candidates of image n are one padded list of
+ * R = P + Gmax entries: its counts_p[n] proposals, then (append_gt != 0) its counts_g[n] boxes, then padding.  The sample is afi_rpn_sample on
+ * the labels with this R.  No host synchronisation, no float atomics; bit-identical between runs.
+ * afi_roi_label: IoU as afi_rpn_match states it; matched_idx [N][R] = the lowest box index that reaches the candidate's maximum IoU, labels
+ *   [N][R] (int8) = 1 from iou_thresh up, 0 below, -1 for padding; no low-quality matches.  counts_g[n] = 0: label 0 and matched_idx 0 on every
+ *   candidate.
+ * afi_roi_gather_samples: from sampled_idx [N][B], n_pos, n_neg (afi_rpn_sample's, B = batch_per_image): boxes [N][B][4], counts [N] = n_pos +
+ *   n_neg, classes [N][B] (int32: gt_classes[matched_idx] for the first n_pos rows, K for the other sampled rows, -1 past the count), gt_boxes
+ *   [N][B][4] (gt[matched_idx] of every sampled row; zeros when the image has no box and past the count).
+ * afi_roi_box_loss: pred [N B][ld_pred] in afi_roi_scores_boxes' layout (K + 1 logits, background at K, then 4 K or 4 deltas).  Over the rows
+ *   below counts: cross-entropy logsumexp(z) - z[class] in fp64; on rows with class < K smooth L1 (beta; |d| when beta < 1e-5) in fp32 of the
+ *   four deltas of the row's class (columns K + 1 .. K + 4 when agnostic) minus get_deltas(box, gt_box) with weights (wx, wy, ww, wh), the
+ *   target in fp64 rounded once.  Both sums in fp64 in a fixed order; loss[0], loss[1] (device fp32) = the sums / Rtot, Rtot = sum of counts,
+ *   formed on the device (0: both losses and the whole gradient are zero).  dpred [N B][ld_pred] (not pred) is written completely:
+ *   (softmax - onehot) / Rtot in fp64 rounded once, sign(d) or d / beta clamped to +-1 times fp32(1 / Rtot), zero everywhere else.
+ *   ws: afi_roi_box_loss_ws_floats() floats, 8-byte aligned.
+ * afi_roi_align_bwd: dpooled [N B][S][S][C] -> grads = HOST array of L pixel-major views [N][H_l][W_l][C], each written completely (zero where
+ *   no box reaches).  Level, grid, inside test, clamp at 0 and the last-row collapse are afi_roi_align's fp64 expressions; per box and axis the
+ *   1-D weights of a bin's samples on a pixel are summed in fp64 in sample order (W_y also divided by max(grid_h grid_w, 1)) and rounded to fp32
+ *   once, and grad[y][x][c] = sum over (box, ph, pw) in that order of fp32(W_y W_x) * g[ph][pw][c] by fmaf.  One block owns an 8 x 8 tile of a
+ *   level of an image.  ws: afi_roi_align_bwd_ws_floats(N, batch_per_image) floats, 16-byte aligned. */
+int afi_roi_label(const float* proposals, const int* counts_p, int N, int P, const float* gt, const int* counts_g, int Gmax, int append_gt,
+                  float iou_thresh, signed char* labels, int* matched_idx, void* stream);
+int afi_roi_gather_samples(const float* proposals, const int* counts_p, int N, int P, const float* gt, const int* gt_classes, const int* counts_g,
+                           int Gmax, int append_gt, const int* matched_idx, const int* sampled_idx, const int* n_pos, const int* n_neg,
+                           int batch_per_image, int K, float* boxes, int* counts, int* classes, float* gt_boxes, void* stream);
+long long afi_roi_box_loss_ws_floats(void);
+int afi_roi_box_loss(const float* pred, long long ld_pred, int N, int batch_per_image, int K, int agnostic, const float* boxes, const int* counts,
+                     const int* gt_classes, const float* gt_boxes, float wx, float wy, float ww, float wh, float beta, float* loss, float* dpred,
+                     float* ws, long long ws_floats, void* stream);
+long long afi_roi_align_bwd_ws_floats(int N, int batch_per_image);
+int afi_roi_align_bwd(const float* dpooled, const afi_view_t* grads, const int* level_hw, int L, int min_level, int N, int C, const float* boxes,
+                      const int* counts, int batch_per_image, int S, int sampling_ratio, float* ws, long long ws_floats, void* stream);
+
 /* ------------------------------------------------------------------ frozen mask branch of StandardROIHeads (afigan_amd/roi_heads.py)
  * detectron2 v0.1.1's mask_rcnn_inference and paste_masks_in_image.  The mask pooler is afi_roi_align on the padded detections, the head's 3x3
  * convs are the frozen conv dispatch, and the deconv (ConvTranspose2d kernel 2, stride 2) is one afi_conv1x1_fwd over a [4 Cout][Cin] weight
