@@ -13,6 +13,8 @@ the input and output views, the epilogue and the profiler kind it must run on (k
   15       small-map pixel GEMM (< 128 tiles of 128x128): pix_gemm_wk (K split inside the block), or -- where wk_prepare
            refuses the problem (operand byte extents >= 2 GB) -- the stream-K kernel launch_sk with its slab-reduction pass.
            Both record as kind 15; the stream-K cases assert the byte extent that forces the fallback.
+  16 19 20 the grouped weight gradients and the bf16x6 small-map kernel on weight images: only a whole interpolator call reaches them; held by
+           tests/test_gpu_smallmap.py.
 
 The profiler (afi_profile_enable / afi_profile_get) shows every launch of the call: a case passes only if its named kind ran and no
 other pixel-GEMM or weight-gradient kind did, so a change of the dispatch cannot quietly move a case off its kernel.
