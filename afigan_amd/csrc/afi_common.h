@@ -137,6 +137,10 @@ struct AfiWgradGemm {
 #define AFI_WINO4_POINTS 1
 #endif
 struct AfiF16Bound { const float* amax; int stride; int pad_; float cmul[36]; };
+// one f16x3 weight image of a Winograd conv for the grouped builder (csrc/winograd.hip, afi_launch_wino_weight_images): w [O][3][3][I] ->
+// dst = [512-byte header][fp16 pieces of U in the NT GEMM's LDS-image order] (afi_gemm_f16.h).  mode 0: forward (GEMM columns O, K = I);
+// mode 1: data gradient (flipped taps, columns I, K = O).  f4: F(4x4,3x3), 36 planes; else F(2x2,3x3), 16.  Columns % 128 == 0, K % 32 == 0.
+struct AfiWinoImgJob { const float* w; unsigned char* dst; int O, I, f4, mode; };
 
 // one bias-gradient problem of afi_launch_colsum_group: db[c] += alpha * sum_rows g[row*ld + c], c < C
 struct AfiColsumProb { const float* g; float* db; long long P, ld; int C; float alpha; };

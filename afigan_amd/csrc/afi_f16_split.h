@@ -17,6 +17,9 @@ __device__ __forceinline__ float afi_f16_scale(float bound) {
     return __uint_as_float((268u - e) << 23);
 }
 __device__ __forceinline__ float afi_pow2_inverse(float s) { return __uint_as_float((254u << 23) - __float_as_uint(s)); }   // s a normal power of two
+// byte offset of 16-byte chunk ch (k = 8 ch .. 8 ch + 7 of the stage's 32) of row r in one [128 rows x 64 bytes] piece of the NT GEMM's B image
+// (afi_gemm_f16.h; afi_bf16_tile16_off addresses the same image by 8-byte halves of a chunk)
+__device__ __forceinline__ int afi_f16_tile_chunk_off(int row, int ch) { return row * 64 + (((ch ^ (-(row >> 2))) & 3) << 4); }
 
 // a pair of values and their (power-of-two) scale -> packed fp16 pieces of x * s (x0 in the low half).  The residual is formed by one
 // fused multiply-add per element straight from the packed hi (v_fma_mix_f32 reads either half of it as an fp16 source): x * s is exact,

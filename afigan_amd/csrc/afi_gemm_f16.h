@@ -20,7 +20,11 @@
 //     log2(L) binades of the range below the largest element, never precision of the elements that matter: lo stays a normal number for
 //     every element within 2^-18 / L of the bound, and below that the ABSOLUTE error of an element is 2^-25 / s = 2^-40 L of the bound --
 //     fp32's own rounding of the plane's large elements is 2^-24 of them.
-//   * weights (B of the NT GEMM) are split once per weight transform by afi_split_f16_tiles_kernel with the exact per-plane maximum.
+//   * weights (B of the NT GEMM) are split once per weight transform.  The Winograd convs bound every plane of U = G g G^T by
+//     max|w| * cmul[plane] (afi_f16_bound kinds 5 / 6) and, by default, build the image straight from w:
+//     afi_wino_img_max_kernel + afi_wino_img_build_kernel (winograd.hip) transform in registers, split and write header and pieces, many
+//     images per launch; with bit 1 of AFI_OPT_F16_PRESPLIT set, the fp32 weight transform raises the header's maximum slot and afi_split_f16_tiles_kernel
+//     below reads U back.  The stand-alone GEMM entry point (wkind 0) splits with the exact per-plane maxima of the B it is given.
 // The accumulators hold s_a s_b C; the epilogue multiplies by 1 / s_a and 1 / s_b (exact; two steps so that neither factor leaves
 // fp32's range).
 #pragma once

@@ -104,6 +104,8 @@ int afi_launch_wino_dw(const float* dU, float* dW, int O, int I, float alpha, hi
 int afi_launch_wino4_input(AfiView x, int N, int H, int W, int C, long long Tpad, float* V, hipStream_t st, long long ldo = 0, float* amax = nullptr,
                            const AfiF16Bound* pre = nullptr);
 int afi_launch_wino4_weight(const float* w, float* U, int O, int I, int mode, hipStream_t st, float* wmax = nullptr);
+// f16x3 weight images straight from w (no fp32 U), all of `jobs` in three launches: one fill of wmax_slots[0 .. n), max|w| per job, transform + split
+int afi_launch_wino_weight_images(const AfiWinoImgJob* jobs, int n, float* wmax_slots, hipStream_t st);
 int afi_launch_wino4_output_epi(const float* M, long long Tpad, const AfiPixGemm& p, hipStream_t st);
 int afi_launch_wino4_dy(AfiView dy, int N, int H, int W, int C, long long Tpad, float* Q, hipStream_t st, long long ldo = 0, float* amax = nullptr, const AfiF16Bound* pre = nullptr);
 int afi_launch_wino4_dw(const float* dU, float* dW, int O, int I, float alpha, hipStream_t st);

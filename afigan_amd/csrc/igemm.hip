@@ -841,6 +841,8 @@ int afi_launch_absmax_planes(const float* X, long long per_plane, int planes, fl
 // wkind = 0: the exact per-plane maxima of B by a pass of their own (three launches: zero the header, maxima, split; the stand-alone GEMM entry point).
 // wkind = 5 / 6 (F(2x2) / F(4x4) weight planes): the header's slot [64] already holds the largest magnitude of the weight tensor the planes were
 // transformed from -- the caller zero-filled the header (afi_f16_image_begin) and the weight transform raised it -- one launch.
+// wkind 5 / 6 are what bit 1 of AFI_OPT_F16_PRESPLIT selects; by default the Winograd convs never form the fp32 B: afi_launch_wino_weight_images
+// (winograd.hip) writes the same header and the same pieces straight from w, with the same scales afi_f16_scale(max|w| * cmul[plane]).
 long long afi_f16_image_bytes(int planes, int N, int K) { return AFI_F16_HDR_BYTES + (long long)planes * N * K * 4; }
 int afi_f16_image_begin(void* out, hipStream_t st) { return hipMemsetAsync(out, 0, AFI_F16_HDR_BYTES, st) == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH; }
 float* afi_f16_image_wmax(void* out) { return (float*)out + 64; }

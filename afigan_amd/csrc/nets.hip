@@ -289,6 +289,14 @@ static float* wino_wcache_slot(afi_ctx* cx, const float* w, int f4, int mode, in
     c.used += need;
     return slot;
 }
+// the cache entries a call registers for images it builds in ONE launch are committed only once that launch is issued: every exit that
+// builds nothing (no room, too many jobs, a failed launch) rolls the cache back, or a later call would find the entries and multiply by
+// unwritten images
+struct CacheRollback {
+    afi_ctx* cx; int n0; long long used0; bool keep = false;
+    explicit CacheRollback(afi_ctx* c) : cx(c), n0(c ? c->wcache.n : 0), used0(c ? c->wcache.used : 0) {}
+    ~CacheRollback() { if (cx && !keep) { cx->wcache.n = n0; cx->wcache.used = used0; } }
+};
 
 // ---- bf16x6 weight images of the small-map kernels (csrc/smallmap.hip: afi_pix_gemm_wk6).  A whole-net call on a small map lists the
 // weights its pixel GEMMs read (forward: K-contiguous; data gradients: row-contiguous), gets every image from the context's weight cache
@@ -325,13 +333,7 @@ static int wk6_build(afi_ctx* cx, Wk6Images& im, const Wk6Req* reqs, int n, floa
     if (side_done) *side_done = false;
     if (ct_built) *ct_built = false;
     if (n > kWk6MaxReq) return AFI_OK;
-    // the cache entries this call registers are committed only once their images are written: every exit that builds nothing (no room,
-    // too many jobs, a failed launch) rolls the cache back, or a later call would find the entries and multiply by unwritten images
-    struct CacheRollback {
-        afi_ctx* cx; int n0; long long used0; bool keep = false;
-        explicit CacheRollback(afi_ctx* c) : cx(c), n0(c ? c->wcache.n : 0), used0(c ? c->wcache.used : 0) {}
-        ~CacheRollback() { if (cx && !keep) { cx->wcache.n = n0; cx->wcache.used = used0; } }
-    } rollback(cx);
+    CacheRollback rollback(cx);
     AfiWk6ImgJob jobs[kWk6MaxReq];
     AfiWk6ConvT ct;
     bool have_ct = false;
@@ -387,6 +389,42 @@ static long long gen_wk6_bwd_floats(int C, int G, int R, long long P) {
     return f + (long long)R * wk6_req_floats(L, C, 1);
 }
 
+// the f16x3 image of a tile-aligned conv comes straight from w (csrc/winograd.hip, afi_launch_wino_weight_images) unless bit 1 of
+// AFI_OPT_F16_PRESPLIT asks for the fp32 transform + split (the A/B of the two builds: same bytes)
+static inline bool wino_direct_build(const afi_ctx* cx) { return !(afi_opt(cx, AFI_OPT_F16_PRESPLIT) & 2); }
+static inline bool wino_direct_image(const afi_ctx* cx, const WinoForm& f) { return f.dma && f.f16 && wino_direct_build(cx); }
+// A whole-net call walks its Winograd convs at entry, in the order it runs them (add), and builds the images the context's weight cache does
+// not hold yet with ONE call of the grouped builder (build: three launches) on the caller's stream; wino_run then finds hits.  The cache
+// slots are taken as wino_run would take them, in the call's own order, so the cache fills exactly as it does without this; the walk
+// closes at the first conv that is not on the direct path (its request then comes from wino_run, behind these); a conv the cache has no
+// room for is left to wino_run as well.  Every exit without a build rolls the entries back.
+// add: weight w [O][3][3][I] of a conv whose GEMM has K input and Nc output channels (data gradient: K = Cout, Nc = Cin) in the form f.
+struct WinoImgBatch {
+    afi_ctx* cx; CacheRollback rollback; bool open;
+    AfiWinoImgJob jobs[24];
+    int nj = 0;
+    explicit WinoImgBatch(afi_ctx* c) : cx(c), rollback(c), open(c && c->wcache.buf && wino_direct_build(c)) {}
+    void add(const float* w, int K, int Nc, const WinoForm& f) {
+        if (!open) return;
+        if (!wino_direct_image(cx, f) || nj == 24) { open = false; return; }
+        const int b_rc = f.kind == kWinoDgrad;
+        bool hit = false;
+        float* slot = wino_wcache_slot(cx, w, f.f4, b_rc | (f.dtype << 4), b_rc ? K : Nc, b_rc ? Nc : K, wino_usplit_floats(f.np, (long long)K * Nc), hit);
+        if (slot && !hit) jobs[nj++] = AfiWinoImgJob{w, (unsigned char*)slot, b_rc ? K : Nc, b_rc ? Nc : K, f.f4 ? 1 : 0, b_rc};
+    }
+    // a descriptor as GenPix will meet it (wino / n_wino: the pass's Winograd scratch)
+    void add(const AfiPixGemm& g, int b_rc, long long n_wino, bool fwd_f4) {
+        if (!open || g.Bimg || g.no_wcache || n_wino <= 0 || !wino_eligible(cx, g, b_rc)) return;
+        add(g.B, g.Ck * g.nKphase, g.Ncols, wino_form(cx, g, b_rc, fwd_f4));
+    }
+    // wmax_slots: the head of the call's Winograd scratch (the U region, which the direct path leaves unused)
+    int build(float* wmax_slots, hipStream_t st) {
+        if (cx) AFI_TRY(afi_launch_wino_weight_images(jobs, nj, wmax_slots, st));
+        rollback.keep = true;
+        return AFI_OK;
+    }
+};
+
 // a forward or data-gradient descriptor in the form f (wino_form of the same descriptor)
 static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st) {
     AFI_TRY(afi_o16_refused(g));                           // (before any pass: the output transform would refuse it last)
@@ -406,7 +444,11 @@ static int wino_run(afi_ctx* cx, const AfiPixGemm& g, const WinoForm& f, float* 
     } else if (dma) {
         if (float* slot = wino_wcache_slot(cx, g.B, f4, b_rc | (dtype << 4), b_rc ? K : Nc, b_rc ? Nc : K, wino_usplit_floats(np, (long long)K * Nc), have_u)) Usp = slot;
     } else if (float* slot = wino_wcache_slot(cx, g.B, f4, b_rc, b_rc ? K : Nc, b_rc ? Nc : K, align4((long long)np * K * Nc), have_u)) U = slot;
-    if (!have_u) {
+    if (!have_u && wino_direct_image(cx, f)) {
+        // one job of the grouped builder: w straight to the image; its maximum slot is the first float of the U region, which this path leaves unused
+        const AfiWinoImgJob job{g.B, (unsigned char*)Usp, b_rc ? K : Nc, b_rc ? Nc : K, f4 ? 1 : 0, b_rc};
+        AFI_TRY(afi_launch_wino_weight_images(&job, 1, U, st));
+    } else if (!have_u) {
         // (f16x3: the weight transform raises the image header's maximum slot as it reads w, and the split takes every plane's scale from it)
         float* wmax = dma && f16 ? afi_f16_image_wmax(Usp) : nullptr;
         if (wmax) AFI_TRY(afi_f16_image_begin(Usp, st));
@@ -1314,6 +1356,31 @@ static int generator_fwd(afi_ctx_t* cx, const afi_gen_params_t* prm, afi_view_t 
             AFI_TRY(afi_launch_convT_pack(prm->wT, wp, C, C, st));
         }
     }
+    {   // the f16x3 weight images of the pass's Winograd convs that the cache does not hold yet, in one builder call: the convs below, in their
+        // order, by the fields wino_eligible and wino_form read.  The growth convs' packed x-part takes its cache slot (and is packed) here,
+        // where the walk meets it: the block below then finds it
+        WinoImgBatch ib(cx);
+        auto want = [&](AfiPixGemm g, const float* key, int c_lo = 0) { if (key) im.attach(g, key, c_lo); ib.add(g, 0, l.n_wino, p.fwd.f4); };
+        want(conv_fwd_desc(x, N, H, W, C, prm->w0, prm->b0, C, buf(0)), prm->w0);
+        for (int r = 0; r < R && !p.fwd.batched && ib.open; ++r) {
+            if (p.fwd.xbatch) {
+                const float* const wk[4] = {prm->rdb_w[r][0], prm->rdb_w[r][1], prm->rdb_w[r][2], prm->rdb_w[r][3]};
+                bool hit = false;
+                if (float* slot = wino_wcache_slot(cx, prm->rdb_w[r][0], /*tag: growth x-part pack*/ 3, 0, 4 * G, C, l.n_rdbx, hit)) {
+                    if (!hit) AFI_TRY(afi_launch_rdb_xpart_pack(wk, slot, C, G, st));
+                    want(conv_fwd_desc(buf(r), N, H, W, C, slot, nullptr, 4 * G, ch_off(buf(r), C)), nullptr);
+                }
+            } else {
+                for (int k = 1; k <= 4; ++k) want(conv_fwd_desc(buf(r), N, H, W, C + (k - 1) * G, prm->rdb_w[r][k - 1], nullptr, G, buf(r)), nullptr);
+            }
+            want(conv_fwd_desc(buf(r), N, H, W, L, prm->rdb_w[r][4], nullptr, C, buf(r)), prm->rdb_w[r][4]);
+        }
+        // (the column-batched blocks run as grouped launches on the small-map kernels: no Winograd conv among them)
+        want(conv_fwd_desc(t, N, H, W, C, prm->w7, prm->b7, C, a7), prm->w7);
+        want(convT_fwd_desc(a7, N, H, W, C, wp, prm->bT, C, u), prm->wT);
+        want(conv_fwd_desc(u, N, 2 * H, 2 * W, C, prm->w9, prm->b9, C, V(outv)), prm->w9);
+        AFI_TRY(ib.build(ws + l.o_wino, st));
+    }
     {   // head conv + LReLU (generator_rdb.py:91-93) -> channels [0,C) of RDB 0's dense buffer
         AfiPixGemm g = conv_fwd_desc(x, N, H, W, C, prm->w0, prm->b0, C, buf(0));
         g.lrelu = 1;
@@ -1601,6 +1668,32 @@ int afi_generator_bwd(afi_ctx_t* cx, const afi_gen_params_t* prm, const afi_gen_
         skip_grad_done = rode && side.bl_dx;
     }
     if (p.bwd.pack_growth && !filled && hipMemsetAsync(fill, 0, sizeof(float) * (size_t)n_fill, st) != hipSuccess) return AFI_ERR_LAUNCH;
+    {   // the flipped f16x3 weight images of the pass's Winograd data gradients that the cache does not hold yet, in one builder call on the main
+        // stream (the side stream runs weight gradients only: they read no weight image): the data gradients below, in their order, by the
+        // fields wino_eligible and wino_form read.  The growth convs' packed x-part takes its cache slot (and is packed) where the walk meets it
+        WinoImgBatch ib(cx);
+        const int G = prm->G;
+        auto want = [&](AfiPixGemm g, const float* key) { if (key) c.im.attach(g, key); ib.add(g, 1, s.n_wino, false); };
+        want(conv_dgrad_desc(dOut, N, 2 * H, 2 * W, C, prm->w9, C, dU), prm->w9);
+        want(convT_dgrad_desc(dU, N, H, W, C, ws + l.o_wp, C, gA), prm->wT);
+        want(conv_dgrad_desc(gA, N, H, W, C, prm->w7, C, gB), prm->w7);
+        for (int r = R - 1; r >= 0 && ib.open; --r) {
+            want(conv_dgrad_desc(gB, N, H, W, C, prm->rdb_w[r][4], L, c.dbuf(r)), prm->rdb_w[r][4]);
+            if (p.bwd.batch_growth) {
+                // (the chain's partial data gradients read G < 128 channels: never in Winograd form)
+                const float* const wk[4] = {prm->rdb_w[r][0], prm->rdb_w[r][1], prm->rdb_w[r][2], prm->rdb_w[r][3]};
+                bool hit = false;
+                if (float* slot = wino_wcache_slot(cx, prm->rdb_w[r][0], /*tag: growth x-part pack*/ 3, 0, 4 * G, C, s.n_rdbx, hit)) {
+                    if (!hit) AFI_TRY(afi_launch_rdb_xpart_pack(wk, slot, C, G, st));
+                    want(conv_dgrad_desc(c.dbuf(r), N, H, W, 4 * G, slot, C, c.dbuf(r)), nullptr);
+                }
+            } else {
+                for (int k = 4; k >= 1; --k) want(conv_dgrad_desc(c.dbuf(r), N, H, W, G, prm->rdb_w[r][k - 1], C + (k - 1) * G, c.dbuf(r)), prm->rdb_w[r][k - 1]);
+            }
+        }
+        if (dx) want(conv_dgrad_desc(gB, N, H, W, C, prm->w0, C, dense_view(dx, H, W, C)), prm->w0);
+        AFI_TRY(ib.build(scratch + s.o_wino, st));
+    }
 
     // ---- final conv (generator_rdb.py:107-108)
     if (gr->w9) AFI_TRY(c.wgrad(dOut, u, 2 * H, 2 * W, C, C, gr->w9, 1.f));
@@ -1850,6 +1943,11 @@ static int disc_fwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, afi_view_t xv,
     const long long Ph = P / halves;
     float* amax = ws + l.o_amax;                            // (DiscPlan::fwd_amax)
     if (pl.fwd_amax && hipMemsetAsync(amax, 0, 16 * sizeof(float), st) != hipSuccess) return AFI_ERR_LAUNCH;
+    if (wino) {                                             // the three forward weight images the cache does not hold yet, in one builder call
+        WinoImgBatch ib(cx);
+        for (int n = 0; n < 3; ++n) ib.add(prm->w[n], prm->F[n], prm->F[n + 1], pl.b[n].fwd);
+        AFI_TRY(ib.build(ws + l.o_wino, st));
+    }
     bool in_known = false;                                  // block n's input maximum is published before its transform runs
     if (pl.x_amax) {
         AFI_TRY(afi_launch_view_absmax(in, N, H, W, prm->F[0], amax, st));
@@ -1942,6 +2040,11 @@ static int disc_bwd(afi_ctx_t* ctx, const afi_disc_params_t* prm, const afi_disc
     float* red = scratch + s.o_red;
     float* red2 = scratch + s.o_red2;
     float* dd9 = scratch + s.o_dd9;
+    if (pl.wino) {                                          // the flipped weight images of the pass's data gradients, last block first, before the side stream forks
+        WinoImgBatch ib(cx);
+        for (int n = 2; n >= (dx ? 0 : 1); --n) ib.add(prm->w[n], prm->F[n + 1], prm->F[n], wino_form(cx, N, H, W, prm->F[n + 1], prm->F[n], kWinoDgrad));
+        AFI_TRY(ib.build(scratch + s.o_wino, st));
+    }
     // (round 3, re-measured with the DMA GEMM: forking the weight gradients of LARGE maps onto the side stream too: 113.2 vs 112.5 ms per step,
     //  two A/B pairs on one box -- the chip has no room left beside the GEMMs)
     Fork fk(cx, st, P <= kSideStreamMaxPixels);

@@ -15,6 +15,9 @@
 // to 8.3 ms of GEMM instead of 18.6 ms of direct convolution.  fp32 throughout; the transform constants are 0, +-1, +-1/2,
 // so the result differs from the direct kernel by a few ulp of the accumulated sum (tests/test_gpu_wino.py holds every form to 4x
 // the error of a plain fp32 evaluation of the same transforms against fp64: ~5e-7 of the output scale at 128 channels).
+#include <stdint.h>
+#include <string.h>
+
 #include "afi_common.h"
 #include "afi_launch.h"
 #include "afi_epilogue.h"
@@ -74,6 +77,14 @@ static unsigned wino_grid(long long work_items) {
 // mode 0 (forward):   U[a][o][i] from g[ky][kx] = w[o][ky][kx][i]            GEMM columns = O, K = I
 // mode 1 (data grad): U[a][i][o] from g[ky][kx] = w[o][2-ky][2-kx][i]        GEMM columns = I, K = O  (flipped taps, swapped roles)
 // wmax (optional): raised to the largest magnitude of w (the f16x3 arithmetic bounds every plane of U by a constant times it; zero-filled by the caller)
+// G applied to three taps (one definition for this kernel and the image builder below)
+template <typename T>
+__device__ __forceinline__ void wino2_g3(const T g0, const T g1, const T g2, T (&a)[4]) {
+    a[0] = g0;
+    a[1] = 0.5f * (g0 + g1 + g2);
+    a[2] = 0.5f * (g0 - g1 + g2);
+    a[3] = g2;
+}
 __global__ void afi_wino_weight_kernel(const float* __restrict__ w, float* __restrict__ U, int O, int I, int mode, float* wmax) {
     const long long total = (long long)O * I;
     float am = 0.f;
@@ -89,20 +100,19 @@ __global__ void afi_wino_weight_kernel(const float* __restrict__ w, float* __res
         float a[4][3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            a[0][j] = g[0][j];
-            a[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-            a[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
-            a[3][j] = g[2][j];
+            float col[4];
+            wino2_g3(g[0][j], g[1][j], g[2][j], col);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r][j] = col[r];
         }
         const long long plane = (long long)O * I;
         const long long off = mode ? (long long)i * O + o : (long long)o * I + i;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float u0 = a[r][0], u1 = 0.5f * (a[r][0] + a[r][1] + a[r][2]), u2 = 0.5f * (a[r][0] - a[r][1] + a[r][2]), u3 = a[r][2];
-            U[(4 * r + 0) * plane + off] = u0;
-            U[(4 * r + 1) * plane + off] = u1;
-            U[(4 * r + 2) * plane + off] = u2;
-            U[(4 * r + 3) * plane + off] = u3;
+            float u[4];
+            wino2_g3(a[r][0], a[r][1], a[r][2], u);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) U[(4 * r + c) * plane + off] = u[c];
         }
     }
     if (wmax) afi_amax_publish(am, wmax);                    // (uniform)
@@ -668,6 +678,179 @@ __global__ __launch_bounds__(1024) void afi_wino4_weight_kernel(const float* __r
 int afi_launch_wino4_weight(const float* w, float* U, int O, int I, int mode, hipStream_t st, float* wmax) {
     if (O <= 0 || I <= 0) return AFI_ERR_BAD_ARG;
     hipLaunchKernelGGL(afi_wino4_weight_kernel, dim3((I + 31) / 32, (O + 31) / 32), dim3(32, 32), 0, st, w, U, O, I, mode, wmax);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ---------------------------------------------------------------- f16x3 weight images straight from w, many per launch
+// What the two weight kernels above and afi_split_f16_tiles_kernel (afi_gemm_f16.h) make in three launches per image through the fp32 planes U
+// -- header fill, transform, split -- made without U: every plane's scale is afi_f16_scale(max|w| * cmul[plane]), so once max|w| is known
+// (a pass over the raw weights, 1.8x / 4x fewer bytes than U) a block can transform in registers, split and store the pieces.  A job table
+// (AfiWinoImgJob, up to AFI_WINO_IMG_MAXJOBS per launch) maps blockIdx to (job, unit) through prefix sums; the maxima kernel and the build
+// kernel each run over the whole table.  Same device functions, same scale, same split as the three-launch path: the same bytes.
+#define AFI_WINO_IMG_MAXJOBS 64
+#define AFI_WINO_IMG_MAX_FLOATS 8192                        /* raw weights one block of the maxima kernel reads */
+struct AfiWinoImgTable {
+    int njobs, pad_;
+    int unit_start[AFI_WINO_IMG_MAXJOBS + 1];              // prefix sums of the build kernel's units: (columns / 64) x (K / 32) per job
+    int max_start[AFI_WINO_IMG_MAXJOBS + 1];               // prefix sums of the maxima kernel's blocks
+    float cmul2[16], cmul4[36];                            // afi_f16_bound kinds 5 / 6: the planes' bounds relative to max|w|
+    float* wmax;                                           // [njobs], zero-filled before the maxima kernel
+    AfiWinoImgJob j[AFI_WINO_IMG_MAXJOBS];
+};
+__global__ __launch_bounds__(256) void afi_wino_img_max_kernel(const AfiWinoImgTable tb) {
+    const int b = (int)blockIdx.x;
+    int ji = 0;
+    while (ji + 1 < tb.njobs && b >= tb.max_start[ji + 1]) ++ji;          // (uniform)
+    const AfiWinoImgJob& jb = tb.j[ji];
+    const long long n4 = (long long)jb.O * 9 * jb.I / 4;
+    const long long i0 = (long long)(b - tb.max_start[ji]) * (AFI_WINO_IMG_MAX_FLOATS / 4) + threadIdx.x;
+    constexpr int NL = AFI_WINO_IMG_MAX_FLOATS / 1024;
+    float m = 0.f;
+    if (i0 + (NL - 1) * 256 < n4) {                         // (all of the thread's loads in flight together; the tensor's last block takes the guarded loop)
+        f32x4 v[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) v[k] = *(const f32x4*)(jb.w + 4 * (i0 + k * 256));
+#pragma unroll
+        for (int k = 0; k < NL; ++k) m = afi_amax4(m, v[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            const long long i = i0 + k * 256;
+            if (i < n4) m = afi_amax4(m, *(const f32x4*)(jb.w + 4 * i));
+        }
+    }
+    afi_amax_publish(m, tb.wmax + ji);
+}
+// One unit = 64 image rows (GEMM columns n) x one k stage of 32: 16 KB of raw weights in, 4 / 9 x 8 KB of pieces out.  Every thread ends up
+// with 8 consecutive k of one row, i.e. ONE 16-byte chunk of hi and one of lo per plane (16 rows x 64 contiguous bytes per wave and store).
+//   mode 0: row = o, k = i: w's memory order is the image's -- thread (o, 8 i), two float4 per tap, no LDS.
+//   mode 1: row = i, k = o: thread (o, 2 x 4 i) reads w with i fastest (128 contiguous bytes per 8 lanes), one row group of planes
+//           (F(4x4): 6, F(2x2): 4) is transposed through LDS ([plane][32 o][64 i + 1]: conflict-free scalar writes and reads), then as mode 0.
+template <bool F4>
+__device__ __forceinline__ void afi_wino_img_unit(const AfiWinoImgJob& jb, int unit, float wmax, const float* __restrict__ cmul, float* lds) {
+    constexpr int NP1 = F4 ? 6 : 4;
+    constexpr int LD = 65, PL = 32 * LD;
+    const int tid = threadIdx.x, mode = jb.mode;
+    const int I = jb.I, N = mode ? jb.I : jb.O, K = mode ? jb.O : jb.I;
+    const int nkc = K >> 5;
+    const int slab = unit / nkc, kc = unit - slab * nkc;    // 64-row slab of the image's rows, k stage
+    float g[9][8];
+    if (!mode) {
+        const float* src = jb.w + (long long)(slab * 64 + (tid >> 2)) * 9 * I + kc * 32 + 8 * (tid & 3);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const f32x4 v0 = *(const f32x4*)(src + (long long)t * I), v1 = *(const f32x4*)(src + (long long)t * I + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { g[t][e] = v0[e]; g[t][4 + e] = v1[e]; }
+        }
+    } else {
+        const float* src = jb.w + (long long)(kc * 32 + (tid >> 3)) * 9 * I + slab * 64 + 4 * (tid & 7);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {                       // flipped taps
+            const f32x4 v0 = *(const f32x4*)(src + (long long)(8 - t) * I), v1 = *(const f32x4*)(src + (long long)(8 - t) * I + 32);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { g[t][e] = v0[e]; g[t][4 + e] = v1[e]; }
+        }
+    }
+    const int srow = tid >> 2, sch = tid & 3;               // the chunk this thread stores: row 64 slab + srow, k = 8 sch .. + 7 of the stage
+    const int row = (slab & 1) * 64 + srow;
+    unsigned char* img = jb.dst + 512 + (((long long)(slab >> 1)) * nkc + kc) * 16384LL + afi_f16_tile_chunk_off(row, sch);
+    const long long plane_bytes = (long long)(N >> 7) * nkc * 16384LL;
+#pragma unroll
+    for (int r = 0; r < NP1; ++r) {
+        float u[NP1][8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float a[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                float col[NP1];
+                if constexpr (F4) wino4_g3(g[j][e], g[3 + j][e], g[6 + j][e], col); else wino2_g3(g[j][e], g[3 + j][e], g[6 + j][e], col);
+                a[j] = col[r];
+            }
+            float uu[NP1];
+            if constexpr (F4) wino4_g3(a[0], a[1], a[2], uu); else wino2_g3(a[0], a[1], a[2], uu);
+#pragma unroll
+            for (int c = 0; c < NP1; ++c) u[c][e] = uu[c];
+        }
+        if (mode) {                                         // (uniform: one job per block)
+            __syncthreads();                                // the reads of the previous row group are done
+            float* wr = lds + (tid >> 3) * LD + 4 * (tid & 7);
+#pragma unroll
+            for (int c = 0; c < NP1; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { wr[c * PL + e] = u[c][e]; wr[c * PL + 32 + e] = u[c][4 + e]; }
+            __syncthreads();
+            const float* rd = lds + (8 * sch) * LD + srow;
+#pragma unroll
+            for (int c = 0; c < NP1; ++c)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) u[c][e] = rd[c * PL + e * LD];
+        }
+#pragma unroll
+        for (int c = 0; c < NP1; ++c) {
+            const int plane = NP1 * r + c;
+            const float s = afi_f16_scale(wmax * cmul[plane]);
+            unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+            afi_split2_f16_pair(u[c][0], u[c][1], s, h0, l0);
+            afi_split2_f16_pair(u[c][2], u[c][3], s, h1, l1);
+            afi_split2_f16_pair(u[c][4], u[c][5], s, h2, l2);
+            afi_split2_f16_pair(u[c][6], u[c][7], s, h3, l3);
+            unsigned char* d = img + plane * plane_bytes;
+            *(u32x4*)d = u32x4{h0, h1, h2, h3};
+            *(u32x4*)(d + 8192) = u32x4{l0, l1, l2, l3};
+        }
+    }
+}
+__global__ __launch_bounds__(256) void afi_wino_img_build_kernel(const AfiWinoImgTable tb) {
+    __shared__ float lds[6 * 32 * 65];
+    const int b = (int)blockIdx.x;
+    int ji = 0;
+    while (ji + 1 < tb.njobs && b >= tb.unit_start[ji + 1]) ++ji;         // (uniform)
+    const AfiWinoImgJob& jb = tb.j[ji];
+    const int unit = b - tb.unit_start[ji];
+    const float wmax = tb.wmax[ji];
+    const float* cmul = jb.f4 ? tb.cmul4 : tb.cmul2;
+    if (unit == 0 && threadIdx.x < 128) {                   // the whole header: the plane scales, the maximum they were made from in [64], zeros elsewhere
+        const int t = threadIdx.x, np = jb.f4 ? 36 : 16;
+        ((float*)jb.dst)[t] = t < np ? afi_f16_scale(wmax * cmul[t]) : (t == 64 ? wmax : 0.f);
+    }
+    if (jb.f4) afi_wino_img_unit<true>(jb, unit, wmax, cmul, lds);
+    else afi_wino_img_unit<false>(jb, unit, wmax, cmul, lds);
+}
+// wmax_slots: the caller's scratch for n floats, rounded up to a multiple of AFI_WINO_IMG_MAXJOBS (anything the stream has finished with);
+// three launches per AFI_WINO_IMG_MAXJOBS images
+int afi_launch_wino_weight_images(const AfiWinoImgJob* jobs, int n, float* wmax_slots, hipStream_t st) {
+    if (n <= 0) return AFI_OK;
+    if (!jobs || !wmax_slots) return AFI_ERR_BAD_ARG;
+    // (whole 256-byte groups of slots, the size of the transforms' own maxima pool: the U region has the room)
+    const size_t nfill = ((size_t)n + AFI_WINO_IMG_MAXJOBS - 1) / AFI_WINO_IMG_MAXJOBS * AFI_WINO_IMG_MAXJOBS;
+    if (hipMemsetAsync(wmax_slots, 0, sizeof(float) * nfill, st) != hipSuccess) return AFI_ERR_LAUNCH;
+    const AfiF16Bound b2 = afi_f16_bound(nullptr, 5), b4 = afi_f16_bound(nullptr, 6);
+    for (int done = 0; done < n; done += AFI_WINO_IMG_MAXJOBS) {
+        const int cnt = n - done < AFI_WINO_IMG_MAXJOBS ? n - done : AFI_WINO_IMG_MAXJOBS;
+        AfiWinoImgTable tb;
+        tb.njobs = cnt; tb.pad_ = 0;
+        tb.wmax = wmax_slots + done;
+        memcpy(tb.cmul2, b2.cmul, sizeof(tb.cmul2));
+        memcpy(tb.cmul4, b4.cmul, sizeof(tb.cmul4));
+        long long units = 0, mblocks = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const AfiWinoImgJob& j = jobs[done + i];
+            if (!j.w || !j.dst || j.O <= 0 || j.I <= 0 || (j.mode != 0 && j.mode != 1)) return AFI_ERR_BAD_ARG;
+            const int N = j.mode ? j.I : j.O, K = j.mode ? j.O : j.I;
+            if ((N % 128) || (K % 32) || (j.I & 3) || (((uintptr_t)j.w | (uintptr_t)j.dst) & 15)) return AFI_ERR_UNSUPPORTED;   // whole units, float4 reads, 16-byte stores
+            tb.j[i] = j;
+            tb.unit_start[i] = (int)units; tb.max_start[i] = (int)mblocks;
+            units += (long long)(N / 64) * (K / 32);
+            mblocks += ((long long)j.O * 9 * j.I + AFI_WINO_IMG_MAX_FLOATS - 1) / AFI_WINO_IMG_MAX_FLOATS;
+            if (units > 0x3fffffffLL || mblocks > 0x3fffffffLL) return AFI_ERR_UNSUPPORTED;
+        }
+        for (int i = cnt; i <= AFI_WINO_IMG_MAXJOBS; ++i) { tb.unit_start[i] = (int)units; tb.max_start[i] = (int)mblocks; }
+        for (int i = cnt; i < AFI_WINO_IMG_MAXJOBS; ++i) tb.j[i] = AfiWinoImgJob{nullptr, nullptr, 0, 0, 0, 0};
+        hipLaunchKernelGGL(afi_wino_img_max_kernel, dim3((unsigned)mblocks), dim3(256), 0, st, tb);
+        hipLaunchKernelGGL(afi_wino_img_build_kernel, dim3((unsigned)units), dim3(256), 0, st, tb);
+    }
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 

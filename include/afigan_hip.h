@@ -156,7 +156,14 @@ int afi_ctx_get_compute_dtype(const afi_ctx_t* ctx);
 #define AFI_OPT_F16_PRESPLIT 11               /* 1 (default): under AFI_DTYPE_F16X3, a Winograd transform whose source tensor's largest magnitude is known before it
                                                * runs (the discriminator's activations and gradients: published by the BatchNorm passes that write them) writes
                                                * its planes already split into the two fp16 pieces and the GEMM stages them by DMA alone.  0: every plane is
-                                               * written in fp32 and split when the GEMM reads its fragments (same results; stage-1 step 86.6 against 84.4 ms) */
+                                               * written in fp32 and split when the GEMM reads its fragments (same results; stage-1 step 86.6 against 84.4 ms).
+                                               * Bit 1 (value 3: planes pre-split as under 1) is the A/B switch of the WEIGHT images: clear (the default), the pre-split
+                                               * weight image of a tile-aligned Winograd conv (forward or data gradient) is built straight from w by the grouped builder
+                                               * of csrc/winograd.hip -- one fill of the maxima slots, one pass over the raw weights for max|w|, one pass that
+                                               * transforms in registers and writes the fp16 pieces and the image header: three launches for ALL the images a
+                                               * whole-net call misses (the discriminator's and the interpolator's passes list theirs at entry; a single conv is a
+                                               * table of one), and the fp32 planes U are neither written nor read; set, every image takes a header fill, the fp32
+                                               * weight transform and the split that reads it back.  Same bytes either way (tests/test_gpu_weight_images.py) */
 #define AFI_OPT_F16_NT256_MIN_TILES 12        /* 512: the f16x3 NT GEMM takes its 256 x 256 tile (sixteen waves per block, half the operand bytes per product)
                                                * from this many tiles on (and 256-column multiples); 0: never (the 128 x 128 tile everywhere) */
 #define AFI_OPT_F16_LOCAL_SUMS 13             /* under AFI_DTYPE_F16X3, which of the discriminator's forward convs that a backward follows (training == 1: their rounding
