@@ -1356,6 +1356,109 @@ def roi_mask_probs(h, w, bias, classes, counts, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ ROI heads, mask branch in training (roi_heads.py)
+def mask_polygons(instances, N, Gmax, device):
+    """The polygons of a training call as afi_mask_targets reads them: ``instances[n]`` = image n's list of instances, each a list of flat
+    coordinate sequences; one annotation per (image, ground-truth slot), the slots past an image's instances empty.  Checked on the host
+    (polygons_batch), uploaded once: (xy float64 [V, 2], vert_off int64 [P + 1], poly_off int64 [N Gmax + 1]) on the device."""
+    anns = []
+    for n in range(N):
+        inst = list(instances[n])
+        if len(inst) > Gmax:
+            raise _lib.AfiError(f"mask_polygons: image {n} has {len(inst)} instances for {Gmax} ground-truth slots")
+        anns.extend(inst + [[]] * (Gmax - len(inst)))
+    xy, vert_off, poly_off, _, _ = polygons_batch(anns, (1, 1))
+    up = lambda a: torch.from_numpy(a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)).to(device)      # noqa: E731  (no null pointer)
+    return up(xy), torch.from_numpy(vert_off).to(device), torch.from_numpy(poly_off).to(device)
+
+
+def mask_targets(xy, vert_off, poly_off, boxes, sampled_idx, matched_idx, counts_g, Gmax, n_pos, Bf, M, out=None):
+    """detectron2's mask targets of the foreground prefix of a training list (PolygonMasks.crop_and_resize restated): xy / vert_off / poly_off
+    = mask_polygons' tensors, boxes [N, B, 4] / sampled_idx [N, B] / matched_idx [N, P + Gmax] / n_pos [N] = the box branch's training list
+    (roi_gather_samples' inputs and output), counts_g [N].  Returns (targets uint8 [N, Bf, M, M], every byte written, rows past the count
+    zero; counts_fg [N] int32 = n_pos clamped to 0..Bf) (afi_mask_targets)."""
+    N, B = boxes.shape[:2] if boxes.dim() == 3 else (0, 0)
+    Bf, M, Gmax = int(Bf), int(M), int(Gmax)
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or not boxes.is_contiguous() or tuple(sampled_idx.shape) != (N, B) or matched_idx.dim() != 2 \
+            or matched_idx.shape[0] != N or tuple(counts_g.shape) != (N,) or tuple(n_pos.shape) != (N,) \
+            or not all(t.is_contiguous() for t in (sampled_idx, matched_idx, counts_g, n_pos)):
+        raise _lib.AfiError(f"mask_targets: dense boxes [N, B, 4], sampled_idx [N, B], matched_idx [N, R], counts_g [N] and n_pos [N] expected, got "
+                            f"{tuple(boxes.shape)}, {tuple(sampled_idx.shape)}, {tuple(matched_idx.shape)}, {tuple(counts_g.shape)}, {tuple(n_pos.shape)}")
+    if not 0 < Bf <= B or not 0 < B <= RPN_MAX_BATCH or not 0 < M <= 2 * ROI_MAX_POOLED or Gmax < 1:
+        raise _lib.AfiError(f"mask_targets: Bf {Bf} (1..B = {B} <= {RPN_MAX_BATCH}), M {M} (1..{2 * ROI_MAX_POOLED}) and Gmax {Gmax} (>= 1) expected")
+    _check_cuda(boxes)
+    _check_i32(sampled_idx, matched_idx, counts_g, n_pos)
+    for name, t, dt in (("xy", xy, torch.float64), ("vert_off", vert_off, torch.int64), ("poly_off", poly_off, torch.int64)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise _lib.AfiError(f"mask_targets: {name} must be a dense {dt} tensor on the GPU (ops.mask_polygons)")
+    if poly_off.numel() != N * Gmax + 1 or vert_off.numel() < 1 or xy.dim() != 2 or xy.shape[1] != 2:
+        raise _lib.AfiError(f"mask_targets: poly_off must hold {N} x {Gmax} + 1 offsets (one annotation per image and ground-truth slot), "
+                            f"got {poly_off.numel()}; xy [V, 2], got {tuple(xy.shape)}")
+    if out is None:
+        out = torch.empty((N, Bf, M, M), device=boxes.device, dtype=torch.uint8)
+    elif tuple(out.shape) != (N, Bf, M, M) or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
+        raise _lib.AfiError(f"mask_targets: out must be a dense uint8 [{N}, {Bf}, {M}, {M}] tensor on the GPU")
+    counts_fg = torch.empty((N,), device=boxes.device, dtype=torch.int32)
+    call("afi_mask_targets", _p(xy), _p(vert_off), _p(poly_off), vert_off.numel() - 1, xy.shape[0], _p(boxes), _p(sampled_idx), N, B,
+         _p(matched_idx), matched_idx.shape[1], _p(counts_g), Gmax, _p(n_pos), Bf, M, _p(out), _p(counts_fg), stream_ptr())
+    return out, counts_fg
+
+
+def _mask_loss_rows(name, h, w, classes, counts_fg):
+    """The shapes shared by mask_loss and mask_pred_bwd: returns (N, D, C, S, Km, w as [Km, C])."""
+    _check_i32(classes, counts_fg)
+    if classes.dim() != 2 or counts_fg.dim() != 1 or counts_fg.shape[0] != classes.shape[0] or classes.stride(1) != 1 or not counts_fg.is_contiguous():
+        raise _lib.AfiError(f"{name}: classes [N, D] with dense rows and counts_fg [N] expected, got {tuple(classes.shape)} and {tuple(counts_fg.shape)}")
+    N, D = classes.shape
+    Km = w.shape[0]
+    w2 = w.reshape(Km, -1).contiguous()
+    C_ = w2.shape[1]
+    if h.dim() != 4 or h.shape[0] != N * D or h.shape[1] != 4 * C_ or h.shape[2] != h.shape[3] or not is_dense_pm(h) or C_ % 4 \
+            or not 0 < h.shape[2] <= ROI_MAX_POOLED:
+        raise _lib.AfiError(f"{name}: a dense pixel-major h [{N * D}, 4 C, S, S] with C = {C_} (a multiple of 4) and S in 1..{ROI_MAX_POOLED} "
+                            f"expected, got {tuple(h.shape)}")
+    return N, D, C_, h.shape[2], Km, w2
+
+
+def mask_loss(h, w, bias, classes, counts_fg, targets):
+    """mask_rcnn_loss on the deconv's 4-phase output: h as in roi_mask_probs with D = Bf rows per image, classes [N, Bf] int32 (a view of the
+    training list's [N, B] classes will do), counts_fg [N], targets uint8 [N, Bf, 2S, 2S].  Returns (loss [1] fp32 on the device = the mean
+    binary cross-entropy with logits over the counts_fg rows' selected-class pixels, dz [N Bf, S, S, 4] = d loss / d logit in h's pixel order,
+    zero on the other rows) (afi_mask_loss)."""
+    _check_cuda(h, w, bias)
+    N, D, C_, S, Km, w2 = _mask_loss_rows("mask_loss", h, w, classes, counts_fg)
+    if tuple(bias.shape) != (Km,) or not bias.is_contiguous() or tuple(targets.shape) != (N, D, 2 * S, 2 * S) or targets.dtype != torch.uint8 \
+            or not targets.is_contiguous() or not targets.is_cuda:
+        raise _lib.AfiError(f"mask_loss: a bias [{Km}] and dense uint8 targets [{N}, {D}, {2 * S}, {2 * S}] on the GPU expected, got "
+                            f"{tuple(bias.shape)} and {targets.dtype} {tuple(targets.shape)}")
+    loss = torch.empty((1,), device=h.device, dtype=torch.float32)
+    dz = new_workspace(N * D * 4 * S * S, h.device).view(N * D, S, S, 4)
+    nws = int(_lib.load().afi_mask_loss_ws_floats(N, D, C_, S))
+    ws = new_workspace(max(nws, 2), h.device)
+    call("afi_mask_loss", _p(h), _p(w2), _p(bias), _p(classes), classes.stride(0), _p(counts_fg), _p(targets), N, D, C_, S, Km, _p(loss), _p(dz),
+         _p(ws), nws, stream_ptr())
+    return loss, dz
+
+
+def mask_pred_bwd(h, dz, w, classes, counts_fg):
+    """The backward of the class-selected mask predictor: h, w, classes, counts_fg as in mask_loss, dz [N Bf, S, S, 4] (mask_loss', possibly
+    scaled).  Returns (dh like h = dz w[class] (h > 0), zero on rows past the count; dW [Km, C]; db [Km]) (afi_mask_pred_bwd)."""
+    _check_cuda(h, w, dz)
+    N, D, C_, S, Km, w2 = _mask_loss_rows("mask_pred_bwd", h, w, classes, counts_fg)
+    if tuple(dz.shape) != (N * D, S, S, 4) or not dz.is_contiguous():
+        raise _lib.AfiError(f"mask_pred_bwd: a dense dz [{N * D}, {S}, {S}, 4] expected, got {tuple(dz.shape)}")
+    nws = int(_lib.load().afi_mask_pred_bwd_ws_floats(N, D, C_))
+    if nws < 0 or N * D > 65535:
+        raise _lib.AfiError(f"mask_pred_bwd: unsupported shape (C {C_} <= 1024 and N Bf {N * D} <= 65535 expected)")
+    dh = new_pixel_major(N * D, 4 * C_, S, S, h.device)
+    dW = torch.empty((Km, C_), device=h.device, dtype=torch.float32)
+    db = torch.empty((Km,), device=h.device, dtype=torch.float32)
+    ws = new_workspace(nws, h.device)
+    call("afi_mask_pred_bwd", _p(h), _p(dz), _p(w2), _p(classes), classes.stride(0), _p(counts_fg), N, D, C_, S, Km, _p(dh), _p(dW), _p(db),
+         _p(ws), nws, stream_ptr())
+    return dh, dW, db
+
+
 def mask_paste(probs, boxes, hw, threshold=0.5, out=None):
     """detectron2's paste_masks_in_image: probs [R, M, M] pasted into boxes [R, 4] (x0, y0, x1, y1) of an image of hw = (H, W), compared with
     ``>= threshold``: bool [R, H, W].  Pixels whose centre is outside their box are False; a box with a non-positive side gives all False

@@ -25,7 +25,14 @@ Training, box branch (``StandardROIHeads.losses``, and ``forward`` in training m
 get_deltas, softmax_cross_entropy_loss and smooth_l1_loss on afi_roi_label / afi_rpn_sample / afi_roi_gather_samples / afi_roi_box_loss
 (csrc/roi_loss.hip), the pooler and head forward on the kernels above, their backward on afi_conv1x1_dgrad / afi_conv1x1_wgrad / afi_relu_bwd
 and afi_roi_align_bwd (``_ROIBoxLossFn``).  The sample is decided by 32-bit keys, as in ``RPN.losses``.  One IOU_THRESHOLDS entry with
-IOU_LABELS [0, 1]; the mask loss, cascade training, crowd handling and TRAIN_ON_PRED_BOXES are out of scope (AfiError).
+IOU_LABELS [0, 1]; cascade training, crowd handling and TRAIN_ON_PRED_BOXES are out of scope (AfiError).
+
+Training, mask branch (heads built with ``masks=True``: ``losses`` returns ``loss_mask`` as well): detectron2's mask_rcnn_loss on the first
+Bf = int(BATCH_SIZE_PER_IMAGE POSITIVE_FRACTION) rows of the box branch's training list, whose n_pos positives come first -- one label /
+sample / gather for both branches.  The targets are the matched instance's polygons (``gt_masks``) rasterised inside the row's box on the
+2S x 2S canvas (afi_mask_targets: PolygonMasks.crop_and_resize restated), the loss is the mean binary cross-entropy with logits of the row's
+own class (afi_mask_loss), the predictor's backward is afi_mask_pred_bwd, and the rest of the chain runs on the conv entry points and
+afi_roi_align_bwd (``_ROIMaskLossFn``; csrc/mask_loss.hip).  ``trainable_(mask_head=True)`` makes the mask head's parameters trainable.  Bitmask targets and a mask loss weight (v0.1.1 has none) are out of scope.
 
 Kernels: afi_roi_align; the FCs and the predictor are afi_conv1x1_fwd over the R = N P rows as pixels (fc1 reads the pooled [R][S][S][C]
 memory in place, its weight permuted once from [out][C][S][S] to [out][S][S][C]; cls_score and bbox_pred are ONE weight, zero-padded to a
@@ -67,7 +74,7 @@ from . import _lib, ops, rle
 from ._lib import AfiError
 from .frozen import FROZEN_BN_EPS, FrozenBatchNorm2d, cfg_get, check_feature, conv3x3, fold_conv, prepared
 from .registry import detectron2_or_local
-from .rpn import SCALE_CLAMP, Boxes, Proposals
+from .rpn import SCALE_CLAMP, Boxes, Proposals, _wino
 
 ROI_MAX_CANDIDATES = ops.ROI_MAX_CANDIDATES
 
@@ -443,6 +450,71 @@ class _ROIBoxLossFn(torch.autograd.Function):
         return (*[None] * na, *dxs, *[v if n else None for v, n in zip(h, need[na + L:])])
 
 
+class _ROIMaskLossFn(torch.autograd.Function):
+    """loss_mask of the features and the mask head's parameters, on the foreground prefix of the training list ``_ROIBoxLossFn`` left in
+    ``heads.last_assignment`` (one label / sample / gather for both branches).  Forward: afi_mask_targets, then the mask pooler, the 3x3 convs
+    and the deconv as one 1x1 conv -- the very chain inference runs --, then afi_mask_loss, which also leaves d loss / d logit.  Backward: the
+    upstream scalar as one multiply of that gradient; afi_mask_pred_bwd (dh already carries the deconv's ReLU mask); the deconv on
+    afi_conv1x1_wgrad / afi_conv1x1_dgrad over the prepared [4 Cout][Cin] weight (its gradient permuted back to [Cin][Cout][2][2], its bias
+    gradient summed over the four phases); afi_relu_bwd and the 3x3 wgrad / dgrad of every ``mask_fcn`` in the regime its forward ran in;
+    then afi_roi_align_bwd at the mask pooler's resolution.  Targets and boxes are not differentiable."""
+    NARGS = 5                              # the non-differentiable leading arguments of forward
+
+    @staticmethod
+    @_lib.ctx_forward
+    def forward(ctx, heads, polys, gcounts, gmax, nlev, *ts):
+        xs = [ops.pixel_major(x.detach()) for x in ts[:nlev]]
+        a, pool, Bf = heads.last_assignment, heads.mask_pooler, heads.mask_batch_per_image
+        tg, cfg_ = ops.mask_targets(*polys, a["boxes"], a["sampled_idx"], a["matched_idx"], gcounts, gmax, a["n_pos"], Bf, 2 * pool.output_size)
+        boxes = a["boxes"][:, :Bf].contiguous()         # the pooler reads a dense list: N Bf 16 bytes, on the device
+        cls = a["gt_classes"][:, :Bf]                   # read in place, with the list's row stride
+        pooled = pool(xs, boxes, cfg_)
+        convs, (wd, bd), (wp, bp) = heads._prepare_mask()
+        x, acts = pooled, []
+        for wb in convs:
+            x = conv3x3(x, wb, relu=True)
+            acts.append(x)
+        h = ops.conv1x1_fwd(x, wd, bd, act=2)
+        loss, dz = ops.mask_loss(h, wp, bp, cls, cfg_, tg)
+        ctx.save_for_backward(wd, wp, *[wb[0] for wb in convs], pooled, *acts, h, dz, boxes, cfg_, cls)
+        ctx.nlev, ctx.nconv = nlev, len(convs)
+        ctx.level_shapes, ctx.min_level, ctx.sampling_ratio = [tuple(x.shape[2:]) for x in xs], pool.min_level, pool.sampling_ratio
+        a.update(mask_targets=tg, counts_fg=cfg_, mask_boxes=boxes, mask_deconv=h, mask_dz=dz)
+        return loss[0]
+
+    @staticmethod
+    @_lib.ctx_backward
+    def backward(ctx, dloss):
+        sv, L, F = ctx.saved_tensors, ctx.nlev, ctx.nconv
+        wd, wp, cw = sv[0], sv[1], sv[2:2 + F]
+        pooled, acts = sv[2 + F], sv[3 + F:3 + 2 * F]
+        h, dz, boxes, cfg_, cls = sv[3 + 2 * F:]
+        na = _ROIMaskLossFn.NARGS
+        need = ctx.needs_input_grad
+        need_x, need_w = any(need[na:na + L]), any(need[na + L:])
+        ins = [pooled] + list(acts)                                          # ins[k]: the input of mask_fcn k + 1; ins[F]: the deconv's
+        dh, dwp, dbp = ops.mask_pred_bwd(h, dz * dloss.float(), wp, cls, cfg_)
+        cgrads, dgrads = [], []
+        if need_w:
+            cout, cin = wd.shape[0] // 4, wd.shape[1]
+            dwd = ops.conv1x1_wgrad(dh, ins[F]).view(2, 2, cout, cin).permute(3, 2, 0, 1)       # row (2a + b) Cout + co, column ci
+            dgrads = [dwd, ops.bias_grad(dh).view(4, cout).sum(0)]
+        dx = ops.conv1x1_dgrad(dh, wd) if F > 0 or need_x else None
+        for k in reversed(range(F)):
+            du = ops.relu_bwd(dx, ins[k + 1])
+            wino = _wino(ins[k], du.shape[1])
+            if need_w:
+                cgrads = [(ops.conv3x3_wino_wgrad if wino else ops.conv3x3_wgrad)(du, ins[k]), ops.bias_grad(du)] + cgrads
+            if k > 0 or need_x:
+                dx = (ops.conv3x3_wino_dgrad if wino else ops.conv3x3_dgrad)(du, cw[k])
+        dxs = [None] * L
+        if need_x:
+            dxs = ops.roi_align_bwd(dx, ctx.level_shapes, ctx.min_level, boxes, cfg_, ctx.sampling_ratio)
+            dxs = [d if n else None for d, n in zip(dxs, need[na:na + L])]
+        g = cgrads + dgrads + [dwp.view(dwp.shape[0], -1, 1, 1), dbp] if need_w else [None] * (2 * F + 4)
+        return (*[None] * na, *dxs, *[v if n else None for v, n in zip(g, need[na + L:])])
+
+
 def _make_sampled(image_size, boxes, gt_classes, gt_boxes):
     """One image's sampled proposals in training: ``proposal_boxes``, ``gt_classes`` (int64, NUM_CLASSES = background) and ``gt_boxes``."""
     try:
@@ -543,10 +615,14 @@ class StandardROIHeads(nn.Module):
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA {self.smooth_l1_beta} must not be negative")
         self.last_assignment = None
 
-    def trainable_(self, flag=True):
-        """Turn the parameters of the box head and the box predictor into trainable ones (or back).  The prepared weights follow the
-        parameters' versions (frozen.prepared), so an optimizer step is seen by the next call."""
-        for mod in (self.box_head, self.box_predictor):
+    def trainable_(self, flag=True, mask_head=False):
+        """Turn the parameters of the box head and the box predictor into trainable ones (or back); with mask_head=True those of the mask
+        head as well (heads built with masks=True; without the keyword the mask head is left as it is, frozen at construction, as before
+        the mask loss existed).  The prepared weights follow the parameters' versions (frozen.prepared), so an optimizer step is seen by
+        the next call."""
+        if mask_head and not self.mask_on:
+            raise AfiError("roi_heads: trainable_(mask_head=True) on heads built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
+        for mod in (self.box_head, self.box_predictor) + ((self.mask_head,) if mask_head else ()):
             for p in mod.parameters():
                 p.requires_grad_(bool(flag))
         return self
@@ -779,40 +855,86 @@ class StandardROIHeads(nn.Module):
                 gc[n, :b.shape[0]] = c.detach().to(device=device, dtype=torch.int32)
         return gt, gc, torch.tensor([b.shape[0] for b in boxes], dtype=torch.int32).to(device)
 
+    @property
+    def mask_batch_per_image(self):
+        """Bf: the rows per image the mask branch trains on, the most positives the sampler takes."""
+        return int(self.batch_size_per_image * self.positive_fraction)
+
+    @staticmethod
+    def _target_polygons(targets):
+        """Every image's instances as lists of flat coordinate sequences, from the targets' ``gt_masks``: an object with ``.polygons`` (what the
+        dual-scale mapper yields) or a list with one list of polygons per instance.  Host data; nothing touches the device."""
+        out = []
+        for n, t in enumerate(targets):
+            m = t.get("gt_masks") if isinstance(t, dict) else getattr(t, "gt_masks", None)
+            if m is None:
+                raise AfiError(f"roi_heads: target {n} has no `gt_masks`: these heads were built with masks=True and train the mask branch "
+                               "on every instance's polygons; for targets with boxes only the mask loss is not built yet: give every target "
+                               "its `gt_masks`, or train heads built without the mask branch (box losses only)")
+            if torch.is_tensor(m) or torch.is_tensor(getattr(m, "tensor", None)):
+                raise AfiError(f"roi_heads: target {n}'s `gt_masks` is a bitmask ({type(m).__name__}); polygon masks only (an object with "
+                               "`.polygons`, or one list of flat coordinate arrays per instance): bitmask targets are out of scope")
+            polys = getattr(m, "polygons", m)
+            if not isinstance(polys, (list, tuple)) or any(not isinstance(p, (list, tuple)) for p in polys):
+                raise AfiError(f"roi_heads: target {n}'s `gt_masks` must be an object with `.polygons` or a list with one list of flat "
+                               f"coordinate arrays per instance, got {type(m).__name__}")
+            b = _target_field(t, "gt_boxes")
+            if torch.is_tensor(b) and len(polys) != b.shape[0]:             # (a target without gt_boxes is _targets' to refuse)
+                raise AfiError(f"roi_heads: target {n}'s `gt_masks` has {len(polys)} instances and `gt_boxes` {b.shape[0]}")
+            out.append([[p.detach().cpu().numpy() if torch.is_tensor(p) else p for p in inst] for inst in polys])
+        return out
+
     def _refuse_training(self):
         if isinstance(self.box_head, nn.ModuleList):
             raise AfiError("roi_heads: CascadeROIHeads is inference-only (frozen): cascade training is out of scope")
-        if self.mask_on:
-            raise AfiError("roi_heads: these heads were built with masks=True and the mask loss is not built yet: train heads built without "
-                           "the mask branch (box losses only)")
 
-    def losses_padded(self, features, boxes, counts, gt, gt_classes, gt_counts, keys=None):
+    def losses_padded(self, features, boxes, counts, gt, gt_classes, gt_counts, keys=None, gt_polygons=None):
         """``losses`` on padded device tensors: proposals boxes [N, P, 4] / counts [N] (``RPN.forward_padded``'s layout), ground truth gt
-        [N, Gmax, 4] fp32, gt_classes [N, Gmax] int32, gt_counts [N] int32.  No host read."""
+        [N, Gmax, 4] fp32, gt_classes [N, Gmax] int32, gt_counts [N] int32.  Heads built with masks=True also take gt_polygons = the packed
+        polygons of the call on the device (``ops.mask_polygons``: xy, vert_off, poly_off, one annotation per (image, ground-truth slot)) and
+        return ``loss_mask`` as well.  No host read."""
         self._refuse_training()
         xs = self._check(features, boxes, counts, train=True)
         _check_feature("roi_heads", "gt boxes", gt)
+        if self.mask_on:
+            if gt_polygons is None or len(gt_polygons) != 3:
+                raise AfiError("roi_heads: heads built with masks=True train the mask branch: losses_padded needs gt_polygons = (xy, vert_off, "
+                               "poly_off) on the device (ops.mask_polygons)")
+            if self.mask_batch_per_image < 1:
+                raise AfiError(f"roi_heads: MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE {self.batch_size_per_image} x POSITIVE_FRACTION "
+                               f"{self.positive_fraction} leaves the mask branch no foreground row")
+        elif gt_polygons is not None:
+            raise AfiError("roi_heads: gt_polygons given to heads built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
         h, pr = self.box_head, self.box_predictor
         params = [t for fc in h.fcs for t in (fc.weight, fc.bias)] + [pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias]
         out = _ROIBoxLossFn.apply(self, boxes.detach().contiguous(), counts.contiguous(), gt.contiguous(), gt_classes.contiguous(),
                                   gt_counts.contiguous(), keys, len(xs), *xs, *params)
-        return {"loss_cls": out[0], "loss_box_reg": out[1]}
+        losses = {"loss_cls": out[0], "loss_box_reg": out[1]}
+        if self.mask_on:
+            mh = self.mask_head
+            mparams = [t for l in mh.conv_norm_relus + [mh.deconv, mh.predictor] for t in (l.weight, l.bias)]
+            losses["loss_mask"] = _ROIMaskLossFn.apply(self, tuple(gt_polygons), gt_counts.contiguous(), int(gt.shape[1]), len(xs), *xs, *mparams)
+        return losses
 
     def losses(self, images, features, proposals, targets, keys=None):
         """{"loss_cls", "loss_box_reg"} of detectron2's StandardROIHeads in training (box branch), differentiable in the features and, after
-        ``trainable_()``, the parameters of the box head and predictor.  proposals: one object with ``proposal_boxes`` per image; targets: one
+        ``trainable_()``, the parameters of the box head and predictor; heads built with masks=True add ``loss_mask`` (differentiable in the
+        mask head's parameters too, after ``trainable_(mask_head=True)``) and need ``gt_masks`` on every target: an object with ``.polygons`` or one list of flat coordinate arrays
+        per instance.  proposals: one object with ``proposal_boxes`` per image; targets: one
         object (or dict) with ``gt_boxes`` and ``gt_classes`` per image.  keys: [N, P + Gmax] 32-bit integers on the device that decide the
         sample (the candidates with the smallest (key, index) are taken; a candidate is a proposal or, behind them, an appended ground-truth
         box); drawn from torch's generator when None.  The assignment, the sample and the training list of the call stay in
         ``last_assignment``.  Works in either mode."""
         self._refuse_training()
+        inst = self._target_polygons(targets) if self.mask_on else None      # host data: refused before anything touches the device
         xs = self._check(features, train=True)
         N, dev = xs[0].shape[0], xs[0].device
         if len(proposals) != N:
             raise AfiError(f"roi_heads: {len(proposals)} proposal lists for a batch of {N}")
         boxes, counts = self._padded_proposals(proposals, N, dev)
         gt, gc, gn = self._targets(targets, N, dev)
-        return self.losses_padded(features, boxes, counts, gt, gc, gn, keys)
+        polys = ops.mask_polygons(inst, N, int(gt.shape[1]), dev) if self.mask_on else None
+        return self.losses_padded(features, boxes, counts, gt, gc, gn, keys, polys)
 
     def _forward_train(self, images, features, proposals, targets, keys=None):
         """(the sampled proposals per image with ``gt_classes`` and ``gt_boxes``, losses), as detectron2's StandardROIHeads.forward in training.

@@ -829,6 +829,41 @@ int afi_poly_rle_emit(const long long* poly_off, const long long* cap_off, int N
                       const long long* start_off, int* starts, void* stream);
 int afi_rle_decode(const int* starts, const long long* start_off, int N, int H, int W, unsigned char* out, void* stream);
 
+/* ------------------------------------------------------------------ the mask branch of StandardROIHeads in training (csrc/mask_loss.hip)
+ * detectron2 v0.1.1's mask_rcnn_loss restated.  The mask branch runs on the first Bf rows of every image of the box
+ * branch's training list (afi_roi_gather_samples puts the n_pos positives first): boxes [N][batch_per_image][4], classes
+ * [N][ld_classes], both read in place with their own row stride.  No float atomics, no host synchronisation; bit-identical between runs.
+ * afi_mask_targets: targets [N][Bf][M][M] bytes (0 / 1, row-major), every byte written, and counts_fg [N] = n_pos clamped to 0 .. Bf.  Row j
+ *   of image n is live when j < counts_fg[n], its sampled index i = sampled_idx[n][j] lies in 0 .. ld_matched - 1 and the image has
+ *   G = clamp(counts_g[n], 0, Gmax) > 0 boxes; its instance is g = clamp(matched_idx[n][i], 0, G - 1) (afi_roi_gather_samples' rule), whose
+ *   polygons are poly_off[n Gmax + g] .. poly_off[n Gmax + g + 1] of the batch format above (xy, vert_off [num_poly + 1], poly_off
+ *   [N Gmax + 1]; offsets outside 0 .. num_poly / 0 .. num_vert give the empty mask).  From the row's fp32 box (x0, y0, x1, y1): w = x1 - x0,
+ *   h = y1 - y0 in fp32; rw = (double)w < 0.1 ? (double)M / 0.1 : (double)((float)M / w) (a NaN w takes the fp32 quotient), rh likewise; every
+ *   vertex becomes X = (x - (double)x0) rw, Y = (y - (double)y0) rh (one fp64 subtraction, one fp64 product, no contraction); the target is the
+ *   union of the polygons on the M x M canvas by the rules above.  A row with a transformed coordinate c that is not finite or has
+ *   |5 c + .5| >= 2^30 is zero (decided on the double; no out-of-range conversion is made), as is a row that is not live or has no polygon.
+ *   M <= 28.
+ * afi_mask_loss: h = afi_roi_mask_probs' layout [N D][S][S][4][C] with D = Bf, w [Km][C], bias [Km], targets [N D][2S][2S].  For a live row
+ *   (d < clamp(counts_fg[n], 0, D), class c = classes[n][d] in 0 .. Km - 1; c = 0 when Km == 1) and output pixel p: z = afi_roi_mask_probs'
+ *   fp32 logit; term = max(z, 0) - z t + log1p(exp(-|z|)) and dz = (1 / (1 + exp(-z)) - t) / Mtot in fp64 from the fp32 z, dz rounded once.
+ *   Mtot = 4 S S sum of the clamped counts, formed on the device.  loss[0] (device fp32) = sum of the terms (fp64, fixed order) / Mtot, rounded
+ *   once; 0 when Mtot = 0.  dz [N D][S][S][4] (h's pixel order) is written completely, zero on rows that are not live.
+ *   ws: afi_mask_loss_ws_floats(N, D, C, S) floats, 8-byte aligned.
+ * afi_mask_pred_bwd: dh (h's layout, not h) = dz w[c][k] (h > 0 ? 1 : 0), one fp32 product, written completely (zero on rows that are not
+ *   live); dW [Km][C], db [Km]: per live row and pixel part the fp32 fmaf sums of dz h[k] and the fp32 sum of dz in pixel order, then per class
+ *   the partials of its rows added in (row, part) order in fp64 and rounded once; a class without a row gets zeros.  dz may have been scaled
+ *   by the caller.  C <= 1024, N D <= 65535.  ws: afi_mask_pred_bwd_ws_floats(N, D, C) floats, 16-byte aligned. */
+int afi_mask_targets(const double* xy, const long long* vert_off, const long long* poly_off, long long num_poly, long long num_vert,
+                     const float* boxes, const int* sampled_idx, int N, int batch_per_image, const int* matched_idx, int ld_matched,
+                     const int* counts_g, int Gmax, const int* n_pos, int Bf, int M, unsigned char* targets, int* counts_fg, void* stream);
+long long afi_mask_loss_ws_floats(int N, int D, int C, int S);
+int afi_mask_loss(const float* h, const float* w, const float* bias, const int* classes, int ld_classes, const int* counts_fg,
+                  const unsigned char* targets, int N, int D, int C, int S, int Km, float* loss, float* dz, float* ws, long long ws_floats,
+                  void* stream);
+long long afi_mask_pred_bwd_ws_floats(int N, int D, int C);
+int afi_mask_pred_bwd(const float* h, const float* dz, const float* w, const int* classes, int ld_classes, const int* counts_fg, int N, int D,
+                      int C, int S, int Km, float* dh, float* dW, float* db, float* ws, long long ws_floats, void* stream);
+
 /* ------------------------------------------------------------------ measurement support (bench.py)
  * When enabled, every MFMA GEMM launch is bracketed by two hipEvents recorded on the launch stream.
  * afi_profile_get(kind, out): out[0] launches, out[1] total ms, out[2] total algorithmic FLOP of that kernel since
