@@ -75,6 +75,10 @@ class SgdDesc(C.Structure):
                 ("wd", C.c_float), ("pad_", C.c_float)]
 
 
+class UnfoldDesc(C.Structure):
+    _fields_ = [("dw", C.c_void_p), ("grad", C.c_void_p), ("s", C.c_void_p), ("O", C.c_int), ("I", C.c_int), ("k", C.c_int), ("pad_", C.c_int)]
+
+
 # the C types of the header -> ctypes.  Every other POINTER (and an array parameter such as `const int F[4]`) is a c_void_p: the header
 # cannot tell a host array from a device pointer, and c_void_p takes a ctypes array, byref(...), an integer address or None alike.
 _CTYPES = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "afi_view_t": View,

@@ -66,6 +66,7 @@ struct AfiPixGemm {
     int r1_bilinear;    // R1 is a low-res [N, H/2, W/2] tensor, added as its bilinear x2 up-sampling
     int lrelu;          // activation on v: 0 none, 1 LeakyReLU(0.2), 2 ReLU
     AfiView Z; int z_lo, z_hi;                 // multiply by (Z > 0 ? 1 : 0.2) for channels in [z_lo, z_hi)
+    int z_relu;                                // the ReLU form of that mask: (Z > 0 ? 1 : 0); 0 (pix_default's memset) keeps the slope 0.2
     // split-K scratch (optional): [splitK][M][roundup4(Ncols)] partial slabs; the launcher picks splitK and fills it in
     float* partial; long long partial_floats; int splitK; int kper;   // kper: K stages per split (set by the launcher)
     // BatchNorm batch statistics of the STORED output, accumulated by the Winograd output transform itself (a separate pass over the

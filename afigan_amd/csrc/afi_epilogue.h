@@ -4,6 +4,10 @@
 #include "afi_half.h"
 
 __device__ __forceinline__ float afi_lrelu(float v) { return v > 0.f ? v : v * AFI_LRELU_SLOPE; }
+// the Z mask of a data gradient: v * lrelu'(z), or with z_relu v * relu'(z) (an exact +0 where z <= 0, whatever v holds)
+__device__ __forceinline__ float afi_zmask(const AfiPixGemm& p, float v, float z) {
+    return z > 0.f ? v : (p.z_relu ? 0.f : v * AFI_LRELU_SLOPE);
+}
 
 // bilinear x2, align_corners=False (generator_rdb.py:125): s = max(0.5*o - 0.25, 0)
 __device__ __forceinline__ void afi_bil_idx(int o, int L, int& i0, int& i1, float& lam) {
@@ -15,7 +19,7 @@ __device__ __forceinline__ void afi_bil_idx(int o, int L, int& i0, int& i1, floa
 
 
 // Fused epilogue of one float4 of accumulators (4 consecutive output columns of one GEMM row):
-//   v = alpha*acc + bias + beta*O_old + r1s*R1 (direct or bilinear x2) + r2s*R2 ; activation ; * lrelu'(Z) ; (pixel-shuffle) store
+//   v = alpha*acc + bias + beta*O_old + r1s*R1 (direct or bilinear x2) + r2s*R2 ; activation ; * lrelu'(Z) (relu'(Z) with z_relu) ; (pixel-shuffle) store
 // POST (generic-tap kernels only): the post-activation form  out = post_scale * act(...) + r2s * R2, act(...) -> O2
 template <bool POST = false>
 __device__ __forceinline__ void afi_epilogue_store(const AfiPixGemm& p, int img, int y, int x, int col, f32x4 accv) {
@@ -53,7 +57,7 @@ __device__ __forceinline__ void afi_epilogue_store(const AfiPixGemm& p, int img,
     if (p.Z.p && ch >= p.z_lo && ch < p.z_hi) {
         const f32x4 z = *(const f32x4*)(p.Z.p + (long long)img * p.Z.sN + (long long)yo * p.Z.sH + (long long)xo * p.Z.sW + ch);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= (z[j] > 0.f ? 1.f : AFI_LRELU_SLOPE);
+        for (int j = 0; j < 4; ++j) v[j] = afi_zmask(p, v[j], z[j]);
     }
     if (POST && p.r2_post) {                              // out = post_scale * act(...) + r2s * R2; the activated value goes to O2
         if (p.O2.p) *(f32x4*)(p.O2.p + (long long)img * p.O2.sN + (long long)yo * p.O2.sH + (long long)xo * p.O2.sW + ch) = v;
@@ -82,7 +86,7 @@ __device__ __forceinline__ f32x4 afi_epilogue_store_simple(const AfiPixGemm& p, 
     if (p.Z.p) {
         const f32x4 z = *(const f32x4*)(p.Z.p + (long long)img * p.Z.sN + (long long)y * p.Z.sH + (long long)x * p.Z.sW + col);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= (z[j] > 0.f ? 1.f : AFI_LRELU_SLOPE);
+        for (int j = 0; j < 4; ++j) v[j] = afi_zmask(p, v[j], z[j]);
     }
     afi_out_store(p, p.O.p + pix, v);
     return v;                                               // (the stored value: what fused statistics accumulate)

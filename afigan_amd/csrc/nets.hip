@@ -504,14 +504,15 @@ struct WinoConvOpt {
 };
 // forward (kinds kWinoFwd / kWinoFwdF4: out = conv(in, w) + bias) or data gradient (kWinoDgrad: out = conv^T(in, w) * lrelu'(z)) by descriptor
 static int wino_conv(afi_ctx* cx, WinoKind kind, AfiView in, int N, int H, int W, int K, const float* w, int Nc, const float* bias, AfiView out, AfiView z,
-                     float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st, const WinoConvOpt& o = WinoConvOpt()) {
+                     float* ws, long long ws_floats, float* part, long long part_floats, hipStream_t st, const WinoConvOpt& o = WinoConvOpt(),
+                     bool z_relu = false) {
     if ((K & 3) || (Nc & 3)) return AFI_ERR_UNSUPPORTED;
     const bool dgrad = kind == kWinoDgrad;
     AfiPixGemm g = dgrad ? conv_dgrad_desc(in, N, H, W, K, w, Nc, out) : conv_fwd_desc(in, N, H, W, K, w, bias, Nc, out);
     g.a_amax = o.in_amax; g.a_amax_known = o.in_amax_known ? 1 : 0;
     g.v_keep = o.v_keep;
     g.nt_local_sums = o.local_sums ? 1 : 0;
-    if (dgrad && z.p) { g.Z = z; g.z_lo = 0; g.z_hi = Nc; }
+    if (dgrad && z.p) { g.Z = z; g.z_lo = 0; g.z_hi = Nc; g.z_relu = z_relu ? 1 : 0; }
     const WinoForm f = wino_form(cx, g, dgrad, kind == kWinoFwdF4);
     const int rows = afi_wino_stats_rows(f.T, Nc);
     if (o.stats_rows) *o.stats_rows = 0;
@@ -888,6 +889,48 @@ int afi_conv1x1_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Co
     g.A = V(dy); g.B = w; g.b_sRow = Cin; g.b_sTap = 0;
     g.O = V(dx); g.alpha = alpha; g.beta = beta;
     return launch_pix_op(cx, g, 1, (hipStream_t)stream);
+}
+// ---- data gradients with the activation's mask by kind (z_act 1: LeakyReLU(0.2), 2: ReLU): the backward of a conv whose input is act(z).
+// The mask is the epilogue's last factor, so with beta / add it covers the join as well: dx = (alpha W^T dy + beta dx + add_scale add) * act'(z).
+// beta != 0 reads dx in the epilogue only, by the thread that stores the element -- in the whole-tile kernels and in the second pass of every
+// split-K / stream-K form alike (their first pass leaves raw partial sums in slabs) --, so dx may be updated in place.
+static int z_act_set(AfiPixGemm& g, afi_view_t z, int z_act, int Cin) {
+    if (!z.p) return AFI_OK;
+    if (z_act != 1 && z_act != 2) return AFI_ERR_BAD_ARG;
+    g.Z = V(z); g.z_lo = 0; g.z_hi = Cin; g.z_relu = z_act == 2;
+    return AFI_OK;
+}
+int afi_conv1x1_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
+                          afi_view_t add, float add_scale, afi_view_t z, int z_act, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
+    AfiPixGemm g = pix_default(N, H, W);
+    g.ntaps = 1; g.a_sgn = -1; g.Ck = Cout; g.Ncols = Cin; g.CoutPhase = Cin;
+    g.A = V(dy); g.B = w; g.b_sRow = Cin; g.b_sTap = 0;
+    g.O = V(dx); g.alpha = alpha; g.beta = beta;
+    if (add.p) { g.R1 = V(add); g.r1s = add_scale; g.r1_lo = 0; g.r1_hi = Cin; }
+    AFI_TRY(z_act_set(g, z, z_act, Cin));
+    return launch_pix_op(cx, g, 1, (hipStream_t)stream);
+}
+int afi_conv3x3_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
+                          afi_view_t z, int z_act, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if ((Cin & 3) || (Cout & 3)) return AFI_ERR_UNSUPPORTED;
+    AfiPixGemm g = conv_dgrad_desc(V(dy), N, H, W, Cout, w, Cin, V(dx));
+    g.alpha = alpha; g.beta = beta;
+    AFI_TRY(z_act_set(g, z, z_act, Cin));
+    return launch_pix_op(cx, g, 1, (hipStream_t)stream);
+}
+int afi_conv3x3_wino_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, afi_view_t z, int z_act,
+                               float* ws, long long ws_floats, void* stream) {
+    afi_ctx* cx = ctx; (void)cx;
+    AFI_CTX_CHECK(ctx);
+    if (N <= 0 || H <= 0 || W <= 0 || !ws) return AFI_ERR_BAD_ARG;
+    if (z.p && z_act != 1 && z_act != 2) return AFI_ERR_BAD_ARG;
+    return wino_conv(cx, kWinoDgrad, V(dy), N, H, W, Cout, w, Cin, nullptr, V(dx), z.p ? V(z) : null_view(), ws, ws_floats, nullptr, 0, (hipStream_t)stream,
+                     WinoConvOpt(), z.p && z_act == 2);
 }
 int afi_conv1x1_dgrad_out16(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, int dx_dtype, float alpha,
                             float beta, void* stream) {

@@ -475,7 +475,7 @@ __device__ __forceinline__ void afi_epilogue_finish(const AfiPixGemm& p, const A
     }
     if (e.use_z) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= (e.zv[j] > 0.f ? 1.f : AFI_LRELU_SLOPE);
+        for (int j = 0; j < 4; ++j) v[j] = afi_zmask(p, v[j], e.zv[j]);
     }
     afi_out_store(p, e.dst, v);
 }

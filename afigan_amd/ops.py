@@ -301,7 +301,20 @@ def conv3x3_fwd(x, w, bias=None, lrelu=False, out=None, alpha=1.0, beta=0.0, out
     return out
 
 
-def conv3x3_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, z=None):
+Z_ACTS = {"lrelu": 1, "relu": 2}           # the activation whose derivative a data gradient's z mask applies (the numbering of lrelu= / act=)
+
+
+def _z_act(where, z, z_act):
+    if z_act not in Z_ACTS:
+        raise _lib.AfiError(f"{where}: z_act must be one of {sorted(Z_ACTS)}, got {z_act!r}")
+    if z is None:
+        raise _lib.AfiError(f"{where}: z_act={z_act!r} needs z=, the activation the mask is read from")
+    return Z_ACTS[z_act]
+
+
+def conv3x3_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, z=None, *, z_act=None):
+    """dx = (alpha*conv3x3^T(dy, w) + beta*dx) * act'(z).  Without z_act: the LeakyReLU(0.2) mask of afi_conv3x3_dgrad; z_act "lrelu" /
+    "relu": afi_conv3x3_dgrad_act."""
     _check_cuda(dy, w, dx, z)
     _ensure_op_scratch(dy.device)
     N, Cout, H, W = dy.shape
@@ -309,6 +322,10 @@ def conv3x3_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, z=None):
     w = ohwi(w)
     if dx is None:
         dx = new_pixel_major(N, Cin, H, W, dy.device)
+    if z_act is not None:
+        call("afi_conv3x3_dgrad_act", view_of(dy), N, H, W, Cout, _p(w), Cin, view_of(dx), float(alpha), float(beta), view_of(z),
+             _z_act("conv3x3_dgrad", z, z_act), stream_ptr())
+        return dx
     call("afi_conv3x3_dgrad", view_of(dy), N, H, W, Cout, _p(w), Cin, view_of(dx), float(alpha), float(beta),
          view_of(z) if z is not None else _NULL_VIEW, stream_ptr())
     return dx
@@ -356,8 +373,8 @@ def conv3x3_wino_infer(x, w, bias=None, act=0):
     return out
 
 
-def conv3x3_wino_dgrad(dy, w, z=None):
-    """Data gradient of the 3x3 conv in Winograd form: dx = conv^T(dy) [* lrelu'(z)]."""
+def conv3x3_wino_dgrad(dy, w, z=None, *, z_act=None):
+    """Data gradient of the 3x3 conv in Winograd form: dx = conv^T(dy) [* lrelu'(z)]; z_act "lrelu" / "relu": afi_conv3x3_wino_dgrad_act."""
     _check_cuda(dy, w, z)
     N, Cout, H, W = dy.shape
     Cin = w.shape[1]
@@ -365,6 +382,10 @@ def conv3x3_wino_dgrad(dy, w, z=None):
     n = _lib.load().afi_conv3x3_wino_ws_floats(N, H, W, Cin, Cout)
     ws = new_workspace(n, dy.device)
     dx = new_pixel_major(N, Cin, H, W, dy.device)
+    if z_act is not None:
+        call("afi_conv3x3_wino_dgrad_act", view_of(dy), N, H, W, Cout, _p(w), Cin, view_of(dx), view_of(z), _z_act("conv3x3_wino_dgrad", z, z_act),
+             _p(ws), n, stream_ptr())
+        return dx
     call("afi_conv3x3_wino_dgrad", view_of(dy), N, H, W, Cout, _p(w), Cin, view_of(dx), view_of(z) if z is not None else _NULL_VIEW,
          _p(ws), n, stream_ptr())
     return dx
@@ -456,13 +477,27 @@ def conv1x1_fwd(x, w, bias=None, add=None, add_scale=1.0, alpha=1.0, out=None, a
     return out
 
 
-def conv1x1_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, out_dtype=torch.float32):
-    """out_dtype bf16 / fp16: a fresh 2-byte dx rounded by the epilogue (afi_conv1x1_dgrad_out16; beta must be 0)."""
-    _check_cuda(dy, w, dx)
+def conv1x1_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, out_dtype=torch.float32, *, z=None, z_act="lrelu", add=None, add_scale=1.0):
+    """out_dtype bf16 / fp16: a fresh 2-byte dx rounded by the epilogue (afi_conv1x1_dgrad_out16; beta must be 0).
+    With z= and / or add= (afi_conv1x1_dgrad_act): dx = (alpha*W^T dy + beta*dx + add_scale*add) * act'(z), z_act "lrelu" or "relu"; dx, add
+    and z may be strided views of pixel-major tensors (every second pixel), and beta = 1 may update dx in place."""
+    _check_cuda(dy, w, dx, z, add)
     _ensure_op_scratch(dy.device)
     N, Cout, H, W = dy.shape
     Cin = w.shape[1]
     w2 = w.reshape(Cout, Cin).contiguous()
+    if z is not None or add is not None:
+        if out_dtype != torch.float32:
+            raise _lib.AfiError("conv1x1_dgrad: z= / add= go with an fp32 dx")
+        if dx is None:
+            dx = new_pixel_major(N, Cin, H, W, dy.device)
+        for name, t in (("dx", dx), ("z", z), ("add", add)):
+            if t is not None and tuple(t.shape) != (N, Cin, H, W):
+                raise _lib.AfiError(f"conv1x1_dgrad: {name} {tuple(t.shape)} is not the conv's input shape {(N, Cin, H, W)}")
+        call("afi_conv1x1_dgrad_act", view_of(dy), N, H, W, Cout, _p(w2), Cin, view_of(dx), float(alpha), float(beta),
+             view_of(add) if add is not None else _NULL_VIEW, float(add_scale), view_of(z) if z is not None else _NULL_VIEW,
+             _z_act("conv1x1_dgrad", z, z_act) if z is not None else 0, stream_ptr())
+        return dx
     if out_dtype != torch.float32:
         if dx is not None:
             raise _lib.AfiError("conv1x1_dgrad: a 2-byte output is always a fresh tensor")
@@ -483,6 +518,30 @@ def conv1x1_wgrad(dy, x, alpha=1.0):
     dw = torch.zeros((Cout, Cin), device=dy.device, dtype=torch.float32)
     call("afi_conv1x1_wgrad", view_of(dy), view_of(x), N, H, W, Cout, Cin, _p(dw), float(alpha), stream_ptr())
     return dw
+
+
+def frozen_wgrad_unfold(descs):
+    """grad[o][i][kh][kw] += s[o] * dw[o][kh][kw][i] for every (dw, grad, s) of `descs` in one launch (afi_frozen_wgrad_unfold): dw the
+    gradient of a weight folded with its FrozenBN, in the kernels' memory ([O, I, k, k] with OHWI memory, or [O, I] for k = 1), grad a
+    contiguous [O, I, k, k] tensor, s the fold's [O] scale."""
+    if not descs:
+        return
+    table = (_lib.UnfoldDesc * len(descs))()
+    max_oi = 0
+    for d, (dw, grad, s_) in zip(table, descs):
+        _check_cuda(dw, grad, s_)
+        O, I = grad.shape[:2]
+        k = grad.shape[2] if grad.dim() == 4 else 1
+        ok = grad.is_contiguous() and k in (1, 3) and dw.numel() == grad.numel() == O * I * k * k and s_.numel() == O and s_.is_contiguous() \
+            and dw.shape[:2] == grad.shape[:2] and (dw.permute(0, 2, 3, 1).is_contiguous() if dw.dim() == 4 else dw.is_contiguous())
+        if not ok:
+            raise _lib.AfiError(f"frozen_wgrad_unfold: dw {tuple(dw.shape)} / grad {tuple(grad.shape)} / s {tuple(s_.shape)}: grad must be a "
+                                "contiguous [O, I, k, k] (k 1 or 3), dw the same shape in OHWI memory, s [O]")
+        d.dw, d.grad, d.s, d.O, d.I, d.k = dw.data_ptr(), grad.data_ptr(), s_.data_ptr(), O, I, k
+        max_oi = max(max_oi, O * ((I + 31) // 32))
+    dev = descs[0][0].device
+    table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    call("afi_frozen_wgrad_unfold", _p(table_dev), len(descs), max_oi, stream_ptr())
 
 
 def bias_grad(dy):

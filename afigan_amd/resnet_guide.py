@@ -12,15 +12,21 @@ epilogue, shortcuts, FPN laterals with the top-down addend) afi_conv1x1_fwd, str
 >= 128 channels on both sides, afi_conv3x3_wino_infer; the stride-2 3x3 of STRIDE_IN_1X1 = False afi_conv3x3s2_fwd; the x2 nearest top-down
 up-sampling and p6 afi_nearest_nhwc.  No MIOpen, hipBLASLt or torch conv / pool / interpolate kernel runs.
 
+Training (``ResNet.trainable_``): the stages behind ``freeze_at`` run as one autograd Function, ``_ResNetTrainFn`` -- forward on the
+kernels above, backward on afi_conv1x1_wgrad / afi_conv3x3_wgrad / afi_conv3x3_wino_wgrad / afi_conv3x3s2_wgrad and the data gradients with
+the ReLU mask, the residual join and the pyramid's cotangent in their epilogue (afi_conv1x1_dgrad_act, afi_conv3x3_dgrad_act,
+afi_conv3x3_wino_dgrad_act), then one afi_frozen_wgrad_unfold launch from the folded weights' gradients to the parameters'.
+
 Out of scope (AfiError at build time): dilation, groups > 1, deformable convs, norms other than FrozenBN, a normalised FPN, the ResNeSt
-options; at call time, a forward that autograd could differentiate."""
+options; at call time, a forward that autograd could differentiate through a frozen module, the stem's backward (``freeze_at=0``)."""
 import torch
 import torch.nn as nn
 
-from . import ops, registry
+from . import _lib, ops, registry
 from ._lib import AfiError
 from .fpn_sr import ShapeSpec
 from .frozen import FROZEN_BN_EPS, Conv2d, FrozenBatchNorm2d, cfg_get, check_forward_only, conv1x1, conv3x3, prepared  # noqa: F401
+from .rpn import _wino
 
 _BLOCKS = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}
 
@@ -67,6 +73,160 @@ class BottleneckBlock(nn.Module):
         y = conv3x3(y, f[id(self.conv2)], self.conv2.stride, relu=True)
         return conv1x1(y, f[id(self.conv3)], add=s, relu=True)
 
+    def convs(self):
+        """The block's convs in the order ``_ResNetTrainFn`` takes their weights: conv1, conv2, conv3, then the shortcut if there is one."""
+        return [self.conv1, self.conv2, self.conv3] + ([self.shortcut] if self.shortcut is not None else [])
+
+    def run_keep(self, x, f):
+        """`run`, also returning conv1's and conv2's (post-ReLU) outputs: what the backward reads its masks and weight gradients from."""
+        s = x if self.shortcut is None else conv1x1(x, f[id(self.shortcut)], self.shortcut.stride)
+        a1 = conv1x1(x, f[id(self.conv1)], self.conv1.stride, relu=True)
+        a2 = conv3x3(a1, f[id(self.conv2)], self.conv2.stride, relu=True)
+        return a1, a2, conv1x1(a2, f[id(self.conv3)], add=s, relu=True)
+
+
+def _strided(t, stride):
+    return t if stride == 1 else t[:, :, ::stride, ::stride]
+
+
+def _dense_pm(t, like):
+    """A cotangent as a dense pixel-major fp32 tensor (None: none arrived for this output)."""
+    if t is None:
+        return None
+    t = ops.pixel_major(t.float())
+    if not ops.is_dense_pm(t):
+        d = ops.new_pixel_major(*like.shape, like.device)
+        d.copy_(t)
+        t = d
+    return t
+
+
+class _ResNetTrainFn(torch.autograd.Function):
+    """The trainable stages of a ResNet bottom-up as one node: ``(net, fuse_masks, x, *weights) -> out_features of those stages``, x the first
+    trainable stage's input (no gradient: the stages below are frozen), weights the conv weights of ``net._train_convs()`` in that order.
+
+    Forward: every block on frozen.conv1x1 / frozen.conv3x3 over the prepared fold (the frozen module's kernels), keeping a1, a2 and y, all
+    post-ReLU.  Backward, blocks in reverse; gz = the gradient at a block's pre-activation output, afi_relu_bwd(d_out, y) for the last block:
+      conv3  weight gradient, then g2 = (W3'^T gz) * [a2 > 0]                      -- afi_conv1x1_dgrad_act
+      conv2  weight gradient and g1 = (W2'^T g2) * [a1 > 0] in the forward's regime  -- afi_conv3x3_dgrad_act / afi_conv3x3_wino_dgrad_act
+             (the stride-2 3x3 of STRIDE_IN_1X1 = False: afi_conv3x3s2_dgrad + one afi_relu_bwd)
+      conv1  weight gradient, then the data gradient LAST: an identity block writes (W1'^T g1 + gz + cotangent of x) * [x > 0] into the gz
+             buffer itself (beta = 1, in place) -- the previous block's gz; a down-sampling block starts a fresh buffer from the cotangent of x
+             (afi_relu_bwd) or zeros, and its shortcut's and conv1's data gradients add into the view of the pixels they read (beta = 1, the
+             mask again: a 0/1 mask applied twice is the same mask).  The first trainable block computes no dx.
+    ``fuse_masks=False``: the same GEMMs through the entry points without the mask, afi_relu_bwd and the adds as passes of their own.
+    All dw' (gradients of the FOLDED weights) live in one zero-filled buffer the weight-gradient kernels add into; one afi_frozen_wgrad_unfold
+    launch takes them through the fold's scale to the parameters' [O][I][kh][kw] gradients."""
+
+    @staticmethod
+    @_lib.ctx_forward
+    def forward(ctx, net, fuse, x, *weights):
+        f, scales = net._prepare(), net._fold_scales()
+        blocks = net._train_blocks()
+        saved, outs, y = [x], [], x
+        ctx.out_block = {}                                                   # index of the block whose y is output k
+        for name in net._train_stages:
+            for blk in getattr(net, name):
+                a1, a2, y = blk.run_keep(y, f)
+                saved += [a1, a2, y]
+            if name in net._out_features:
+                ctx.out_block[len(saved) // 3 - 1] = len(outs)
+                outs.append(y)
+        convs = [c for blk in blocks for c in blk.convs()]
+        ctx.save_for_backward(*saved, *[f[id(c)][0] for c in convs], *[scales[id(c)] for c in convs])
+        ctx.blocks, ctx.fuse = blocks, bool(fuse)
+        ctx.wshapes = [tuple(w.shape) for w in weights]
+        return tuple(outs)
+
+    @staticmethod
+    @_lib.ctx_backward
+    def backward(ctx, *douts):
+        blocks, fuse, sv = ctx.blocks, ctx.fuse, ctx.saved_tensors
+        B = len(blocks)
+        nconv = len(ctx.wshapes)
+        acts, wf, sc = sv[:1 + 3 * B], sv[1 + 3 * B:1 + 3 * B + nconv], sv[1 + 3 * B + nconv:]
+        dev = acts[0].device
+        xin = lambda b: acts[3 * b]                                          # block b's input: x, or block b - 1's y
+        a1, a2, yb = (lambda b: acts[3 * b + 1]), (lambda b: acts[3 * b + 2]), (lambda b: acts[3 * b + 3])
+        cot = {b: _dense_pm(douts[k], yb(b)) for b, k in ctx.out_block.items()}
+        # one zero-filled home for every dw' (OHWI / [O][I] memory, each slice a multiple of 16 bytes) and one for the parameters' gradients
+        sizes = [int(torch.Size(s_).numel()) for s_ in ctx.wshapes]
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        dwflat = torch.zeros(offs[-1], device=dev, dtype=torch.float32)
+        gflat = torch.zeros(offs[-1], device=dev, dtype=torch.float32)
+        dws, grads = [], []
+        for (O, I, k, _), o, n in zip(ctx.wshapes, offs, sizes):
+            seg = dwflat[o:o + n]
+            dws.append(seg.view(O, 3, 3, I).permute(0, 3, 1, 2) if k == 3 else seg.view(O, I))
+            grads.append(gflat[o:o + n].view(O, I, k, k))
+
+        def wgrad1x1(dy, x, dw):
+            N, Cout, H, W = dy.shape
+            _lib.call("afi_conv1x1_wgrad", ops.view_of(dy), ops.view_of(x), N, H, W, Cout, x.shape[1], ops._p(dw), 1.0, ops.stream_ptr())
+
+        ci = nconv
+        gz = None
+        for b in reversed(range(B)):
+            blk = blocks[b]
+            n_own = len(blk.convs())
+            ci -= n_own
+            i1, i2, i3, isc = ci, ci + 1, ci + 2, (ci + 3 if n_own == 4 else None)
+            x, A1, A2 = xin(b), a1(b), a2(b)
+            if gz is None:                                                   # the last block: everything it gets is its output's cotangent
+                c = cot.get(b)
+                gz = ops.relu_bwd(c, yb(b)) if c is not None else ops.new_pixel_major(*yb(b).shape, dev, zero=True)
+            # conv3
+            wgrad1x1(gz, A2, dws[i3])
+            g2 = ops.conv1x1_dgrad(gz, wf[i3], z=A2, z_act="relu") if fuse else ops.relu_bwd(ops.conv1x1_dgrad(gz, wf[i3]), A2)
+            # conv2, in the regime its forward ran in
+            if blk.conv2.stride == 2:
+                ops.conv3x3s2_wgrad(g2, A1, dw=dws[i2])
+                g1 = ops.relu_bwd(ops.conv3x3s2_dgrad(g2, wf[i2], tuple(A1.shape[2:])), A1)
+            else:
+                wino = _wino(A1, g2.shape[1])
+                (ops.conv3x3_wino_wgrad if wino else ops.conv3x3_wgrad)(g2, A1, dw=dws[i2])
+                dgrad = ops.conv3x3_wino_dgrad if wino else ops.conv3x3_dgrad
+                g1 = dgrad(g2, wf[i2], z=A1, z_act="relu") if fuse else ops.relu_bwd(dgrad(g2, wf[i2]), A1)
+            # conv1 and the shortcut: weight gradients on the pixels they read
+            s1 = blk.conv1.stride
+            wgrad1x1(g1, _strided(x, s1), dws[i1])
+            if isc is not None:
+                ss = blk.shortcut.stride
+                wgrad1x1(gz, _strided(x, ss), dws[isc])
+            if b == 0:
+                break                                                        # the stages below are frozen: no dx
+            c = cot.get(b - 1)
+            if fuse:
+                if isc is None:                                              # identity block: join, cotangent and mask in conv1's epilogue, in place
+                    gz = ops.conv1x1_dgrad(g1, wf[i1], dx=gz, beta=1.0, z=x, z_act="relu", add=c)
+                else:
+                    dx = ops.relu_bwd(c, x) if c is not None else ops.new_pixel_major(*x.shape, dev, zero=True)
+                    ops.conv1x1_dgrad(gz, wf[isc], dx=_strided(dx, ss), beta=1.0, z=_strided(x, ss), z_act="relu")
+                    ops.conv1x1_dgrad(g1, wf[i1], dx=_strided(dx, s1), beta=1.0, z=_strided(x, s1), z_act="relu")
+                    gz = dx
+            else:                                                            # the unfused baseline: every add and mask a pass of its own
+                if s1 == 1:
+                    dx = ops.conv1x1_dgrad(g1, wf[i1])
+                else:
+                    dx = ops.new_pixel_major(*x.shape, dev, zero=True)
+                    ops.conv1x1_dgrad(g1, wf[i1], dx=_strided(dx, s1))
+                if isc is None:
+                    dx = dx + gz
+                elif ss == 1:
+                    dx = dx + ops.conv1x1_dgrad(gz, wf[isc])
+                else:
+                    t = ops.new_pixel_major(*x.shape, dev, zero=True)
+                    ops.conv1x1_dgrad(gz, wf[isc], dx=_strided(t, ss))
+                    dx = dx + t
+                if c is not None:
+                    dx = dx + c
+                gz = ops.relu_bwd(dx, x)
+        ops.frozen_wgrad_unfold(list(zip(dws, grads, sc)))
+        need = ctx.needs_input_grad[3:]
+        return (None, None, None, *[g if n else None for g, n in zip(grads, need)])
+
 
 class ResNetBase(_Frozen):
     """What the ResNet and ResNeSt bottom-ups share: a stem (4x down) and the stages res2.. of bottleneck blocks, each twice as wide and, from
@@ -101,7 +261,17 @@ class ResNetBase(_Frozen):
     def output_shape(self):
         return {n: ShapeSpec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
 
+    _train_stages = ()                   # ResNet.trainable_: the stages that run under autograd
+    _fuse_masks = True
+
+    def _wants_graph(self):
+        """The differentiable path: grad mode on, ``trainable_`` has named stages and a parameter requires grad (BiFPN_AFIGAN._wants_graph's
+        rule).  Everything else is the frozen forward, with its refusals."""
+        return bool(self._train_stages) and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
     def forward(self, x):
+        if self._wants_graph():
+            return self._forward_train(x)
         check_forward_only(self, x, self.what)
         with torch.no_grad():
             f = self._prepare()
@@ -135,6 +305,68 @@ class ResNet(ResNetBase):
 
     def _own_convs(self):
         return [m for m in self.modules() if isinstance(m, Conv2d)]
+
+    # ---- training
+    def trainable_(self, freeze_at=2, fuse_masks=True):
+        """detectron2's ``ResNet.freeze(freeze_at)`` read the other way round: the stem and res2..res{freeze_at} stay frozen, the conv weights
+        of the later stages get ``requires_grad=True`` (the FrozenBN tensors stay buffers) and ``forward`` runs those stages under autograd
+        (``_ResNetTrainFn``).  ``trainable_(False)`` restores the all-frozen, forward-only module.  ``fuse_masks=False``: the unfused backward
+        (every ReLU mask and residual add a pass of its own), the baseline the fused one is measured against.  Returns self."""
+        if freeze_at is False:
+            stages = []
+        else:
+            if isinstance(freeze_at, bool) or not isinstance(freeze_at, int) or not 0 <= freeze_at <= 5:
+                raise AfiError(f"resnet_guide: trainable_(freeze_at={freeze_at!r}): an integer 1..5 (BACKBONE.FREEZE_AT), or False to freeze everything")
+            if freeze_at == 0:
+                raise AfiError("resnet_guide: BACKBONE.FREEZE_AT 0 trains the stem, which needs the backward of the 7x7 stride-2 conv and of the "
+                               "max-pool; neither exists here (freeze_at >= 1 only)")
+            stages = [n for n in self.stage_names if int(n[3:]) > freeze_at]
+        for name in self.stage_names:
+            for blk in getattr(self, name):
+                for c in blk.convs():
+                    c.weight.requires_grad_(name in stages)
+        self._train_stages, self._fuse_masks = tuple(stages), bool(fuse_masks)
+        return self
+
+    def _train_blocks(self):
+        return [blk for name in self._train_stages for blk in getattr(self, name)]
+
+    def _train_convs(self):
+        return [c for blk in self._train_blocks() for c in blk.convs()]
+
+    def _fold_scales(self):
+        """s = gamma / sqrt(var + eps) of every trainable conv's FrozenBN, fp64 rounded once: d w / d w' of the fold, per output channel."""
+        convs = self._train_convs()
+        ts = [t for c in convs for t in c.norm.buffers()]
+        return prepared(self, "bn_scales", ts, lambda: {
+            id(c): (c.norm.weight.double() * torch.rsqrt(c.norm.running_var.double() + c.norm.eps)).float().contiguous() for c in convs})
+
+    def _forward_train(self, x):
+        if not x.is_cuda:
+            raise AfiError(f"{self.what} runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if x.requires_grad:
+            raise AfiError(f"{self.what}: the input requires grad, but the stem is frozen (its backward does not exist here)")
+        convs = self._train_convs()
+        own = {id(c.weight) for c in convs}
+        stray = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in own]
+        if stray:
+            raise AfiError(f"{self.what}: {stray[:3]} require grad but belong to a frozen stage (trainable_(freeze_at) names the trainable ones)")
+        with torch.no_grad():
+            f = self._prepare()
+            out = {}
+            y = self.stem.run(x.float(), f)
+            if "stem" in self._out_features:
+                out["stem"] = y
+            for name in self.stage_names:
+                if name in self._train_stages:
+                    break
+                for blk in getattr(self, name):
+                    y = blk.run(y, f)
+                if name in self._out_features:
+                    out[name] = y
+        outs = _ResNetTrainFn.apply(self, self._fuse_masks, y, *[c.weight for c in convs])
+        out.update(zip([n for n in self._train_stages if n in self._out_features], outs))
+        return out
 
 
 class LastLevelMaxPool(nn.Module):
@@ -247,9 +479,15 @@ def build_resnet_fpn_backbone(cfg, input_shape=None):
                cfg_get(fpn, "OUT_CHANNELS", 256), cfg_get(fpn, "FUSE_TYPE", "sum"))
 
 
-def use_as_bottom_up():
-    """Opt in: the AFI backbones' "resnet" bottom-up lookup (registry.bottom_up_builder) returns this frozen, forward-only ResNet."""
-    registry.set_bottom_up_builder("resnet", build_resnet_backbone)
+def build_trainable_resnet_backbone(cfg, input_shape=None):
+    """The ResNet bottom-up with the stages behind ``cfg.MODEL.BACKBONE.FREEZE_AT`` trainable (steps 2 and 3: FREEZE_AT 2)."""
+    return _resnet_from_cfg(cfg, input_shape).trainable_(int(cfg_get(cfg_get(cfg.MODEL, "BACKBONE", None), "FREEZE_AT", 2)))
+
+
+def use_as_bottom_up(trainable=False):
+    """Opt in: the AFI backbones' "resnet" bottom-up lookup (registry.bottom_up_builder) returns this ResNet -- frozen and forward-only, or
+    with ``trainable=True`` the one ``build_trainable_resnet_backbone`` makes (same state-dict keys: a model-zoo file loads as before)."""
+    registry.set_bottom_up_builder("resnet", build_trainable_resnet_backbone if trainable else build_resnet_backbone)
 
 
 REGISTERED = registry.register_local_backbone(build_resnet_fpn_backbone)        # (with detectron2 installed the name is detectron2's)

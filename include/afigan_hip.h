@@ -349,6 +349,17 @@ int afi_conv1x1_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, 
 int afi_conv1x1_dgrad(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
                       void* stream);
 int afi_conv1x1_wgrad(afi_ctx_t* ctx, afi_view_t dy, afi_view_t x, int N, int H, int W, int Cout, int Cin, float* dw, float alpha, void* stream);
+/* The data gradients with the activation's mask by kind, for a conv whose input is act(z): z_act 1 = LeakyReLU(0.2) (the factor of the
+ * z_or_null forms above), 2 = ReLU (z > 0 ? 1 : 0, an exact 0 where z <= 0); z NULL = no mask.  The mask is the last factor, over the join:
+ *   dx = (alpha*W^T dy + beta*dx + add_scale*add) * act'(z).
+ * dx, add and z may be strided views (every second pixel).  beta != 0 reads dx only in the epilogue, by the thread that stores the element
+ * (split-K forms included), so dx may be updated in place as long as it aliases neither dy nor w. */
+int afi_conv1x1_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, float alpha, float beta,
+                          afi_view_t add_or_null, float add_scale, afi_view_t z_or_null, int z_act, void* stream);
+int afi_conv3x3_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx,
+                          float alpha, float beta, afi_view_t z_or_null, int z_act, void* stream);
+int afi_conv3x3_wino_dgrad_act(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w_ohwi, int Cin, afi_view_t dx,
+                               afi_view_t z_or_null, int z_act, float* ws, long long ws_floats, void* stream);
 /* afi_conv1x1_dgrad storing a 2-byte `dx` (dx_dtype AFI_STORE_BF16 / _F16; beta != 0: AFI_ERR_UNSUPPORTED) -- the lateral conv's input gradient */
 int afi_conv1x1_dgrad_out16(afi_ctx_t* ctx, afi_view_t dy, int N, int H, int W, int Cout, const float* w, int Cin, afi_view_t dx, int dx_dtype,
                             float alpha, float beta, void* stream);
@@ -476,6 +487,13 @@ typedef struct afi_sgd_desc { float* p; const float* g; float* m; long long n; f
 int afi_sgd_momentum_step(const afi_sgd_desc_t* descs_dev, int ntensors, long long max_n, float lr, float momentum,
                           float gscale, void* stream);
 int afi_scale_inplace(float* p, long long n, float s, void* stream);
+
+/* Weight gradients of convs that ran on weights folded with their FrozenBN (w' = w * s[o], s = gamma / sqrt(var + eps)), back to the
+ * parameter: grad[o][i][kh][kw] = fmaf(s[o], dw'[o][kh][kw][i], grad[o][i][kh][kw]) -- dw' in the kernels' [O][k][k][I] memory ([O][I] for
+ * k = 1), grad in the parameter's [O][I][k][k].  One launch over a DEVICE array of descriptors (all trainable convs of a network); every
+ * element has one owner: no atomics, bit-identical between runs.  max_oi: the largest O * ceil(I / 32) of the descriptors. */
+typedef struct afi_unfold_desc { const float* dw; float* grad; const float* s; int O; int I; int k; int pad_; } afi_unfold_desc_t;
+int afi_frozen_wgrad_unfold(const afi_unfold_desc_t* descs_dev, int ntensors, long long max_oi, void* stream);
 
 /* layout changes at the detectron2 boundary: [N][C][P] <-> [N][P][C] */
 int afi_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, void* stream);
