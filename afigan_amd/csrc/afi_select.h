@@ -4,6 +4,8 @@
 #include "afi_common.h"
 
 #define RPN_MAXK 1024
+#define RPN_MAXK_WIDE 4096                  // the "wide" selection of rpn.hip: 64 x 64, so the suppressed set is one 64-bit word per lane of a wave
+#define RPN_WIDE_TOTAL (5 * RPN_MAXK_WIDE)  // entries of all levels of an image afi_rpn_merge_wide holds in LDS (keys 80 KiB + positions 40 KiB)
 
 typedef unsigned long long u64;
 

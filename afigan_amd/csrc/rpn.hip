@@ -18,6 +18,10 @@
 //                    is compiled without fused multiply-adds: inter / (area_a + area_b - inter) > thresh, each operation rounded to fp32.
 //   afi_rpn_merge    the kept boxes of all levels of an image in (logit descending, level, rank) order, cut to post_k: every level's list is
 //                    already sorted, so an entry's place is its own rank plus one binary search per other level.  No sort, no atomics.
+// The "wide" forms (lists of 1025 .. 4096 per level: PRE_NMS_TOPK_TRAIN of the reference's base config is 2000) are the last section of the file:
+//   afi_rpn_topk_wide   the same histogram, filter and radix select; the pick holds sel[4096] and sorts the next power of two >= k.
+//   afi_rpn_nms_wide    the bit matrix in a workspace, its upper triangle built by one block per 64 x 64 tile; one wave per image sweeps it.
+//   afi_rpn_merge_wide  afi_rpn_merge with threads looping over a level's entries, 5 x 4096 entries in all.
 // Nothing here synchronises with the host, and every result is bit-identical from run to run and under hipGraph replay.
 #include "../../include/afigan_hip.h"
 #include "afi_common.h"
@@ -349,5 +353,295 @@ int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N,
     if (level_off[L] <= 0) return AFI_ERR_BAD_ARG;
     hipLaunchKernelGGL(afi_rpn_merge_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes, out_logits,
                        counts);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ================================================================================================ the wide forms: 1024 < k <= 4096 per level
+// ------------------------------------------------------------------------------------------------ top-k
+// afi_rpn_pick_kernel with sel[RPN_MAXK_WIDE]: the same select (restated: the narrow kernel's code object stays as it is), then a bitonic sort
+// of P = 2048 or 4096 words, P / 2 compare-exchanges per step over the 1024 threads.
+template <bool DIRECT>
+__global__ __launch_bounds__(1024) void afi_rpn_pick_wide_kernel(const AfiView lg, int W, int A, int n, int k, const int* __restrict__ hdr,
+                                                                 const u64* __restrict__ cand_all, float* __restrict__ vals,
+                                                                 int* __restrict__ idx, long long ld) {
+    __shared__ int hist[2048];
+    __shared__ int wtot[16];
+    __shared__ int res[2];
+    __shared__ u64 sel[RPN_MAXK_WIDE];
+    __shared__ int nsel;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    int m = n;
+    const u64* cand = nullptr;
+    if (!DIRECT) {
+        m = hdr[(long long)img * RPN_HDR + RPN_BINS];
+        m = m < 0 ? 0 : (m > n ? n : m);
+        cand = cand_all + (long long)img * n;
+    }
+    auto word = [&](int i) -> u64 { return DIRECT ? rpn_word(*rpn_at(lg, img, i, W, A), i) : cand[i]; };
+    int need = k < m ? k : m, group = m, shift = 32 + RPN_IDX_BITS;
+    u64 prefix = 0;
+    const int widths[5] = {11, 11, 10, 11, 11};
+    for (int p = 0; p < 5 && need < group; ++p) {
+        const int bits = widths[p], nb = 1 << bits;
+        shift -= bits;
+        for (int i = tid; i < nb; i += 1024) hist[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < m; i += 1024) {
+            const u64 c = word(i);
+            if ((c >> (shift + bits)) == prefix) atomicAdd(&hist[(int)(c >> shift) & (nb - 1)], 1);
+        }
+        __syncthreads();
+        rpn_find_digit(hist, nb, need, wtot, res);
+        need -= res[1];
+        group = hist[res[0]];
+        prefix = (prefix << bits) | (u64)res[0];
+        __syncthreads();
+    }
+    if (tid == 0) nsel = 0;
+    __syncthreads();
+    for (int i = tid; i < m; i += 1024) {
+        const u64 c = word(i);
+        if ((c >> shift) >= prefix) {
+            const int s = atomicAdd(&nsel, 1);
+            if (s < RPN_MAXK_WIDE) sel[s] = c;             // (never more than min(k, m) <= 4096: the guard keeps a wrong count inside the array)
+        }
+    }
+    __syncthreads();
+    const int ns = nsel < RPN_MAXK_WIDE ? nsel : RPN_MAXK_WIDE;
+    const int P = (k > 2048 || ns > 2048) ? 4096 : 2048;
+    for (int i = ns + tid; i < P; i += 1024) sel[i] = 0;   // below every real word
+    __syncthreads();
+    for (int ksz = 2; ksz <= P; ksz <<= 1)
+        for (int j = ksz >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += 1024) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;        // the t-th pair of this step: bit j clear / set
+                const u64 a = sel[i], b = sel[o];
+                const bool desc = (i & ksz) == 0;
+                if (desc ? a < b : a > b) { sel[i] = b; sel[o] = a; }
+            }
+            __syncthreads();
+        }
+    for (int t = tid; t < k; t += 1024) {
+        const u64 c = sel[t];
+        int i = (int)((~(unsigned)c) & RPN_IDX_MASK);
+        if (c == 0 || i >= n) i = 0;                       // (never: k <= m real words)
+        idx[(long long)img * ld + t] = i;
+        vals[(long long)img * ld + t] = *rpn_at(lg, img, i, W, A);
+    }
+}
+
+long long afi_rpn_topk_wide_ws_floats(int N, int H, int W, int A) { return afi_rpn_topk_ws_floats(N, H, W, A); }
+
+int afi_rpn_topk_wide(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                      void* stream) {
+    if (!logits.p || !vals || !idx || N <= 0 || N > 65535 || H <= 0 || W <= 0 || A <= 0 || k <= 0 || ld < k) return AFI_ERR_BAD_ARG;
+    const long long nn = (long long)H * W * A;
+    if (A > RPN_MAX_A || k <= RPN_MAXK || k > RPN_MAXK_WIDE || nn >= RPN_IDX_MASK) return AFI_ERR_UNSUPPORTED;      // k <= 1024: afi_rpn_topk
+    if (k > nn) return AFI_ERR_BAD_ARG;
+    const int n = (int)nn;
+    const AfiView lg{(float*)logits.p, logits.sN, logits.sH, logits.sW};
+    hipStream_t st = (hipStream_t)stream;
+    if (n <= RPN_DIRECT_MAX) {
+        hipLaunchKernelGGL(afi_rpn_pick_wide_kernel<true>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)nullptr, (const u64*)nullptr,
+                           vals, idx, ld);
+        return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+    }
+    const long long need = afi_rpn_topk_wide_ws_floats(N, H, W, A);
+    if (!ws || ws_floats < need || ((uintptr_t)ws & 7)) return AFI_ERR_WORKSPACE;
+    int* hdr = (int*)ws;
+    u64* cand = (u64*)(hdr + (long long)N * RPN_HDR);
+    hipLaunchKernelGGL(afi_rpn_zero_kernel, dim3((N * RPN_HDR + 255) / 256), dim3(256), 0, st, hdr, N * RPN_HDR);
+    int gx = (n + 256 * 8 - 1) / (256 * 8);
+    if (gx > 512) gx = 512;
+    hipLaunchKernelGGL(afi_rpn_hist_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, hdr);
+    hipLaunchKernelGGL(afi_rpn_filter_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, k, hdr, cand);
+    hipLaunchKernelGGL(afi_rpn_pick_wide_kernel<false>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)hdr, (const u64*)cand, vals, idx,
+                       ld);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ NMS
+// The bit matrix in the workspace: per image k rows of nw = ceil(k / 64) words, mask[i][w] bit j as in afi_nms_kernel.  Build: one block per
+// 64 x 64 tile (column word w, row tile rt <= w) of the upper triangle, blockIdx.x = w (w + 1) / 2 + rt; a wave takes sixteen rows, a lane is a
+// column, a wave's __ballot is the word.  The overlap test is afi_nms_kernel's expression, restated (that kernel's code object stays as it is).
+__global__ __launch_bounds__(256) void afi_rpn_nms_build_kernel(const float* __restrict__ boxes, const int* __restrict__ valid, int k, long long ld,
+                                                                float thresh, u64* __restrict__ mask_all) {
+#pragma clang fp contract(off)                          // the overlap test is the stated fp32 expression, operation by operation
+    const int img = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nw = (k + 63) >> 6, t = blockIdx.x;
+    int w = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+    while ((w + 1) * (w + 2) / 2 <= t) ++w;
+    while (w * (w + 1) / 2 > t) --w;
+    const int rt = t - w * (w + 1) / 2;
+    if (w >= nw || rt > w) return;                      // (never: the grid is nw (nw + 1) / 2 wide)
+    const int j = 64 * w + lane;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool cok = false;
+    if (j < k) {
+        const float* q = boxes + 4 * ((long long)img * ld + j);
+        c = make_float4(q[0], q[1], q[2], q[3]);
+        cok = valid[(long long)img * ld + j] != 0;
+    }
+    const float carea = (c.z - c.x) * (c.w - c.y);
+    u64* mask = mask_all + (long long)img * k * nw;
+    const int i0 = 64 * rt + 16 * wave;
+    for (int s = 0; s < 16; ++s) {
+        const int i = i0 + s;
+        if (i >= k) break;
+        const float* q = boxes + 4 * ((long long)img * ld + i);
+        const float4 r = make_float4(q[0], q[1], q[2], q[3]);
+        const float iw = fmaxf(fminf(r.z, c.z) - fmaxf(r.x, c.x), 0.f), ih = fmaxf(fminf(r.w, c.w) - fmaxf(r.y, c.y), 0.f);
+        const float inter = iw * ih, rarea = (r.z - r.x) * (r.w - r.y);
+        const bool hit = cok && j > i && (inter / (rarea + carea - inter) > thresh);
+        const u64 word = __ballot(hit);
+        if (lane == 0) mask[(long long)i * nw + w] = word;
+    }
+}
+
+// One wave per image; lane w holds word w of the boxes suppressed so far.  Per chunk of 64 rows: the diagonal word resolved in registers as in
+// afi_nms_kernel, then the kept rows' words OR-ed in -- sixteen rows' loads issued together (a row is nw <= 64 words: one coalesced read), rows
+// of a group that were not kept are read and masked out, a group without a kept row is skipped.  Only words the build wrote are read: column
+// words w > c of rows 64 c .. min(64 c + 63, k - 1), and the diagonal words.
+__global__ __launch_bounds__(64) void afi_rpn_nms_sweep_kernel(const u64* __restrict__ mask_all, const int* __restrict__ valid, int k, long long ld,
+                                                               int* __restrict__ keep) {
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const int nw = (k + 63) >> 6;
+    const u64* mask = mask_all + (long long)img * k * nw;
+    u64 remv = 0;
+    for (int c = 0; c < nw; ++c) {
+        const int row = 64 * c + lane;
+        const u64 diag = (row < k) ? mask[(long long)row * nw + c] : 0ull;
+        const u64 V = __ballot(row < k && valid[(long long)img * ld + (row < k ? row : 0)] != 0);
+        u64 R = rpn_readlane64(remv, c) | ~V;           // an invalid box is neither kept nor suppresses anything
+        u64 K = 0;
+#pragma unroll
+        for (int b = 0; b < 64; ++b) {
+            if (!((R >> b) & 1ull)) {
+                K |= 1ull << b;
+                R |= rpn_readlane64(diag, b);
+            }
+        }
+        if (row < k) keep[(long long)img * ld + row] = (int)((K >> lane) & 1ull);
+        const bool mine = lane > c && lane < nw;
+        u64 acc = 0;
+        for (int g = 0; g < 64; g += 16) {
+            if (!mine || !((K >> g) & 0xFFFFull)) continue;
+            u64 v[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                int r = 64 * c + g + s;
+                r = r < k ? r : k - 1;                  // (a row past the list is never kept: its word is masked out below)
+                v[s] = mask[(long long)r * nw + lane];
+            }
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if ((K >> (g + s)) & 1ull) acc |= v[s];
+        }
+        remv |= acc;
+    }
+}
+
+long long afi_rpn_nms_wide_ws_floats(int N, int k) {
+    if (N <= 0 || k < 0 || k > RPN_MAXK_WIDE) return -1;
+    return 2ll * N * k * ((k + 63) / 64);
+}
+
+int afi_rpn_nms_wide(const float* boxes, const int* valid, int N, int k, long long ld, float thresh, int* keep, float* ws, long long ws_floats,
+                     void* stream) {
+    if (N <= 0 || N > 65535 || k < 0 || ld < k) return AFI_ERR_BAD_ARG;
+    if (k == 0) return AFI_OK;
+    if (!boxes || !valid || !keep) return AFI_ERR_BAD_ARG;
+    if (k > RPN_MAXK_WIDE) return AFI_ERR_UNSUPPORTED;
+    if (!ws || ws_floats < afi_rpn_nms_wide_ws_floats(N, k) || ((uintptr_t)ws & 7)) return AFI_ERR_WORKSPACE;
+    const int nw = (k + 63) / 64;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(afi_rpn_nms_build_kernel, dim3(nw * (nw + 1) / 2, N), dim3(256), 0, st, boxes, valid, k, ld, thresh, (u64*)ws);
+    hipLaunchKernelGGL(afi_rpn_nms_sweep_kernel, dim3(N), dim3(64), 0, st, (const u64*)ws, valid, k, ld, keep);
+    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------ merge
+// afi_rpn_merge_kernel with levels of up to RPN_MAXK_WIDE entries: the threads loop over a level's entries in chunks of 1024 (one block scan per
+// chunk), positions are 16 bits (RPN_WIDE_TOTAL < 65536).  The same order: logit descending, then level, then rank.
+__global__ __launch_bounds__(1024) void afi_rpn_merge_wide_kernel(const float* __restrict__ boxes, const float* __restrict__ vals,
+                                                                  const int* __restrict__ keep, const RpnLevels lv, int post_k,
+                                                                  float* __restrict__ ob, float* __restrict__ ol, int* __restrict__ counts) {
+    __shared__ unsigned ckey[RPN_WIDE_TOTAL];
+    __shared__ unsigned short cpos[RPN_WIDE_TOTAL];
+    __shared__ int cnt[RPN_MAX_LEVELS];
+    __shared__ int wtot[16];
+    const int img = blockIdx.x, tid = threadIdx.x, Ktot = lv.off[lv.L];
+    const long long row0 = (long long)img * Ktot;
+    for (int l = 0; l < lv.L; ++l) {
+        const int o = lv.off[l], kl = lv.off[l + 1] - o;
+        int base = 0;
+        for (int e0 = 0; e0 < kl; e0 += 1024) {
+            const int e = e0 + tid;
+            const int f = (e < kl) && keep[row0 + o + (e < kl ? e : 0)] != 0;
+            int tot;
+            const int inc = rpn_block_scan(f, wtot, &tot);
+            if (f) {
+                ckey[o + base + inc - 1] = rpn_key(vals[row0 + o + e]);
+                cpos[o + base + inc - 1] = (unsigned short)(o + e);
+            }
+            base += tot;
+        }
+        if (tid == 0) cnt[l] = base;
+    }
+    __syncthreads();
+    int total = 0;
+    for (int l = 0; l < lv.L; ++l) total += cnt[l];
+    for (int l = 0; l < lv.L; ++l) {
+        for (int e = tid; e < cnt[l]; e += 1024) {
+            const unsigned key = ckey[lv.off[l] + e];
+            int rank = e;
+            for (int b = 0; b < lv.L && rank < post_k; ++b) {
+                if (b == l) continue;
+                const unsigned* arr = ckey + lv.off[b];
+                int lo = 0, hi = cnt[b];
+                while (lo < hi) {                          // entries of level b in front: >= key for an earlier level, > key for a later one
+                    const int mid = (lo + hi) >> 1;
+                    const bool front = b < l ? arr[mid] >= key : arr[mid] > key;
+                    if (front) lo = mid + 1; else hi = mid;
+                }
+                rank += lo;
+            }
+            if (rank < post_k) {
+                const long long src = row0 + cpos[lv.off[l] + e], dst = (long long)img * post_k + rank;
+                const float* q = boxes + 4 * src;
+                float* p = ob + 4 * dst;
+                p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; p[3] = q[3];
+                ol[dst] = vals[src];
+            }
+        }
+    }
+    const int c = total < post_k ? total : post_k;
+    if (tid == 0) counts[img] = c;
+    for (int r = c + tid; r < post_k; r += 1024) {
+        const long long dst = (long long)img * post_k + r;
+        float* p = ob + 4 * dst;
+        p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; p[3] = 0.f;
+        ol[dst] = 0.f;
+    }
+}
+
+int afi_rpn_merge_wide(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                       float* out_logits, int* counts, void* stream) {
+    if (!boxes || !vals || !keep || !level_off || !out_boxes || !out_logits || !counts || N <= 0 || N > 65535 || L <= 0 || post_k <= 0)
+        return AFI_ERR_BAD_ARG;
+    if (L > RPN_MAX_LEVELS) return AFI_ERR_UNSUPPORTED;
+    RpnLevels lv;
+    lv.L = L;
+    if (level_off[0] != 0) return AFI_ERR_BAD_ARG;
+    for (int l = 0; l <= RPN_MAX_LEVELS; ++l) lv.off[l] = level_off[l < L ? l : L];
+    for (int l = 0; l < L; ++l) {
+        const int kl = level_off[l + 1] - level_off[l];
+        if (kl < 0) return AFI_ERR_BAD_ARG;
+        if (kl > RPN_MAXK_WIDE) return AFI_ERR_UNSUPPORTED;
+    }
+    if (level_off[L] <= 0) return AFI_ERR_BAD_ARG;
+    if (level_off[L] > RPN_WIDE_TOTAL) return AFI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(afi_rpn_merge_wide_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes,
+                       out_logits, counts);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }

@@ -1018,6 +1018,78 @@ def rpn_merge(boxes, vals, keep, level_off, post_k):
     return ob, ol, counts
 
 
+# The wide forms: per-level lists of 1025 .. 4096 (PRE_NMS_TOPK_TRAIN of the reference's base config is 2000).  RPN.select uses them for the
+# levels whose list is longer than RPN_MAX_TOPK; the functions above keep their limits.
+RPN_MAX_TOPK_WIDE = 4096                    # 64 x 64: the suppressed set of the NMS sweep is one 64-bit word per lane of a wave
+RPN_MAX_MERGE_WIDE = 5 * RPN_MAX_TOPK_WIDE  # entries of all levels of an image rpn_merge_wide holds
+
+
+def rpn_topk_wide(head, A, k, vals=None, idx=None):
+    """rpn_topk for RPN_MAX_TOPK < k <= RPN_MAX_TOPK_WIDE: the same order, tie rule, NaN rule and output layout (afi_rpn_topk_wide).  A k of
+    at most RPN_MAX_TOPK is rpn_topk's and is refused here."""
+    _check_cuda(head)
+    N, Cp, H, W = head.shape
+    if not 0 < A <= min(Cp, RPN_MAX_ANCHORS) or not RPN_MAX_TOPK < k <= min(RPN_MAX_TOPK_WIDE, H * W * A):
+        raise _lib.AfiError(f"rpn_topk_wide: A {A} (1..{min(Cp, RPN_MAX_ANCHORS)}), k {k} ({RPN_MAX_TOPK + 1}..{min(RPN_MAX_TOPK_WIDE, H * W * A)}) "
+                            f"for a head of shape {tuple(head.shape)}")
+    if vals is None:
+        vals = torch.empty((N, k), device=head.device, dtype=torch.float32)
+        idx = torch.empty((N, k), device=head.device, dtype=torch.int32)
+    _check_cuda(vals)
+    _check_i32(idx)
+    ld = _rpn_rows(vals, k)
+    if vals.shape[0] != N or idx.shape[0] != N or _rpn_rows(idx, k) != ld:
+        raise _lib.AfiError("rpn_topk_wide: vals and idx must be [N, >= k] with one row stride")
+    n = _lib.load().afi_rpn_topk_wide_ws_floats(N, H, W, A)
+    if n < 0:
+        raise _lib.AfiError(f"rpn_topk_wide: unsupported map {H}x{W}x{A}")
+    ws = new_workspace(n, head.device) if n else None
+    call("afi_rpn_topk_wide", view_of(head), N, H, W, A, k, _p(vals), _p(idx), ld, _p(ws), n, stream_ptr())
+    return vals, idx
+
+
+def rpn_nms_wide(boxes, valid, thresh, keep=None):
+    """rpn_nms for lists of up to RPN_MAX_TOPK_WIDE boxes, the suppression bit matrix in a workspace (afi_rpn_nms_wide).  For k <= RPN_MAX_TOPK
+    the keep set is rpn_nms's."""
+    _check_cuda(boxes)
+    _check_i32(valid)
+    N, k = valid.shape
+    if keep is None:
+        keep = torch.empty((N, k), device=boxes.device, dtype=torch.int32)
+    _check_i32(keep)
+    if k > RPN_MAX_TOPK_WIDE:
+        raise _lib.AfiError(f"rpn_nms_wide: lists of at most {RPN_MAX_TOPK_WIDE} boxes, got {k}")
+    if k == 0:
+        return keep
+    ld = _rpn_rows(valid, k)
+    if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(keep, k) != ld or not (boxes.shape[0] == keep.shape[0] == N):
+        raise _lib.AfiError("rpn_nms_wide: boxes, valid and keep must be lists of one row stride")
+    n = _lib.load().afi_rpn_nms_wide_ws_floats(N, k)
+    ws = new_workspace(n, boxes.device)
+    call("afi_rpn_nms_wide", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), _p(ws), n, stream_ptr())
+    return keep
+
+
+def rpn_merge_wide(boxes, vals, keep, level_off, post_k):
+    """rpn_merge with levels of up to RPN_MAX_TOPK_WIDE entries, at most RPN_MAX_MERGE_WIDE over all levels (afi_rpn_merge_wide)."""
+    _check_cuda(boxes, vals)
+    _check_i32(keep)
+    N, K = vals.shape
+    L = len(level_off) - 1
+    if not (boxes.is_contiguous() and vals.is_contiguous() and keep.is_contiguous()) or tuple(boxes.shape) != (N, K, 4) or tuple(keep.shape) != (N, K) \
+            or level_off[0] != 0 or level_off[-1] != K or not 0 < L <= RPN_MAX_LEVELS or post_k <= 0:
+        raise _lib.AfiError(f"rpn_merge_wide: dense boxes [N, K, 4], vals / keep [N, K] and 1..{RPN_MAX_LEVELS} levels ending at K expected, got "
+                            f"{tuple(boxes.shape)}, {tuple(vals.shape)}, {tuple(keep.shape)}, offsets {list(level_off)}")
+    if K > RPN_MAX_MERGE_WIDE or any(level_off[l + 1] - level_off[l] > RPN_MAX_TOPK_WIDE for l in range(L)):
+        raise _lib.AfiError(f"rpn_merge_wide: levels of at most {RPN_MAX_TOPK_WIDE} entries, {RPN_MAX_MERGE_WIDE} in all; got offsets {list(level_off)}")
+    ob = torch.empty((N, post_k, 4), device=boxes.device, dtype=torch.float32)
+    ol = torch.empty((N, post_k), device=boxes.device, dtype=torch.float32)
+    counts = torch.empty((N,), device=boxes.device, dtype=torch.int32)
+    off = (C.c_int * (L + 1))(*[int(o) for o in level_off])
+    call("afi_rpn_merge_wide", _p(boxes), _p(vals), _p(keep), N, L, off, int(post_k), _p(ob), _p(ol), _p(counts), stream_ptr())
+    return ob, ol, counts
+
+
 # ------------------------------------------------------------------------------------------------ RPN training (rpn.py: RPN.losses)
 RPN_MAX_TOTAL_ANCHORS = 1 << 22             # anchors of one image over all levels: an index is 22 bits of a select word
 RPN_MAX_GT = 1024                           # ground-truth boxes per image (four LDS tiles of 256)

@@ -17,7 +17,9 @@ detectron2's, so a detector checkpoint's ``proposal_generator.*`` loads with str
 
 Kernels: the 3x3 conv + ReLU is afi_conv3x3_wino_infer / afi_conv3x3_fwd (the regime rule of frozen.conv3x3), the two 1x1 convs ONE
 afi_conv1x1_fwd over their concatenated weights (A + 4A channels, zero-padded to a multiple of 4; rebuilt when a parameter changes:
-frozen.prepared); selection afi_rpn_topk, afi_rpn_decode, afi_rpn_nms per level and one afi_rpn_merge (csrc/rpn.hip).  No torch sort / topk /
+frozen.prepared); selection afi_rpn_topk, afi_rpn_decode, afi_rpn_nms per level and one afi_rpn_merge (csrc/rpn.hip); a level whose list is
+longer than 1024 (training: PRE_NMS_TOPK_TRAIN up to 4096) runs afi_rpn_topk_wide / afi_rpn_nms_wide, and the merge is then
+afi_rpn_merge_wide.  No torch sort / topk /
 conv, MIOpen or hipBLASLt kernel runs.  ``forward_padded`` has no host read and can be captured in a hipGraph; ``forward`` reads ``counts`` once.
 
 Training (``RPN.losses``, and ``forward`` in training mode with ``gt_instances``): RPNOutputs._get_ground_truth, subsample_labels, get_deltas
@@ -26,7 +28,7 @@ weight-gradient entry points (``_RPNLossFn``).  The sample is decided by 32-bit 
 torch's generator unless given: uniform, but not ``randperm``'s stream.  ``trainable_()`` makes the six parameters trainable.
 
 Out of scope (AfiError): a training-mode call without ``gt_instances``, ``gt_instances`` in eval mode, BOUNDARY_THRESH other than -1,
-IOU_LABELS other than [0, -1, 1], PRE_NMS_TOPK_TRAIN above 1024 (for proposals; the losses do not need it), more than 1024 ground-truth boxes
+IOU_LABELS other than [0, -1, 1], PRE_NMS_TOPK_TRAIN above 4096 (for proposals; the losses do not need it), more than 1024 ground-truth boxes
 per image or 2^22 anchors, rotated anchors, heads other than StandardRPNHead, PRE_NMS_TOPK_TEST above 1024, more than 16 anchors per cell,
 more than 8 levels, CPU tensors, 2-byte features."""
 import math
@@ -339,7 +341,9 @@ class RPN(nn.Module):
     def select(self, heads, image_hw, pre_k=None, post_k=None):
         """top-k, decode, NMS per level and the merge, on the head outputs; image_hw [N, 2] fp32 on the device.  Returns a dict with the padded
         result (boxes [N, post_k, 4], logits [N, post_k], counts [N] int32) and the stages' own outputs with the levels side by side
-        (level_off, vals / idx / valid / keep [N, K], level_boxes [N, K, 4]).  pre_k / post_k: the *_TEST values unless given."""
+        (level_off, vals / idx / valid / keep [N, K], level_boxes [N, K, 4]).  pre_k / post_k: the *_TEST values unless given.  A level whose
+        list min(pre_k, H W A) is longer than ops.RPN_MAX_TOPK (up to ops.RPN_MAX_TOPK_WIDE) runs the wide top-k and NMS, and the merge is then
+        the wide one; every other level runs the calls it always ran."""
         A, N, dev = self.num_anchors, heads[0].shape[0], heads[0].device
         pre_k, post_k = pre_k or self.pre_nms_topk, post_k or self.post_nms_topk
         ks = [min(pre_k, o.shape[2] * o.shape[3] * A) for o in heads]
@@ -354,11 +358,13 @@ class RPN(nn.Module):
         keep = torch.empty((N, K), device=dev, dtype=torch.int32)
         for l, (o, k) in enumerate(zip(heads, ks)):
             s = slice(off[l], off[l + 1])
-            ops.rpn_topk(o, A, k, vals[:, s], idx[:, s])
+            wide = k > ops.RPN_MAX_TOPK                      # a list the LDS-resident kernels cannot hold: the wide forms, this level only
+            (ops.rpn_topk_wide if wide else ops.rpn_topk)(o, A, k, vals[:, s], idx[:, s])
             ops.rpn_decode(o, A, A, self.anchor_generator.cell_anchors[l], self.anchor_generator.strides[l], idx[:, s], k, image_hw,
                            self.box_weights, SCALE_CLAMP, self.min_box_side_len, boxes[:, s], valid[:, s])
-            ops.rpn_nms(boxes[:, s], valid[:, s], self.nms_thresh, keep[:, s])
-        ob, ol, counts = ops.rpn_merge(boxes, vals, keep, off, post_k)
+            (ops.rpn_nms_wide if wide else ops.rpn_nms)(boxes[:, s], valid[:, s], self.nms_thresh, keep[:, s])
+        merge = ops.rpn_merge_wide if max(ks) > ops.RPN_MAX_TOPK else ops.rpn_merge
+        ob, ol, counts = merge(boxes, vals, keep, off, post_k)
         return {"boxes": ob, "logits": ol, "counts": counts, "level_off": off, "vals": vals, "idx": idx, "level_boxes": boxes, "valid": valid,
                 "keep": keep}
 
@@ -411,10 +417,12 @@ class RPN(nn.Module):
         return self._losses_and_heads(features, gt_instances, keys)[0]
 
     def _forward_train(self, images, features, gt_instances, keys=None):
-        if self.pre_nms_topk_train > ops.RPN_MAX_TOPK:
-            raise AfiError(f"rpn: MODEL.RPN.PRE_NMS_TOPK_TRAIN {self.pre_nms_topk_train} is above {ops.RPN_MAX_TOPK}, the per-level list the "
-                           "selection kernels hold, so a training-mode forward cannot make proposals (the reference's base config sets 2000).  "
-                           "RPN.losses() works regardless; raising the selection's capacity is a separate piece of work")
+        if self.pre_nms_topk_train > ops.RPN_MAX_TOPK_WIDE:
+            raise AfiError(f"rpn: MODEL.RPN.PRE_NMS_TOPK_TRAIN {self.pre_nms_topk_train} is above both {ops.RPN_MAX_TOPK}, the per-level list the "
+                           f"selection kernels hold in LDS, and {ops.RPN_MAX_TOPK_WIDE}, the list their wide forms hold through a workspace, so a "
+                           "training-mode forward cannot make proposals (the reference's base config sets 2000, which runs; detectron2's default "
+                           "is 12000).  RPN.losses() works regardless; lists above "
+                           f"{ops.RPN_MAX_TOPK_WIDE} are a separate piece of work")
         if self.post_nms_topk_train <= 0 or self.pre_nms_topk_train <= 0:
             raise AfiError(f"rpn: MODEL.RPN.PRE_NMS_TOPK_TRAIN / POST_NMS_TOPK_TRAIN {self.pre_nms_topk_train} / {self.post_nms_topk_train} must be positive")
         losses, heads = self._losses_and_heads(features, gt_instances, keys)

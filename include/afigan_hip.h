@@ -618,6 +618,24 @@ int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld
 int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
                   float* out_logits, int* counts, void* stream);
 
+/* The wide forms of the three selection stages: per-level lists of up to 4096 entries (the reference's training configs set
+ * PRE_NMS_TOPK_TRAIN 2000).  Same rules, layouts, status codes and determinism as the entry points above; no host synchronisation.
+ * afi_rpn_topk_wide: afi_rpn_topk for 1024 < k <= 4096, k <= H W A (k <= 1024 is afi_rpn_topk's: AFI_ERR_UNSUPPORTED here, as is k > 4096).
+ *   ws: afi_rpn_topk_wide_ws_floats(N, H, W, A) floats, 8-byte aligned (0: none needed; -1: unsupported) -- the size afi_rpn_topk needs.
+ * afi_rpn_nms_wide: afi_rpn_nms for 0 <= k <= 4096 with the suppression bit matrix in ws: afi_rpn_nms_wide_ws_floats(N, k) =
+ *   2 N k ceil(k / 64) floats, 8-byte aligned (-1: k > 4096).  The workspace need not be initialised: only words written by the call are read.
+ *   For k <= 1024 the keep set is afi_rpn_nms's.
+ * afi_rpn_merge_wide: afi_rpn_merge with levels of up to 4096 entries and level_off[L] <= 20480 (5 x 4096: the keys and positions of all
+ *   levels are held in LDS) -- AFI_ERR_UNSUPPORTED above either. */
+long long afi_rpn_topk_wide_ws_floats(int N, int H, int W, int A);
+int afi_rpn_topk_wide(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                      void* stream);
+long long afi_rpn_nms_wide_ws_floats(int N, int k);
+int afi_rpn_nms_wide(const float* boxes, const int* valid, int N, int k, long long ld, float thresh, int* keep, float* ws, long long ws_floats,
+                     void* stream);
+int afi_rpn_merge_wide(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                       float* out_logits, int* counts, void* stream);
+
 /* ------------------------------------------------------------------ RPN training: labels, sampling, losses (afigan_amd/rpn.py: RPN.losses)
  * detectron2 v0.1.1's RPNOutputs._get_ground_truth (Matcher with low-quality matches), subsample_labels, Box2BoxTransform.get_deltas and
  * rpn_losses.  The levels of an image are concatenated in the order given: level_hw = HOST array {H_0, W_0, H_1, ...}, strides = HOST array of L
