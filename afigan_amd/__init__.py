@@ -37,5 +37,6 @@ from .rle import from_polygons as polygons_to_rle  # noqa: E402
 from .coco_eval import COCOEvaluator  # noqa: E402
 from .rcnn_extractor import GeneralizedRCNN_AFExtractor, META_ARCH_REGISTRY  # noqa: E402
 from .config import add_afigan_config, get_cfg  # noqa: E402
+from .detector_optim import DetectorOptim, DetectorStep, GeneralizedRCNN, build_detector_optimizer  # noqa: E402
 
-__all__ = ["Generator", "Discriminator", "Stage1Step", "GuidePrefetcher", "warmup_multistep_lr", "FPN_AFIGAN", "PAFPN_AFIGAN", "BiFPN_AFIGAN", "LastLevelP6P7", "LastLevelMaxPool", "Stage2Adversarial", "l1_loss_common", "nearest_half", "DualScaleMapper", "preprocess_images", "ops", "AfiError", "compute_dtype", "BACKBONE_REGISTRY", "GUIDE_ARCH_REGISTRY", "build_guide_model", "RCNN_FPN_only", "GeneralizedRCNN_AFExtractor", "META_ARCH_REGISTRY", "Stage2Step", "add_afigan_config", "get_cfg", "RPN", "PROPOSAL_GENERATOR_REGISTRY", "build_proposal_generator", "StandardROIHeads", "ROIPooler", "FastRCNNConvFCHead", "FastRCNNOutputLayers", "ROI_HEADS_REGISTRY", "build_roi_heads", "MaskRCNNConvUpsampleHead", "paste_masks_in_image", "CascadeROIHeads", "paste_masks_rle", "instances_to_coco_json", "rle", "COCOEvaluator", "polygons_to_rle"]
+__all__ = ["Generator", "Discriminator", "Stage1Step", "GuidePrefetcher", "warmup_multistep_lr", "FPN_AFIGAN", "PAFPN_AFIGAN", "BiFPN_AFIGAN", "LastLevelP6P7", "LastLevelMaxPool", "Stage2Adversarial", "l1_loss_common", "nearest_half", "DualScaleMapper", "preprocess_images", "ops", "AfiError", "compute_dtype", "BACKBONE_REGISTRY", "GUIDE_ARCH_REGISTRY", "build_guide_model", "RCNN_FPN_only", "GeneralizedRCNN_AFExtractor", "META_ARCH_REGISTRY", "Stage2Step", "add_afigan_config", "get_cfg", "RPN", "PROPOSAL_GENERATOR_REGISTRY", "build_proposal_generator", "StandardROIHeads", "ROIPooler", "FastRCNNConvFCHead", "FastRCNNOutputLayers", "ROI_HEADS_REGISTRY", "build_roi_heads", "MaskRCNNConvUpsampleHead", "paste_masks_in_image", "CascadeROIHeads", "paste_masks_rle", "instances_to_coco_json", "rle", "COCOEvaluator", "polygons_to_rle", "DetectorOptim", "DetectorStep", "GeneralizedRCNN", "build_detector_optimizer"]

@@ -79,6 +79,11 @@ class UnfoldDesc(C.Structure):
     _fields_ = [("dw", C.c_void_p), ("grad", C.c_void_p), ("s", C.c_void_p), ("O", C.c_int), ("I", C.c_int), ("k", C.c_int), ("pad_", C.c_int)]
 
 
+class DetSgdDesc(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float),
+                ("fold_out", C.c_void_p), ("s64", C.c_void_p), ("O", C.c_int), ("I", C.c_int), ("k", C.c_int), ("pad_", C.c_int)]
+
+
 # the C types of the header -> ctypes.  Every other POINTER (and an array parameter such as `const int F[4]`) is a c_void_p: the header
 # cannot tell a host array from a device pointer, and c_void_p takes a ctypes array, byref(...), an integer address or None alike.
 _CTYPES = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "afi_view_t": View,

@@ -84,6 +84,15 @@ def prepared(module, name, tensors, build):
     return getattr(module, f"_{name}")
 
 
+def adopt_prepared(module, name, tensors):
+    """Re-key the existing ``_<name>`` slot of `module` to the CURRENT versions of `tensors` without rebuilding it: for a caller that has just
+    written both sides itself -- the tensors and, consistently, what the slot holds (detector_optim: the update and the refold are one
+    kernel).  The slot must exist and have been current before those writes; nothing here can check that."""
+    if not hasattr(module, f"_{name}_key"):
+        raise AfiError(f"adopt_prepared: {type(module).__name__} has no prepared slot {name!r} to adopt (prepared() builds it first)")
+    setattr(module, f"_{name}_key", tuple((t._version, t.data_ptr(), str(t.device)) for t in tensors))
+
+
 def check_forward_only(module, x, what):
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
         raise AfiError(f"{what} is forward-only (frozen): run it under torch.no_grad() with no parameter or input requiring grad")

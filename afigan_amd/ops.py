@@ -544,6 +544,31 @@ def frozen_wgrad_unfold(descs):
     call("afi_frozen_wgrad_unfold", _p(table_dev), len(descs), max_oi, stream_ptr())
 
 
+def detector_sgd_units(n, O=0, I=0, k=0, fold=False):
+    """The number of work units afi_detector_sgd_step cuts a tensor into (afi_detector_sgd_units)."""
+    return int(_lib.load().afi_detector_sgd_units(int(n), int(O), int(I), int(k), int(bool(fold))))
+
+
+def detector_sgd_step(table, device, momentum, gscale=1.0, flat=False, units=None):
+    """One afi_detector_sgd_step launch over `table`, a ctypes array of _lib.DetSgdDesc (device pointers; see include/afigan_hip.h): SGD with
+    momentum and per-tensor lr / weight decay, and the FrozenBN refold of the entries with a ``fold_out``.  `flat`: the flat grid over all work
+    units, else the (<= 512, ntensors) grid.  `units`: the entries' unit counts if the caller keeps them (detector_sgd_units otherwise).
+    The table (and the flat grid's unit prefix behind it) goes to the device in one copy."""
+    nt = len(table)
+    if nt == 0:
+        return
+    if units is None:
+        units = [detector_sgd_units(d.n, d.O, d.I, d.k, bool(d.fold_out)) if d.n > 0 else 0 for d in table]
+    raw = bytes(table)
+    if flat:
+        raw += b"\0" * (-len(raw) % 16)
+        prefix = len(raw)
+        raw += np.concatenate([[0], np.cumsum(units)]).astype(np.int32).tobytes()
+    buf = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+    unit_off = C.c_void_p(buf.data_ptr() + prefix) if flat else C.c_void_p(None)
+    call("afi_detector_sgd_step", table, _p(buf), nt, max(units), unit_off, sum(units), float(momentum), float(gscale), stream_ptr())
+
+
 def bias_grad(dy):
     """Column sums of a dense pixel-major gradient: d/d bias of a conv."""
     assert is_dense_pm(dy)

@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import _lib, ops, registry
 from ._lib import AfiError
 from .fpn_sr import ShapeSpec
-from .frozen import FROZEN_BN_EPS, Conv2d, FrozenBatchNorm2d, cfg_get, check_forward_only, conv1x1, conv3x3, prepared  # noqa: F401
+from .frozen import FROZEN_BN_EPS, Conv2d, FrozenBatchNorm2d, adopt_prepared, cfg_get, check_forward_only, conv1x1, conv3x3, prepared  # noqa: F401
 from .rpn import _wino
 
 _BLOCKS = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}
@@ -41,10 +41,12 @@ class _Frozen(nn.Module):
     def _fold_own(self, convs):
         return {id(m): m.fold() for m in convs}
 
+    def _prepare_tensors(self, convs):
+        return [t for m in convs for t in list(m.parameters()) + list(m.buffers())]
+
     def _prepare(self):
         convs = self._own_convs()
-        ts = [t for m in convs for t in list(m.parameters()) + list(m.buffers())]
-        return prepared(self, "folded", ts, lambda: self._fold_own(convs))
+        return prepared(self, "folded", self._prepare_tensors(convs), lambda: self._fold_own(convs))
 
 
 class BasicStem(nn.Module):
@@ -340,6 +342,24 @@ class ResNet(ResNetBase):
         ts = [t for c in convs for t in c.norm.buffers()]
         return prepared(self, "bn_scales", ts, lambda: {
             id(c): (c.norm.weight.double() * torch.rsqrt(c.norm.running_var.double() + c.norm.eps)).float().contiguous() for c in convs})
+
+    def _fold_scales64(self):
+        """`_fold_scales` before its rounding: frozen.fold_conv's own fp64 expression, what the fold multiplies the weight by."""
+        convs = self._train_convs()
+        ts = [t for c in convs for t in c.norm.buffers()]
+        return prepared(self, "bn_scales64", ts, lambda: {
+            id(c): (c.norm.weight.double() * torch.rsqrt(c.norm.running_var.double() + c.norm.eps)).contiguous() for c in convs})
+
+    def fold_slots(self):
+        """[(weight parameter, fp64 fold scale [O], folded weight)] per trainable conv: the folded weight is the tensor that lives in the
+        ``_prepare()`` dict ([O, I] for a 1x1, [O, I, 3, 3] in [O][kh][kw][I] memory for a 3x3), so a writer that keeps it equal to
+        ``fold_conv`` of the parameter (afi_detector_sgd_step) and then calls ``adopt_folded`` spares the next forward the refold."""
+        f, s = self._prepare(), self._fold_scales64()
+        return [(c.weight, s[id(c)], f[id(c)][0]) for c in self._train_convs()]
+
+    def adopt_folded(self):
+        """The ``_prepare()`` dict is current for the parameters as they are now (frozen.adopt_prepared): only for the writer `fold_slots` names."""
+        adopt_prepared(self, "folded", self._prepare_tensors(self._own_convs()))
 
     def _forward_train(self, x):
         if not x.is_cuda:

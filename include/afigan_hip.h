@@ -495,6 +495,27 @@ int afi_scale_inplace(float* p, long long n, float s, void* stream);
 typedef struct afi_unfold_desc { const float* dw; float* grad; const float* s; int O; int I; int k; int pad_; } afi_unfold_desc_t;
 int afi_frozen_wgrad_unfold(const afi_unfold_desc_t* descs_dev, int ntensors, long long max_oi, void* stream);
 
+/* The detector's optimiser step (afigan_amd/detector_optim.py): torch.optim.SGD as detectron2 v0.1.1's build_optimizer configures it, for every
+ * trainable tensor in one launch, with the FrozenBN refold of the trainable frozen.Conv2d weights in the same pass.  Per element, in fp32:
+ *   d = fmaf(wd, p, g * gscale);  m = fmaf(momentum, m, d);  p = fmaf(-lr, m, p)          lr and wd per tensor
+ * p, g, m: n dense floats in one memory order (the parameter's own); 16-byte accesses where the three pointers allow, scalar otherwise.
+ * A fold entry (fold_out != NULL; a contiguous [O][I][k][k] weight, k 1 or 3, n = O I k k) also gets
+ *   fold_out = (float)((double)p_new * s64[o])      s64: DEVICE fp64 [O], gamma / sqrt(var + eps) of the conv's FrozenBN
+ * written as [O][I] for k = 1 and as the kernels' [O][kh][kw][I] for k = 3: one fp64 product rounded once, frozen.fold_conv's expression.
+ * The table is given twice: descs_host is checked (AFI_ERR_BAD_ARG: a null table, ntensors <= 0 or > 65535, a live entry without p, g or m, a
+ * fold entry without s64, with k other than 1 or 3, or with n != O I k k), descs_dev is what the kernel reads.  n == 0 entries are skipped.
+ * Work is cut into units, afi_detector_sgd_units per tensor (4096 elements; 4 pieces of one output channel x 32 input channels of a k = 3 fold
+ * entry).  unit_off_dev == NULL: a (min(512, max_units), ntensors) grid, max_units the largest unit count of the table.  Otherwise a flat grid
+ * of min(2048, total_units) blocks over all units, unit_off_dev a DEVICE int [ntensors + 1] = the exclusive prefix of the unit counts and
+ * total_units its last element.  One owner per element, no atomics: results are bit-identical between runs and between the two grids. */
+typedef struct afi_det_sgd_desc {
+    float* p; const float* g; float* m; long long n; float lr; float wd;
+    float* fold_out; const double* s64; int O; int I; int k; int pad_;
+} afi_det_sgd_desc_t;
+long long afi_detector_sgd_units(long long n, int O, int I, int k, int fold);
+int afi_detector_sgd_step(const afi_det_sgd_desc_t* descs_host, const afi_det_sgd_desc_t* descs_dev, int ntensors, long long max_units,
+                          const int* unit_off_dev, long long total_units, float momentum, float gscale, void* stream);
+
 /* layout changes at the detectron2 boundary: [N][C][P] <-> [N][P][C] */
 int afi_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, void* stream);
 int afi_nhwc_to_nchw(const float* in, float* out, int N, int C, int P, void* stream);
