@@ -18,6 +18,7 @@
 #include "../../include/afigan_hip.h"
 #include "afi_common.h"
 #include "afi_select.h"
+#include "afi_roi_decode.h"
 
 #define ROI_MAX_LEVELS 8
 #define ROI_MAX_S 14
@@ -137,82 +138,7 @@ int afi_roi_align(const afi_view_t* levels, const int* level_hw, int L, int min_
 }
 
 // ------------------------------------------------------------------------------------------------ scores and boxes
-struct RoiDecode {
-    int N, P, K, agnostic;
-    long long ld;
-    float wx, wy, ww, wh;
-    double clamp;
-};
-
-__device__ __forceinline__ double roi_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double roi_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The running score of the cascade: (prev + s) and then, when out_scale != 1, the product with out_scale -- one fp32 operation each.
-__device__ __forceinline__ float roi_running_score(float s, const float* prev, float out_scale) {
-#pragma clang fp contract(off)
-    float v = prev ? *prev + s : s;               // (the lane reads its own element before it writes it: scores may be prev_scores)
-    if (out_scale != 1.f) v = v * out_scale;
-    return v;
-}
-
-// One wave per row r = n P + j; lane c, c + 64, ...: class c.  CASCADE: the scores go through roi_running_score (d.agnostic is 1 there).
-template <bool CASCADE>
-__device__ __forceinline__ void roi_scores_boxes_row(const RoiDecode& d, const float* pred, const float* proposals, const int* counts,
-                                                     const float* image_hw, const float* prev, float out_scale, float* scores, float* boxes) {
-    const int lane = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (long long)d.N * d.P) return;
-    const int n = (int)(row / d.P), j = (int)(row - (long long)n * d.P), K = d.K, Kb = d.agnostic ? 1 : K;
-    float* sc = scores + row * K;
-    float* bx = boxes + row * Kb * 4;
-    const float* pv = CASCADE && prev ? prev + row * K : nullptr;
-    if (j >= counts[n]) {
-        for (int c = lane; c < K; c += 64) sc[c] = CASCADE ? roi_running_score(-INFINITY, pv ? pv + c : nullptr, out_scale) : -INFINITY;
-        for (int c = lane; c < 4 * Kb; c += 64) bx[c] = 0.f;
-        return;
-    }
-    const float* q = pred + row * d.ld;
-    double m = -INFINITY;
-    bool bad = false;
-    for (int c = lane; c <= K; c += 64) {
-        const float l = q[c];
-        bad |= l != l;
-        m = fmax(m, (double)l);
-    }
-    m = roi_wave_max(m);
-    bad = __any(bad);
-    double s = 0.0;
-    for (int c = lane; c <= K; c += 64) s += exp((double)q[c] - m);
-    s = roi_wave_sum(s);
-    const double px1 = (double)proposals[4 * row], py1 = (double)proposals[4 * row + 1], px2 = (double)proposals[4 * row + 2],
-                 py2 = (double)proposals[4 * row + 3];
-    const double w = px2 - px1, h = py2 - py1, cx = px1 + 0.5 * w, cy = py1 + 0.5 * h;
-    const float ih = image_hw[2 * n], iw = image_hw[2 * n + 1];
-    const float* dl = q + K + 1;
-    for (int c = lane; c < K; c += 64) {
-        const float sv = bad ? __builtin_nanf("") : (float)(exp((double)q[c] - m) / s);
-        sc[c] = CASCADE ? roi_running_score(sv, pv ? pv + c : nullptr, out_scale) : sv;
-        if (c < Kb) {
-            const float* t = dl + 4 * c;
-            const double dx = (double)t[0] / (double)d.wx, dy = (double)t[1] / (double)d.wy;
-            const double dw = fmin((double)t[2] / (double)d.ww, d.clamp), dh = fmin((double)t[3] / (double)d.wh, d.clamp);
-            const double pcx = dx * w + cx, pcy = dy * h + cy, pw = exp(dw) * w, ph = exp(dh) * h;
-            float* o = bx + 4 * c;
-            o[0] = fminf(fmaxf((float)(pcx - 0.5 * pw), 0.f), iw);
-            o[1] = fminf(fmaxf((float)(pcy - 0.5 * ph), 0.f), ih);
-            o[2] = fminf(fmaxf((float)(pcx + 0.5 * pw), 0.f), iw);
-            o[3] = fminf(fmaxf((float)(pcy + 0.5 * ph), 0.f), ih);
-        }
-    }
-}
+// (RoiDecode, the softmax / decode row code roi_scores_boxes_row and its helpers: afi_roi_decode.h, shared with cascade_train.hip)
 
 __global__ __launch_bounds__(256) void afi_roi_scores_boxes_kernel(const RoiDecode d, const float* __restrict__ pred,
                                                                    const float* __restrict__ proposals, const int* __restrict__ counts,

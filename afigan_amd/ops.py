@@ -1945,3 +1945,114 @@ def l1_crop(a, b, loss, lscale=1.0, gscale=1.0, want_grad=True):
     da = new_pixel_major(N, C_, Ha, Wa, a.device) if want_grad else None
     call("afi_l1_fwd_bwd", view_of(a), view_of(b), N, h, w, C_, Ha, Wa, float(lscale), _p(loss), float(gscale), _p(da), stream_ptr())
     return da
+
+
+# ------------------------------------------------------------------------------------------------ CascadeROIHeads in training (roi_heads.py)
+def roi_cascade_relabel(pred, K, proposals, counts, image_hw, weights, gt, gt_classes, counts_g, iou_thresh, scale_clamp=4.135166556742356):
+    """The next cascade stage's training list from stage k's predictor output pred [N B, Cpad] and its boxes proposals [N, B, 4] / counts [N]
+    (detectron2's _create_proposals_from_boxes + _match_and_label_boxes): decode and clip as roi_cascade_stage does, drop the boxes that
+    clipped to empty keeping the order, match the rest to gt [N, Gmax, 4] / gt_classes [N, Gmax] / counts_g [N] at iou_thresh.  Returns a
+    dict: boxes [N, B, 4], counts [N], gt_classes [N, B] int32 (K = background, -1 past counts), gt_boxes [N, B, 4], src [N, B] int32 (the
+    input row, -1 past counts), matched_idx [N, B] int32 (afi_roi_cascade_relabel)."""
+    p2, N, B = _roi_pred_rows("roi_cascade_relabel", pred, K, 1, proposals, counts, image_hw)
+    if gt.dim() != 3 or gt.shape[0] != N or gt.shape[2] != 4 or gt.shape[1] < 1 or not gt.is_contiguous() \
+            or tuple(gt_classes.shape) != tuple(gt.shape[:2]) or not gt_classes.is_contiguous() or tuple(counts_g.shape) != (N,) \
+            or not counts_g.is_contiguous():
+        raise _lib.AfiError(f"roi_cascade_relabel: dense ground truth [{N}, Gmax >= 1, 4], gt_classes [{N}, Gmax] and counts_g [{N}] expected, "
+                            f"got {tuple(gt.shape)}, {tuple(gt_classes.shape)}, {tuple(counts_g.shape)}")
+    if gt.shape[1] > RPN_MAX_GT:
+        raise _lib.AfiError(f"roi_cascade_relabel: {gt.shape[1]} ground-truth boxes per image; at most {RPN_MAX_GT} are supported")
+    if B > RPN_MAX_BATCH:
+        raise _lib.AfiError(f"roi_cascade_relabel: lists of {B} rows per image; at most {RPN_MAX_BATCH} are supported")
+    _check_cuda(gt)
+    _check_i32(gt_classes, counts_g)
+    if not float(iou_thresh) == float(iou_thresh):
+        raise _lib.AfiError("roi_cascade_relabel: the IoU threshold is NaN")
+    dev, Gmax = pred.device, gt.shape[1]
+    r = {"boxes": torch.empty((N, B, 4), device=dev, dtype=torch.float32), "counts": torch.empty((N,), device=dev, dtype=torch.int32),
+         "gt_classes": torch.empty((N, B), device=dev, dtype=torch.int32), "gt_boxes": torch.empty((N, B, 4), device=dev, dtype=torch.float32),
+         "src": torch.empty((N, B), device=dev, dtype=torch.int32), "matched_idx": torch.empty((N, B), device=dev, dtype=torch.int32)}
+    call("afi_roi_cascade_relabel", _p(p2), p2.stride(0), N, B, int(K), _p(proposals.contiguous()), _p(counts.contiguous()),
+         _p(image_hw.contiguous()), *[float(w) for w in weights], float(scale_clamp), _p(gt), _p(gt_classes), _p(counts_g), Gmax, float(iou_thresh),
+         _p(r["boxes"]), _p(r["counts"]), _p(r["gt_classes"]), _p(r["gt_boxes"]), _p(r["src"]), _p(r["matched_idx"]), stream_ptr())
+    return r
+
+
+ROI_BN_MAX_IMAGES = 1024                    # CT_MAX_N: the list-masked passes walk the counts of every image in every thread
+
+
+def _roi_bn_list(name, x, counts, *same, vectors=()):
+    """The checks of the list-masked BatchNorm passes: x (and every tensor of `same`) is the dense rows [N B, P1, C] or their pixel-major
+    form [N B, C, S, S]; counts [N] int32; `vectors` are dense fp32 [C].  Shapes and limits first, then devices and dtypes.  Returns
+    (N, B, P1, C)."""
+    dense = x.is_contiguous() if x.dim() == 3 else is_dense_pm(x)
+    if x.dim() not in (3, 4) or not dense or counts.dim() != 1 or counts.shape[0] < 1 or x.shape[0] % counts.shape[0] or x.shape[0] == 0 \
+            or not counts.is_contiguous():
+        raise _lib.AfiError(f"{name}: dense rows [N B, P1, C] (or pixel-major [N B, C, S, S]) and counts [N] with N dividing the rows expected, "
+                            f"got {tuple(x.shape)} and {tuple(counts.shape)}")
+    N, B = counts.shape[0], x.shape[0] // counts.shape[0]
+    P1, C_ = (x.shape[1], x.shape[2]) if x.dim() == 3 else (x.shape[2] * x.shape[3], x.shape[1])
+    if C_ % 4 or P1 < 1 or B > RPN_MAX_BATCH or N > ROI_BN_MAX_IMAGES:
+        raise _lib.AfiError(f"{name}: {C_} channels (a multiple of 4 is needed), {P1} pixels per row, {B} rows per image (at most {RPN_MAX_BATCH}), "
+                            f"{N} images (at most {ROI_BN_MAX_IMAGES})")
+    for t in same:
+        if t is not None and (t.shape != x.shape or t.stride() != x.stride()):
+            raise _lib.AfiError(f"{name}: every row tensor must have x's shape and memory layout, got {tuple(t.shape)} for {tuple(x.shape)}")
+    for v in vectors:
+        if v is not None and (tuple(v.shape) != (C_,) or not v.is_contiguous()):
+            raise _lib.AfiError(f"{name}: dense per-channel vectors [{C_}] expected, got {tuple(v.shape)}")
+    _check_cuda(x, *same, *[v for v in vectors if v is not None])
+    _check_i32(counts)
+    return N, B, P1, C_
+
+
+def roi_bn_stats(x, counts, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None, want_var=False):
+    """Train-mode BatchNorm statistics over the valid rows (j < counts[n]) of the padded list x [N B, P1, C] (or pixel-major [N B, C, S, S]):
+    (mean, invstd[, biased var]); the running buffers and the counter are updated in place, and left alone when no row is valid
+    (afi_roi_bn_stats)."""
+    N, B, P1, C_ = _roi_bn_list("roi_bn_stats", x, counts, vectors=(running_mean, running_var))
+    if (running_mean is None) != (running_var is None):
+        raise _lib.AfiError("roi_bn_stats: running_mean and running_var come together")
+    if num_batches_tracked is not None and (not num_batches_tracked.is_cuda or num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise _lib.AfiError("roi_bn_stats: num_batches_tracked must be one int64 on the GPU")
+    mean, invstd = torch.empty(C_, device=x.device), torch.empty(C_, device=x.device)
+    var = torch.empty(C_, device=x.device) if want_var else None
+    call("afi_roi_bn_stats", _p(x), _p(counts), N, B, P1, C_, float(eps), float(momentum), _p(mean), _p(invstd), _p(var), _p(running_mean),
+         _p(running_var), _p(num_batches_tracked), _p(reduce_scratch(C_, x.device)), stream_ptr())
+    return (mean, invstd, var) if want_var else (mean, invstd)
+
+
+def roi_bn_relu_fwd(x, counts, mean, invstd, gamma, beta, relu=True):
+    """y = max(0, (x - mean) invstd gamma + beta) on the valid rows of the padded list (relu=False: the plain affine), exactly 0 on its
+    padding rows, in x's layout (afi_roi_bn_relu_fwd)."""
+    N, B, P1, C_ = _roi_bn_list("roi_bn_relu_fwd", x, counts, vectors=(mean, invstd, gamma, beta))
+    y = torch.empty_like(x)
+    call("afi_roi_bn_relu_fwd", _p(x), _p(counts), N, B, P1, C_, _p(mean), _p(invstd), _p(gamma), _p(beta), int(bool(relu)), _p(y), stream_ptr())
+    return y
+
+
+def roi_bn_relu_bwd_sums(g, x, y, counts, mean, invstd, dgamma=None, dbeta=None, relu=True):
+    """[2, C] = (sum g', sum g' xhat) over the valid rows, g' = g [y > 0] from the stored y (relu=False: g' = g, y may be None); dbeta /
+    dgamma += them (afi_roi_bn_relu_bwd_sums)."""
+    if relu and y is None:
+        raise _lib.AfiError("roi_bn_relu_bwd_sums: relu=True needs the forward's stored y (the mask is the forward's)")
+    N, B, P1, C_ = _roi_bn_list("roi_bn_relu_bwd_sums", x, counts, g, y if relu else None, vectors=(mean, invstd, dgamma, dbeta))
+    sums = torch.empty((2, C_), device=x.device)
+    call("afi_roi_bn_relu_bwd_sums", _p(g), _p(x), _p(y if relu else None), _p(counts), N, B, P1, C_, _p(mean), _p(invstd), int(bool(relu)),
+         _p(dgamma), _p(dbeta), _p(sums), _p(reduce_scratch(C_, x.device)), stream_ptr())
+    return sums
+
+
+def roi_bn_relu_bwd_apply(g, x, y, counts, mean, invstd, gamma, sums, relu=True):
+    """dx = gamma invstd (g' - s0 / Pn - xhat s1 / Pn) on the valid rows, 0 on the padding rows, Pn formed from counts on the device
+    (afi_roi_bn_relu_bwd_apply)."""
+    if relu and y is None:
+        raise _lib.AfiError("roi_bn_relu_bwd_apply: relu=True needs the forward's stored y (the mask is the forward's)")
+    N, B, P1, C_ = _roi_bn_list("roi_bn_relu_bwd_apply", x, counts, g, y if relu else None, vectors=(mean, invstd, gamma))
+    _check_cuda(sums)
+    if tuple(sums.shape) != (2, C_) or not sums.is_contiguous():
+        raise _lib.AfiError(f"roi_bn_relu_bwd_apply: dense sums [2, {C_}] expected, got {tuple(sums.shape)}")
+    dx = torch.empty_like(x)
+    call("afi_roi_bn_relu_bwd_apply", _p(g), _p(x), _p(y if relu else None), _p(counts), N, B, P1, C_, _p(mean), _p(invstd), _p(gamma), _p(sums),
+         int(bool(relu)), _p(dx), stream_ptr())
+    return dx

@@ -25,7 +25,7 @@ Training, box branch (``StandardROIHeads.losses``, and ``forward`` in training m
 get_deltas, softmax_cross_entropy_loss and smooth_l1_loss on afi_roi_label / afi_rpn_sample / afi_roi_gather_samples / afi_roi_box_loss
 (csrc/roi_loss.hip), the pooler and head forward on the kernels above, their backward on afi_conv1x1_dgrad / afi_conv1x1_wgrad / afi_relu_bwd
 and afi_roi_align_bwd (``_ROIBoxLossFn``).  The sample is decided by 32-bit keys, as in ``RPN.losses``.  One IOU_THRESHOLDS entry with
-IOU_LABELS [0, 1]; cascade training, crowd handling and TRAIN_ON_PRED_BOXES are out of scope (AfiError).
+IOU_LABELS [0, 1]; crowd handling and TRAIN_ON_PRED_BOXES are out of scope (AfiError).  CascadeROIHeads trains after its ``trainable_()`` (at the end).
 
 Training, mask branch (heads built with ``masks=True``: ``losses`` returns ``loss_mask`` as well): detectron2's mask_rcnn_loss on the first
 Bf = int(BATCH_SIZE_PER_IMAGE POSITIVE_FRACTION) rows of the box branch's training list, whose n_pos positives come first -- one label /
@@ -62,9 +62,22 @@ stage with its own ``box_head.{k}`` (``conv1`` .. ``conv{NUM_CONV}``: 3x3, pad 1
     detectron2's ``sum(scores_per_stage) * (1.0 / S)``.  The S score tensors are never stored;
   - then fast_rcnn_inference on the mean scores and the last stage's boxes (class-agnostic), and StandardROIHeads' mask branch.
 The norm of a conv (ROI_BOX_HEAD.NORM / ROI_MASK_HEAD.NORM: "", "BN", "SyncBN", "FrozenBN") is its child ``norm`` (buffers weight, bias,
-running_mean, running_var; BN / SyncBN also num_batches_tracked, so an nn.SyncBatchNorm checkpoint loads with strict=True), always on its running
+running_mean, running_var; BN / SyncBN also num_batches_tracked, so an nn.SyncBatchNorm checkpoint loads with strict=True), at inference always on its running
 statistics, eps 1e-5, folded into the conv in fp64 (frozen.fold_conv) and cached (frozen.prepared).  The conv head and the normed mask head are
-the Cascade class's only."""
+the Cascade class's only.
+
+``CascadeROIHeads`` in training (detectron2 v0.1.1's ``_forward_box`` with targets; opt-in: ``trainable_()`` enables it, heads on which it was
+never called refuse as before): ``losses`` / ``losses_padded`` / ``forward`` in training mode with targets return ``loss_cls_stage{k}`` and
+``loss_box_reg_stage{k}`` (``_CascadeBoxLossFn``).  Stage 0's training list is the parent's label / sample / gather at IOUS[0]; stage k's is
+afi_roi_cascade_relabel on stage k - 1's predictor output and boxes at IOUS[k] (decode and clip as afi_roi_cascade_stage does, boxes that
+clipped to empty dropped in order, the rest matched; csrc/cascade_train.hip), which is why these calls need the image sizes.  Every stage: the
+box pooler, its convs as ``_train_conv`` blocks -- no norm: biased conv + ReLU; FrozenBN: the folded conv + ReLU, the weight gradient through
+afi_frozen_wgrad_unfold; BN / SyncBN in training mode: the conv without bias, then afi_roi_bn_stats and afi_roi_bn_relu_fwd over the rows below
+counts (the running buffers advance; the affine is a pair of parameters under ``norm.weight`` / ``norm.bias``), backward on
+afi_roi_bn_relu_bwd_sums / _apply --, the FCs, the predictor and afi_roi_box_loss (class-agnostic, BBOX_REG_WEIGHTS[k]).  The features get
+(1 / S) of every stage's ROIAlign backward (_ScaleGradient).  With masks=True ``loss_mask`` is computed on the foreground prefix of stage 0's
+list; a normed ``mask_fcn`` chain trains through the same blocks (``_CascadeMaskLossFn``).  Refused: BN / SyncBN heads in eval mode with
+targets, SyncBN under a process group of more than one rank.  ``last_assignment["stages"]`` holds every stage's list."""
 import math
 
 import torch
@@ -416,30 +429,7 @@ class _ROIBoxLossFn(torch.autograd.Function):
         g = _rows_as_pixels(dpred * s)
         x0 = pooled.permute(0, 2, 3, 1).reshape(R, -1)                      # fc1's input rows, in the pooled memory's [S][S][C] order
         ins = [_rows_as_pixels(x0)] + [_rows_as_pixels(a) for a in acts]    # ins[k]: the input of FC k; ins[F]: the predictor's
-        pgrads = []
-
-        def layer_grads(dy, x):
-            """(weight gradient [Cout, Cin], bias gradient [Cout]) of one FC seen as a 1x1 conv over the R rows."""
-            cout, cin = dy.shape[1], x.shape[1]
-            dw = torch.zeros((cout, cin), device=dev, dtype=torch.float32)
-            _lib.call("afi_conv1x1_wgrad", ops.view_of(dy), ops.view_of(x), 1, 1, R, cout, cin, ops._p(dw), 1.0, ops.stream_ptr())
-            db = torch.zeros((cout,), device=dev, dtype=torch.float32)
-            ops.colsum_accum(_pixels_as_rows(dy), db)
-            return dw, db
-        if need_w:
-            dwp, dbp = layer_grads(g, ins[F])
-            pgrads = [dwp[:nc], dbp[:nc], dwp[nc:nc + nb], dbp[nc:nc + nb]]
-        dx, fgrads = ops.conv1x1_dgrad(g, wp), []
-        for k in reversed(range(F)):
-            du = ops.relu_bwd(dx, ins[k + 1])
-            if need_w:
-                dw, db = layer_grads(du, ins[k])
-                if k == 0:                                                   # back to the parameter's [out][C][S][S] order
-                    C_, S = pooled.shape[1], pooled.shape[2]
-                    dw = dw.view(-1, S, S, C_).permute(0, 3, 1, 2).reshape(dw.shape[0], -1)
-                fgrads = [dw, db] + fgrads
-            if k > 0 or need_x:
-                dx = ops.conv1x1_dgrad(du, fcw[k - 1] if k > 0 else w1)
+        dx, fgrads, pgrads = _fc_chain_backward(g, ins, w1, wp, fcw, (pooled.shape[1], pooled.shape[2]), nc, nb, need_w, need_x)
         dxs = [None] * L
         if need_x:
             C_, S = pooled.shape[1], pooled.shape[2]
@@ -513,6 +503,225 @@ class _ROIMaskLossFn(torch.autograd.Function):
             dxs = [d if n else None for d, n in zip(dxs, need[na:na + L])]
         g = cgrads + dgrads + [dwp.view(dwp.shape[0], -1, 1, 1), dbp] if need_w else [None] * (2 * F + 4)
         return (*[None] * na, *dxs, *[v if n else None for v, n in zip(g, need[na + L:])])
+
+
+def _fc_chain_backward(g, ins, w1, wp, fcw, pooled_shape, nc, nb, need_w, need_x):
+    """The backward of ``_run_head``'s FCs and predictor, shared by ``_ROIBoxLossFn`` and ``_CascadeBoxLossFn``: g = d loss / d predictor output as pixels, ins[k] the
+    input rows of FC k (ins[F]: the predictor's) as pixels.  Returns (d loss / d the rows fc1 read, as pixels, or None; the FCs' [weight, bias]
+    gradients, fc1's back in [out][C][S][S] order; the predictor's four)."""
+    F, R, dev = len(ins) - 1, g.shape[3], g.device
+
+    def layer_grads(dy, x):
+        cout, cin = dy.shape[1], x.shape[1]
+        dw = torch.zeros((cout, cin), device=dev, dtype=torch.float32)
+        _lib.call("afi_conv1x1_wgrad", ops.view_of(dy), ops.view_of(x), 1, 1, R, cout, cin, ops._p(dw), 1.0, ops.stream_ptr())
+        db = torch.zeros((cout,), device=dev, dtype=torch.float32)
+        ops.colsum_accum(_pixels_as_rows(dy), db)
+        return dw, db
+    pgrads, fgrads = [], []
+    if need_w:
+        dwp, dbp = layer_grads(g, ins[F])
+        pgrads = [dwp[:nc], dbp[:nc], dwp[nc:nc + nb], dbp[nc:nc + nb]]
+    dx = ops.conv1x1_dgrad(g, wp)
+    for k in reversed(range(F)):
+        du = ops.relu_bwd(dx, ins[k + 1])
+        if need_w:
+            dw, db = layer_grads(du, ins[k])
+            if k == 0:
+                C_, S = pooled_shape
+                dw = dw.view(-1, S, S, C_).permute(0, 3, 1, 2).reshape(dw.shape[0], -1)
+            fgrads = [dw, db] + fgrads
+        dx = ops.conv1x1_dgrad(du, fcw[k - 1] if k > 0 else w1) if k > 0 or need_x else None
+    return dx, fgrads, pgrads
+
+
+def _train_convs_backward(dx, kinds, ct, x0, counts, slots, pgrads, need_w, need_x):
+    """The backward of a chain of ``CascadeROIHeads._train_conv`` blocks on the padded rows: dx = d loss / d the last block's output, kinds[i] /
+    ct[i] what block i's forward kept, x0 the chain's input, slots[i] where block i's parameter gradients go in `pgrads`.  Per block: the
+    ReLU mask (no norm, FrozenBN) or the two list-masked BatchNorm halves over the rows below counts, then the 3x3 weight and data gradients
+    in the forward's regime; the FrozenBN weight gradient goes through afi_frozen_wgrad_unfold.  Returns d loss / d x0 (None unless need_x)."""
+    for i in reversed(range(len(ct))):
+        kind, tt, slot = kinds[i], ct[i], slots[i]
+        xin = ct[i - 1][0] if i > 0 else x0
+        if kind == "bn":
+            y, u, mean, invstd, gamma, w = tt
+            dgamma, dbeta = torch.zeros_like(mean), torch.zeros_like(mean)
+            sums = ops.roi_bn_relu_bwd_sums(dx, u, y, counts, mean, invstd, dgamma, dbeta)
+            du = ops.roi_bn_relu_bwd_apply(dx, u, y, counts, mean, invstd, gamma, sums)
+            if need_w:
+                pgrads[slot["gamma"]], pgrads[slot["beta"]] = dgamma, dbeta
+        else:
+            y, w = tt[0], tt[1]
+            du = ops.relu_bwd(dx, y)
+        wino = _wino(xin, du.shape[1])
+        if need_w:
+            dw = (ops.conv3x3_wino_wgrad if wino else ops.conv3x3_wgrad)(du, xin)
+            if kind == "frozen":                                        # the gradient of the FOLDED weight: back to the parameter's
+                gw = torch.zeros(dw.shape, device=dw.device, dtype=torch.float32)
+                ops.frozen_wgrad_unfold([(dw, gw, tt[2])])
+                dw = gw
+            pgrads[slot["weight"]] = dw
+            if slot["bias"] is not None:
+                pgrads[slot["bias"]] = ops.bias_grad(du)
+        dx = (ops.conv3x3_wino_dgrad if wino else ops.conv3x3_dgrad)(du, w) if i > 0 or need_x else None
+    return dx
+
+
+class _CascadeMaskLossFn(torch.autograd.Function):
+    """``_ROIMaskLossFn`` for a mask head whose ``mask_fcn`` convs carry a norm (CascadeROIHeads: ROI_MASK_HEAD.NORM "BN" / "SyncBN" /
+    "FrozenBN"): the same targets, pooler, deconv, loss and predictor backward on the foreground prefix of stage 0's training list; the convs
+    run as ``CascadeROIHeads._train_conv`` blocks, the list-masked BatchNorm passes over the rows below counts_fg at 14 x 14 pixels a row."""
+    NARGS = 5
+
+    @staticmethod
+    @_lib.ctx_forward
+    def forward(ctx, heads, polys, gcounts, gmax, nlev, *ts):
+        xs = [ops.pixel_major(x.detach()) for x in ts[:nlev]]
+        a, pool, Bf, mh = heads.last_assignment, heads.mask_pooler, heads.mask_batch_per_image, heads.mask_head
+        tg, cfg_ = ops.mask_targets(*polys, a["boxes"], a["sampled_idx"], a["matched_idx"], gcounts, gmax, a["n_pos"], Bf, 2 * pool.output_size)
+        boxes = a["boxes"][:, :Bf].contiguous()
+        cls = a["gt_classes"][:, :Bf]
+        pooled = pool(xs, boxes, cfg_)
+        _, (wd, bd), (wp, bp) = heads._prepare_mask()
+        x, recs = pooled, []
+        for i, conv in enumerate(mh.conv_norm_relus):
+            x, rec = heads._train_conv(f"m{i}", conv, x, cfg_, lambda i=i: heads._prepare_mask()[0][i])
+            recs.append(rec)
+        h = ops.conv1x1_fwd(x, wd, bd, act=2)
+        loss, dz = ops.mask_loss(h, wp, bp, cls, cfg_, tg)
+        ctx.save_for_backward(wd, wp, pooled, h, dz, boxes, cfg_, cls, *[t for r in recs for t in r["tensors"]])
+        ctx.kinds, ctx.nts, ctx.nlev, ctx.layout = [r["kind"] for r in recs], [len(r["tensors"]) for r in recs], nlev, heads._mask_layout
+        ctx.level_shapes, ctx.min_level, ctx.sampling_ratio = [tuple(x.shape[2:]) for x in xs], pool.min_level, pool.sampling_ratio
+        a.update(mask_targets=tg, counts_fg=cfg_, mask_boxes=boxes, mask_deconv=h, mask_dz=dz)
+        return loss[0]
+
+    @staticmethod
+    @_lib.ctx_backward
+    def backward(ctx, dloss):
+        sv, L, na = ctx.saved_tensors, ctx.nlev, _CascadeMaskLossFn.NARGS
+        wd, wp, pooled, h, dz, boxes, cfg_, cls = sv[:8]
+        ct, pos = [], 8
+        for n in ctx.nts:
+            ct.append(sv[pos:pos + n])
+            pos += n
+        need = ctx.needs_input_grad
+        need_x, need_w = any(need[na:na + L]), any(need[na + L:])
+        lay = ctx.layout
+        pgrads = [None] * (len(need) - na - L)
+        x_last = ct[-1][0] if ct else pooled
+        dh, dwp, dbp = ops.mask_pred_bwd(h, dz * dloss.float(), wp, cls, cfg_)
+        if need_w:
+            cout, cin = wd.shape[0] // 4, wd.shape[1]
+            pgrads[lay["deconv"][0]] = ops.conv1x1_wgrad(dh, x_last).view(2, 2, cout, cin).permute(3, 2, 0, 1)
+            pgrads[lay["deconv"][1]] = ops.bias_grad(dh).view(4, cout).sum(0)
+            pgrads[lay["pred"][0]], pgrads[lay["pred"][1]] = dwp.view(dwp.shape[0], -1, 1, 1), dbp
+        dx = ops.conv1x1_dgrad(dh, wd) if ct or need_x else None
+        dx = _train_convs_backward(dx, ctx.kinds, ct, pooled, cfg_, lay["conv"], pgrads, need_w, need_x)
+        dxs = [None] * L
+        if need_x:
+            dxs = ops.roi_align_bwd(dx, ctx.level_shapes, ctx.min_level, boxes, cfg_, ctx.sampling_ratio)
+            dxs = [d if n else None for d, n in zip(dxs, need[na:na + L])]
+        return (*[None] * na, *dxs, *[v if n else None for v, n in zip(pgrads, need[na + L:])])
+
+
+class _CascadeBoxLossFn(torch.autograd.Function):
+    """(loss_cls_stage0, loss_box_reg_stage0, ...) of the features and every stage's parameters: detectron2 v0.1.1's
+    CascadeROIHeads._forward_box in training.  Forward, per stage: stage 0's training list is the parent's label / sample / gather at IOUS[0],
+    stage k > 0's is afi_roi_cascade_relabel on stage k - 1's predictor output and boxes at IOUS[k]; then the box pooler, the conv-norm-ReLU
+    chain (``heads._train_conv``), the FCs and the predictor, and afi_roi_box_loss (class-agnostic, BBOX_REG_WEIGHTS[k]) over the stage's own
+    rows.  Backward, per stage: ``_fc_chain_backward``, the convs' backward in the forward's regime (ReLU mask or the list-masked BatchNorm
+    halves; the FrozenBN weight gradient through afi_frozen_wgrad_unfold), afi_roi_align_bwd of (1 / S) d pooled (detectron2's _ScaleGradient),
+    summed over the stages.  Boxes, labels and targets are not differentiable."""
+    NARGS = 9
+
+    @staticmethod
+    @_lib.ctx_forward
+    def forward(ctx, heads, pboxes, pcounts, gt, gcls, gcounts, keys, image_hw, nlev, *ts):
+        xs = [ops.pixel_major(x.detach()) for x in ts[:nlev]]
+        pool, K, B, S_ = heads.box_pooler, heads.num_classes, heads.batch_size_per_image, heads.num_stages
+        saved, meta, losses, stages = [], [], [], []
+        boxes = counts = pred = None
+        for k in range(S_):
+            head, pr = heads.box_head[k], heads.box_predictor[k]
+            if k == 0:
+                labels, midx = ops.roi_label(pboxes, pcounts, gt, gcounts, heads.stage_ious[0], heads.proposal_append_gt)
+                if keys is None:
+                    keys = torch.randint(-2 ** 31, 2 ** 31, labels.shape, device=labels.device, dtype=torch.int32)
+                labels, sidx, n_pos, n_neg = ops.rpn_sample(labels, keys, B, heads.positive_fraction)
+                boxes, counts, cls, gboxes = ops.roi_gather_samples(pboxes, pcounts, gt, gcls, gcounts, midx, sidx, n_pos, n_neg, K,
+                                                                    heads.proposal_append_gt)
+                first = {"labels": labels, "matched_idx": midx, "sampled_idx": sidx, "n_pos": n_pos, "n_neg": n_neg}
+                st = {"src": None, "matched_idx": None}
+            else:
+                r = ops.roi_cascade_relabel(pred, K, boxes, counts, image_hw, heads.stage_weights[k - 1], gt, gcls, gcounts, heads.stage_ious[k],
+                                            SCALE_CLAMP)
+                boxes, counts, cls, gboxes = r["boxes"], r["counts"], r["gt_classes"], r["gt_boxes"]
+                st = {"src": r["src"], "matched_idx": r["matched_idx"]}
+            pooled = pool(xs, boxes, counts)
+            x, convs = pooled, []
+            for i, conv in enumerate(head.conv_norm_relus):
+                x, rec = heads._train_conv(f"{k}_{i}", conv, x, counts, lambda k=k, i=i, head=head: heads._prepare_convs(head, f"prep_convs{k}")[i])
+                convs.append(rec)
+            w1, wp, bp = heads._prepare_head(head, pr, f"prep{k}")
+            pred, _, acts = heads._run_head(head, [], (w1, wp, bp), x)
+            loss, dpred = ops.roi_box_loss(pred, K, True, boxes, counts, cls, gboxes, heads.stage_weights[k], heads.smooth_l1_beta)
+            losses += [loss[0], loss[1]]
+            t = [w1, wp, *[fc.weight.detach() for fc in head.fcs[1:]], pooled, *acts, dpred, boxes, counts]
+            for rec in convs:
+                t += rec["tensors"]
+            meta.append({"at": len(saved), "n": len(t), "nfc": len(head.fcs), "nc": pr.cls_score.weight.shape[0], "nb": pr.bbox_pred.weight.shape[0],
+                         "convs": [{"kind": rec["kind"], "nt": len(rec["tensors"])} for rec in convs]})
+            saved += t
+            st.update(boxes=boxes, counts=counts, gt_classes=cls, gt_boxes=gboxes, pred=pred)
+            stages.append(st)
+        ctx.save_for_backward(*saved)
+        ctx.meta, ctx.nlev, ctx.layout = meta, nlev, heads._train_layout
+        ctx.level_shapes, ctx.min_level, ctx.sampling_ratio = [tuple(x.shape[2:]) for x in xs], pool.min_level, pool.sampling_ratio
+        s0 = stages[0]
+        heads.last_assignment = dict(first, boxes=s0["boxes"], counts=s0["counts"], gt_classes=s0["gt_classes"], gt_boxes=s0["gt_boxes"], pred=s0["pred"],
+                                     stages=stages)
+        return tuple(losses)
+
+    @staticmethod
+    @_lib.ctx_backward
+    def backward(ctx, *dlosses):
+        sv, L, na = ctx.saved_tensors, ctx.nlev, _CascadeBoxLossFn.NARGS
+        need = ctx.needs_input_grad
+        need_x = any(need[na:na + L])
+        S_ = len(ctx.meta)
+        pgrads = [None] * (len(need) - na - L)
+        dxs = None
+        for k, m in enumerate(ctx.meta):
+            t = sv[m["at"]:m["at"] + m["n"]]
+            F = m["nfc"]
+            w1, wp, fcw, pooled, acts = t[0], t[1], t[2:1 + F], t[1 + F], t[2 + F:2 + 2 * F]
+            dpred, boxes, counts = t[2 + 2 * F:5 + 2 * F]
+            ct, pos = [], 5 + 2 * F
+            for c in m["convs"]:
+                ct.append(t[pos:pos + c["nt"]])
+                pos += c["nt"]
+            lay = ctx.layout[k]
+            need_w = any(need[na + L + i] for i in lay["all"])
+            nc, nb = m["nc"], m["nb"]
+            s = torch.zeros(dpred.shape[1], device=dpred.device, dtype=torch.float32)
+            s[:nc], s[nc:nc + nb] = dlosses[2 * k].float(), dlosses[2 * k + 1].float()
+            g = _rows_as_pixels(dpred * s)
+            R = dpred.shape[0]
+            x_last = ct[-1][0] if ct else pooled                               # what fc1 read: the last conv's output, or the pooled features
+            C_, S = x_last.shape[1], x_last.shape[2]
+            ins = [_rows_as_pixels(x_last.permute(0, 2, 3, 1).reshape(R, -1))] + [_rows_as_pixels(a) for a in acts]
+            dx, fgrads, prg = _fc_chain_backward(g, ins, w1, wp, fcw, (C_, S), nc, nb, need_w, need_x or bool(ct))
+            if need_w:
+                for i, v in zip(lay["fc"] + lay["pred"], fgrads + prg):
+                    pgrads[i] = v
+            if dx is not None:
+                dx = _pixels_as_rows(dx).view(R, S, S, C_).permute(0, 3, 1, 2)
+            dx = _train_convs_backward(dx, [c["kind"] for c in m["convs"]], ct, pooled, counts, lay["conv"], pgrads, need_w, need_x)
+            if need_x:
+                d = ops.roi_align_bwd(dx * (1.0 / S_), ctx.level_shapes, ctx.min_level, boxes, counts, ctx.sampling_ratio)
+                dxs = d if dxs is None else [a + b for a, b in zip(dxs, d)]
+        dxs = [d if n else None for d, n in zip(dxs, need[na:na + L])] if need_x else [None] * L
+        return (*[None] * na, *dxs, *[v if n else None for v, n in zip(pgrads, need[na + L:])])
 
 
 def _make_sampled(image_size, boxes, gt_classes, gt_boxes):
@@ -594,6 +803,7 @@ class StandardROIHeads(nn.Module):
             Sm = self.mask_pooler.output_size
             self.mask_head = MaskRCNNConvUpsampleHead((C_, Sm, Sm), self.num_classes, int(cfg_get(mh, "NUM_CONV", 0)), int(cfg_get(mh, "CONV_DIM", 256)),
                                                       cfg_get(mh, "NORM", ""), bool(cfg_get(mh, "CLS_AGNOSTIC_MASK", False)), norms=self.conv_norm_heads)
+            self.mask_norm = cfg_get(mh, "NORM", "")
         for p in self.parameters():
             p.requires_grad_(False)
         # ---- the training side (losses): read here, so that a config it cannot honour fails at construction
@@ -1036,6 +1246,9 @@ class CascadeROIHeads(StandardROIHeads):
             raise AfiError(f"roi_heads: MODEL.ROI_BOX_CASCADE_HEAD.IOUS[0] {ious[0]} must equal MODEL.ROI_HEADS.IOU_THRESHOLDS[0] {first} (detectron2 "
                            "asserts it)")
         self.num_stages = len(ious)
+        self.stage_ious = tuple(float(v) for v in ious)
+        self.box_norm = cfg_get(bh, "NORM", "")
+        self._train_enabled = False
         self.stage_weights = tuple(_reg_weights(f"MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS[{k}]", w) for k, w in enumerate(weights))
         if not cfg_get(bh, "CLS_AGNOSTIC_BBOX_REG", False):
             raise AfiError("roi_heads: MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG False is not supported by CascadeROIHeads (detectron2 asserts "
@@ -1057,6 +1270,153 @@ class CascadeROIHeads(StandardROIHeads):
 
     def select(self, pred, boxes, counts, image_hw):
         raise AfiError("roi_heads: CascadeROIHeads decodes stage by stage (forward_padded); there is no selection on one predictor output")
+
+    # ------------------------------------------------------------------ training (the box branch of every stage)
+    def trainable_(self, flag=True, mask_head=False):
+        """Enable training of these heads (``losses`` / ``losses_padded`` / ``forward`` with targets refuse until this was called) and make the
+        parameters of every stage's box head and predictor trainable (flag=False: frozen, training stays enabled).  The affine of a "BN" /
+        "SyncBN" norm of the box heads becomes a pair of parameters under the same keys ``norm.weight`` / ``norm.bias`` (a "FrozenBN" norm
+        stays four buffers).  mask_head=True: the mask head's parameters as well (heads built with masks=True), its norms' affine likewise."""
+        if mask_head and not self.mask_on:
+            raise AfiError("roi_heads: trainable_(mask_head=True) on heads built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
+        for head in list(self.box_head) + ([self.mask_head] if mask_head else []):
+            for conv in head.conv_norm_relus:
+                n = getattr(conv, "norm", None)
+                if isinstance(n, TrackedFrozenBatchNorm2d) and not isinstance(n.weight, nn.Parameter):
+                    w, b = n.weight, n.bias
+                    del n._buffers["weight"], n._buffers["bias"]
+                    n.weight, n.bias = nn.Parameter(w.detach().clone(), requires_grad=False), nn.Parameter(b.detach().clone(), requires_grad=False)
+        self._train_enabled = True
+        for mod in (self.box_head, self.box_predictor) + ((self.mask_head,) if mask_head else ()):
+            for p in mod.parameters():
+                p.requires_grad_(bool(flag))
+        return self
+
+    def _refuse_training(self):
+        if not self._train_enabled:
+            raise AfiError("roi_heads: CascadeROIHeads is inference-only (frozen): cascade training is out of scope until trainable_() enables it "
+                           "(CascadeROIHeads.trainable_)")
+        # what depends on the module's state alone is refused here, before anything touches the device
+        heads = [(h, self.box_norm) for h in self.box_head] + ([(self.mask_head, self.mask_norm)] if self.mask_on else [])
+        batch = [norm for h, norm in heads if any(isinstance(getattr(c, "norm", None), TrackedFrozenBatchNorm2d) for c in h.conv_norm_relus)]
+        if batch and not self.training:
+            raise AfiError("roi_heads: targets given to CascadeROIHeads in eval mode whose heads carry BN / SyncBN: the batch statistics "
+                           "are those of training mode -- call .train()")
+        if "SyncBN" in batch and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            raise AfiError("roi_heads: SyncBN heads under a process group of more than one rank: the exchange of the statistics "
+                           "between ranks is not built yet")
+
+    def _train_params(self):
+        """(every stage's trainable tensors in one list, per stage the positions of each in it): conv weight, bias (no norm) or the BN affine,
+        the FCs, the predictor."""
+        plist, layout = [], []
+
+        def add(t):
+            plist.append(t)
+            return len(plist) - 1
+        for head, pr in zip(self.box_head, self.box_predictor):
+            start, convs = len(plist), []
+            for conv in head.conv_norm_relus:
+                n = getattr(conv, "norm", None)
+                slot = {"weight": add(conv.weight), "bias": add(conv.bias) if conv.bias is not None else None, "gamma": None, "beta": None}
+                if isinstance(n, TrackedFrozenBatchNorm2d):
+                    slot["gamma"], slot["beta"] = add(n.weight), add(n.bias)
+                convs.append(slot)
+            fc = [add(t) for l in head.fcs for t in (l.weight, l.bias)]
+            pred = [add(t) for t in (pr.cls_score.weight, pr.cls_score.bias, pr.bbox_pred.weight, pr.bbox_pred.bias)]
+            layout.append({"conv": convs, "fc": fc, "pred": pred, "all": list(range(start, len(plist)))})
+        return plist, layout
+
+    def _train_conv(self, name, conv, x, counts, folded):
+        """One conv-norm-ReLU of a head in training on the padded rows x [N B, C, S, S]: (output, what the backward keeps).  No norm: the
+        biased conv with ReLU.  FrozenBN: the folded conv with ReLU (folded(): its prepared weight and bias).  BN / SyncBN: the conv without
+        bias, then the statistics over the rows below counts (the running buffers and num_batches_tracked advance) and the list-masked
+        normalise + ReLU.  name: the slot the conv's weight in the kernels' memory is kept under.  (Eval mode and more than one rank under
+        BN / SyncBN are ``_refuse_training``'s to refuse, before the call reaches the device.)"""
+        n = getattr(conv, "norm", None)
+        if isinstance(n, TrackedFrozenBatchNorm2d):
+            w = prepared(self, f"train_w{name}", [conv.weight], lambda: ops.to_ohwi(conv.weight.detach().float()))
+            u = conv3x3(x, (w, None), relu=False)
+            mean, invstd = ops.roi_bn_stats(u, counts, n.eps, self.bn_momentum, n.running_mean, n.running_var, n.num_batches_tracked)
+            gamma, beta = n.weight.detach().float().contiguous(), n.bias.detach().float().contiguous()
+            y = ops.roi_bn_relu_fwd(u, counts, mean, invstd, gamma, beta)
+            return y, {"kind": "bn", "tensors": [y, u, mean, invstd, gamma, w]}
+        wb = folded()
+        y = conv3x3(x, wb, relu=True)
+        if n is None:
+            return y, {"kind": "relu", "tensors": [y, wb[0]]}
+        s = (n.weight.double() * torch.rsqrt(n.running_var.double() + n.eps)).float().contiguous()
+        return y, {"kind": "frozen", "tensors": [y, wb[0], s]}
+
+    bn_momentum = 0.1                 # nn.BatchNorm2d's / nn.SyncBatchNorm's default, which detectron2's get_norm keeps
+
+    def losses_padded(self, features, boxes, counts, gt, gt_classes, gt_counts, keys=None, gt_polygons=None, image_sizes=None):
+        """``StandardROIHeads.losses_padded`` for the cascade: {"loss_cls_stage{k}", "loss_box_reg_stage{k}"} of every stage (and ``loss_mask``
+        on stage 0's training list for heads built with masks=True).  image_sizes: [N, 2] fp32 (height, width) on the device, which the boxes
+        a stage hands to the next are clipped to.  No host read."""
+        self._refuse_training()
+        xs = self._check(features, boxes, counts, train=True)
+        _check_feature("roi_heads", "gt boxes", gt)
+        N = xs[0].shape[0]
+        if not torch.is_tensor(image_sizes) or not image_sizes.is_cuda or tuple(image_sizes.shape) != (N, 2):
+            raise AfiError(f"roi_heads: CascadeROIHeads.losses_padded needs image_sizes = an [{N}, 2] tensor (height, width) on the GPU: the boxes "
+                           "of a stage are clipped to the image before the next stage is labelled")
+        if self.mask_on:
+            if gt_polygons is None or len(gt_polygons) != 3:
+                raise AfiError("roi_heads: heads built with masks=True train the mask branch: losses_padded needs gt_polygons = (xy, vert_off, "
+                               "poly_off) on the device (ops.mask_polygons)")
+            if self.mask_batch_per_image < 1:
+                raise AfiError(f"roi_heads: MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE {self.batch_size_per_image} x POSITIVE_FRACTION "
+                               f"{self.positive_fraction} leaves the mask branch no foreground row")
+        elif gt_polygons is not None:
+            raise AfiError("roi_heads: gt_polygons given to heads built without the mask branch (build_roi_heads(cfg, input_shape, masks=True))")
+        params, self._train_layout = self._train_params()
+        out = _CascadeBoxLossFn.apply(self, boxes.detach().contiguous(), counts.contiguous(), gt.contiguous(), gt_classes.contiguous(),
+                                      gt_counts.contiguous(), keys, image_sizes.detach().to(torch.float32).contiguous(), len(xs), *xs, *params)
+        losses = {}
+        for k in range(self.num_stages):
+            losses[f"loss_cls_stage{k}"], losses[f"loss_box_reg_stage{k}"] = out[2 * k], out[2 * k + 1]
+        if self.mask_on:
+            mh = self.mask_head
+            if not any(getattr(l, "norm", None) is not None for l in mh.conv_norm_relus):           # without norm: the parent's path
+                mparams = [t for l in mh.conv_norm_relus + [mh.deconv, mh.predictor] for t in (l.weight, l.bias)]
+                losses["loss_mask"] = _ROIMaskLossFn.apply(self, tuple(gt_polygons), gt_counts.contiguous(), int(gt.shape[1]), len(xs), *xs, *mparams)
+                return losses
+            mparams, convs = [], []
+
+            def add(t):
+                mparams.append(t)
+                return len(mparams) - 1
+            for conv in mh.conv_norm_relus:
+                n = getattr(conv, "norm", None)
+                slot = {"weight": add(conv.weight), "bias": add(conv.bias) if conv.bias is not None else None, "gamma": None, "beta": None}
+                if isinstance(n, TrackedFrozenBatchNorm2d):
+                    slot["gamma"], slot["beta"] = add(n.weight), add(n.bias)
+                convs.append(slot)
+            self._mask_layout = {"conv": convs, "deconv": [add(mh.deconv.weight), add(mh.deconv.bias)],
+                                 "pred": [add(mh.predictor.weight), add(mh.predictor.bias)]}
+            losses["loss_mask"] = _CascadeMaskLossFn.apply(self, tuple(gt_polygons), gt_counts.contiguous(), int(gt.shape[1]), len(xs), *xs, *mparams)
+        return losses
+
+    def losses(self, images, features, proposals, targets, keys=None):
+        """The stage losses of detectron2's CascadeROIHeads in training (``losses_padded``), from per-image proposals and targets as
+        ``StandardROIHeads.losses`` takes them; the image sizes come from ``images.image_sizes`` or, without it, the proposals' ``image_size``."""
+        self._refuse_training()
+        inst = self._target_polygons(targets) if self.mask_on else None
+        xs = self._check(features, train=True)
+        N, dev = xs[0].shape[0], xs[0].device
+        if len(proposals) != N:
+            raise AfiError(f"roi_heads: {len(proposals)} proposal lists for a batch of {N}")
+        sizes = getattr(images, "image_sizes", None) or [getattr(p, "image_size", None) for p in proposals]
+        if len(sizes) != N or any(s is None or len(s) != 2 for s in sizes):
+            raise AfiError("roi_heads: CascadeROIHeads.losses needs the image sizes (images.image_sizes, or image_size on every proposal list): the "
+                           "boxes of a stage are clipped to the image before the next stage is labelled")
+        boxes, counts = self._padded_proposals(proposals, N, dev)
+        gt, gc, gn = self._targets(targets, N, dev)
+        polys = ops.mask_polygons(inst, N, int(gt.shape[1]), dev) if self.mask_on else None
+        hw = torch.tensor([(float(h), float(w)) for h, w in sizes], dtype=torch.float32).to(dev)
+        return self.losses_padded(features, boxes, counts, gt, gc, gn, keys, polys, hw)
 
     def _box_branch(self, xs, boxes, counts, image_hw, intermediates):
         """The S stages and the selection: ``_pick``'s dict, ``class_scores`` the mean scores, ``class_boxes`` the last stage's boxes [N, P, 1, 4],

@@ -771,6 +771,47 @@ long long afi_roi_align_bwd_ws_floats(int N, int batch_per_image);
 int afi_roi_align_bwd(const float* dpooled, const afi_view_t* grads, const int* level_hw, int L, int min_level, int N, int C, const float* boxes,
                       const int* counts, int batch_per_image, int S, int sampling_ratio, float* ws, long long ws_floats, void* stream);
 
+/* ------------------------------------------------------------------ CascadeROIHeads in training (csrc/cascade_train.hip)
+ * The two passes of a cascade stage in training that are specific to the padded [N][B] row lists with device-side counts.  No host
+ * synchronisation, no atomics; every result is bit-identical between runs and every output is written completely.
+ * afi_roi_cascade_relabel: detectron2 v0.1.1's _create_proposals_from_boxes + _match_and_label_boxes.  pred [N B][ld_pred], proposals [N][B][4],
+ *   counts [N], image_hw, the four weights and scale_clamp as afi_roi_cascade_stage takes them: rows below counts[n] are decoded and clipped by
+ *   the device function that kernel instantiates, so the boxes are its boxes bit for bit.  A row is kept when, in fp32 on the clipped box,
+ *   x2 - x1 > 0 and y2 - y1 > 0 (Boxes.nonempty(); a NaN box is dropped).  Kept rows are written in their original order: boxes [N][B][4],
+ *   src [N][B] = the input row, counts_out [N] = their number.  Each is matched to gt [N][Gmax][4] (counts_g [N]) as afi_roi_label states it:
+ *   matched_idx [N][B] = the lowest ground-truth index that reaches the maximum IoU, label 1 from iou_thresh up, no low-quality matches;
+ *   classes [N][B] (int32) = gt_classes[matched] where the label is 1, K otherwise; gt_boxes [N][B][4] = gt[matched] on every kept row.
+ *   counts_g[n] = 0: class K, matched_idx 0 and a zero gt_boxes on every kept row.  Past counts_out[n]: boxes and gt_boxes zero, classes -1,
+ *   src -1, matched_idx 0.  B <= 4096, Gmax <= 1024, K <= 1024 (AFI_ERR_UNSUPPORTED), ld_pred >= K + 5; boxes and gt_boxes 16-byte aligned.
+ * afi_roi_bn_*: train-mode BatchNorm (+ ReLU) over x [N B][P1][C] (dense, pixel-major: P1 pixels per list row) in which row n B + j exists iff
+ *   j < counts[n] (counts clamped to 0 .. B).  Pn = P1 sum(min(counts, B)) is formed on the device.  Padding rows of x, g and y are never read
+ *   into a result.  C % 4 == 0, every pointer 16-byte aligned, N <= 1024, B <= 4096 and N B P1 C / 4 < 2^31 (AFI_ERR_UNSUPPORTED).  scratch: afi_reduce_scratch_floats(C) floats, 32-byte aligned.
+ *   afi_roi_bn_stats           mean, invstd = 1 / sqrt(var + eps) and (optional) the biased variance over the Pn valid pixels, accumulated as
+ *                              afi_bn_stats_ex does (fp64, shifted by the first valid pixel, rounded once); the running buffers (both or
+ *                              neither) are updated with momentum, the variance unbiased over Pn, and num_batches_tracked += 1.  Pn == 0:
+ *                              mean 0, invstd 1 / sqrt(eps), variance 0; the running buffers and the counter stay untouched.
+ *   afi_roi_bn_relu_fwd        valid rows: y = max(0, ((x - mean) invstd) gamma + beta) with relu = 1, the plain affine with relu = 0, every
+ *                              operation rounded on its own (afi_bn_apply_fwd's arithmetic); padding rows: y = 0 exactly.
+ *   afi_roi_bn_relu_bwd_sums   sums2C[0..C) = sum g', sums2C[C..2C) = sum g' xhat over the valid rows, g' = g [y > 0] from the STORED y
+ *                              (relu = 1; relu = 0: g' = g and y may be NULL), xhat = (x - mean) invstd; dbeta / dgamma (optional) += them.
+ *   afi_roi_bn_relu_bwd_apply  valid rows: dx = gamma invstd (g' - s0 / Pn - xhat s1 / Pn); padding rows, and every row when Pn == 0: dx = 0.
+ *                              dx may be g. */
+int afi_roi_cascade_relabel(const float* pred, long long ld_pred, int N, int B, int K, const float* proposals, const int* counts,
+                            const float* image_hw, float wx, float wy, float ww, float wh, double scale_clamp, const float* gt,
+                            const int* gt_classes, const int* counts_g, int Gmax, float iou_thresh, float* boxes, int* counts_out, int* classes,
+                            float* gt_boxes, int* src, int* matched_idx, void* stream);
+int afi_roi_bn_stats(const float* x, const int* counts, int N, int B, int P1, int C, float eps, float momentum, float* mean, float* invstd,
+                     float* var_biased_or_null, float* running_mean_or_null, float* running_var_or_null,
+                     long long* num_batches_tracked_or_null, float* scratch, void* stream);
+int afi_roi_bn_relu_fwd(const float* x, const int* counts, int N, int B, int P1, int C, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, int relu, float* y, void* stream);
+int afi_roi_bn_relu_bwd_sums(const float* g, const float* x, const float* y_or_null, const int* counts, int N, int B, int P1, int C,
+                             const float* mean, const float* invstd, int relu, float* dgamma_or_null, float* dbeta_or_null, float* sums2C,
+                             float* scratch, void* stream);
+int afi_roi_bn_relu_bwd_apply(const float* g, const float* x, const float* y_or_null, const int* counts, int N, int B, int P1, int C,
+                              const float* mean, const float* invstd, const float* gamma, const float* sums2C, int relu, float* dx,
+                              void* stream);
+
 /* ------------------------------------------------------------------ frozen mask branch of StandardROIHeads (afigan_amd/roi_heads.py)
  * detectron2 v0.1.1's mask_rcnn_inference and paste_masks_in_image.  The mask pooler is afi_roi_align on the padded detections, the head's 3x3
  * convs are the frozen conv dispatch, and the deconv (ConvTranspose2d kernel 2, stride 2) is one afi_conv1x1_fwd over a [4 Cout][Cin] weight
