@@ -10,21 +10,9 @@
 //                               fc2 + bias, the softmax over each radix pair.
 //   afi_resnest_splat_combine   pass 3: a0 * split0 + a1 * split1, optionally with the AVD 3/2/1 average pool fused in.
 // No atomics anywhere: every sum has one fixed order, so a forward is bit-identical from run to run and under hipGraph replay.
-#include "../../include/afigan_hip.h"
-#include "afi_common.h"
+#include "afi_resnest.h"
 
 #define RS_STEM_MAXC 128        // stem output channels held in LDS
-#define RS_GAP_BYTES 65536      // bytes of one split a gap block reads per chunk (chunk pixels = RS_GAP_BYTES / (4 C), at least a block's slots)
-#define RS_MAX_C 1024           // split width limit of the gap pass (C / 4 float4 lanes <= 256 threads)
-
-static inline unsigned grid_of(long long work, long long cap) {
-    long long b = (work + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-static inline bool view_ok(const afi_view_t& v) {
-    return v.p && !((uintptr_t)v.p & 15) && !(v.sN & 3) && !(v.sH & 3) && !(v.sW & 3);
-}
 
 // ------------------------------------------------------------------------------------------------ deep stem, first conv
 // x dense NCHW [N][3][H][W]; w dense [Cout][3][3][3] in (O, kh, kw, I) order; out dense [N][Ho][Wo][Cout].  One thread = one output pixel x
@@ -76,10 +64,6 @@ int afi_resnest_stem_fwd(const float* x, int N, int H, int W, const float* w, co
 }
 
 // ------------------------------------------------------------------------------------------------ pixel-major pooling
-__device__ __forceinline__ f32x4 ld4(const AfiView& v, int n, int y, int x, int c) {
-    return *(const f32x4*)(v.p + n * v.sN + y * v.sH + x * v.sW + c);
-}
-
 __global__ __launch_bounds__(256) void afi_resnest_pool_kernel(const AfiView x, int N, int H, int W, int C, int mode, int Ho, int Wo,
                                                               float* __restrict__ out) {
     const int C4 = C >> 2;
@@ -130,15 +114,7 @@ int afi_resnest_pool_nhwc(afi_view_t x, int N, int H, int W, int C, int mode, fl
 }
 
 // ------------------------------------------------------------------------------------------------ split attention (radix 2, cardinality 1)
-// The chunking of the pooled-sum pass, shared by its launcher, the attention pass and the workspace query: a 256-thread block holds
-// 256 / (C / 4) pixel slots x C / 4 float4 lanes and sums one chunk of about RS_GAP_BYTES per split.
-static inline int gap_slots(int C) { return 256 / (C >> 2); }
-static inline int gap_chunk_pix(int C) {
-    const int p = RS_GAP_BYTES / (4 * C), s = gap_slots(C);
-    return p > s ? p : s;
-}
-static inline int gap_chunks(int H, int W, int C) { return (int)(((long long)H * W + gap_chunk_pix(C) - 1) / gap_chunk_pix(C)); }
-
+// (the chunk geometry gap_slots / gap_chunk_pix / gap_chunks: afi_resnest.h)
 long long afi_resnest_splat_ws_floats(int N, int H, int W, int C) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || C > RS_MAX_C) return 0;
     return (long long)N * gap_chunks(H, W, C) * C;
@@ -207,7 +183,8 @@ __device__ __forceinline__ void dot4rows(const float* __restrict__ w, int K, int
 __global__ __launch_bounds__(RS_ATTN_THREADS) void afi_resnest_splat_attn_kernel(const float* __restrict__ part, int nchunk, int C, int I,
                                                                                 float hw, const float* __restrict__ w1,
                                                                                 const float* __restrict__ b1, const float* __restrict__ w2,
-                                                                                const float* __restrict__ b2, float* __restrict__ att) {
+                                                                                const float* __restrict__ b2, float* __restrict__ att,
+                                                                                float* __restrict__ g_keep, float* __restrict__ h_keep) {
     __shared__ f32x4 red[RS_ATTN_THREADS];
     extern __shared__ f32x4 sm4[];
     float* gap = (float*)sm4;
@@ -225,12 +202,17 @@ __global__ __launch_bounds__(RS_ATTN_THREADS) void afi_resnest_splat_attn_kernel
         f32x4 s = red[tid];
         for (int j = 1; j < slots; ++j) s += red[j * C4 + tid];
         *(f32x4*)(gap + c) = s / hw;
+        if (g_keep) *(f32x4*)(g_keep + (long long)n * C + c) = s / hw;
     }
     __syncthreads();
     for (int j0 = wave * 4; j0 < I; j0 += RS_ATTN_THREADS / 16) {          // fc1 with bn1 folded, ReLU
         float d[4];
         dot4rows(w1, C, j0, gap, lane, d);
-        if (lane < 4) h[j0 + lane] = fmaxf((lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : d[3]) + b1[j0 + lane], 0.f);
+        if (lane < 4) {
+            const float v = fmaxf((lane == 0 ? d[0] : lane == 1 ? d[1] : lane == 2 ? d[2] : d[3]) + b1[j0 + lane], 0.f);
+            h[j0 + lane] = v;
+            if (h_keep) h_keep[(long long)n * I + j0 + lane] = v;
+        }
     }
     __syncthreads();
     for (int o0 = wave * 4; o0 < 2 * C; o0 += RS_ATTN_THREADS / 16) {      // fc2 + bias
@@ -247,14 +229,27 @@ __global__ __launch_bounds__(RS_ATTN_THREADS) void afi_resnest_splat_attn_kernel
     }
 }
 
-int afi_resnest_splat_attn(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
-                           const float* b2, float* att, void* stream) {
+static int splat_attn_launch(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
+                             const float* b2, float* att, float* g_keep, float* h_keep, void* stream) {
     if (!part || !w1 || !b1 || !w2 || !b2 || !att || N <= 0 || H <= 0 || W <= 0 || C <= 0 || I <= 0) return AFI_ERR_BAD_ARG;
     if ((C & 3) || (I & 3) || C > RS_MAX_C || I > 4 * RS_MAX_C || ((uintptr_t)w1 & 15) || ((uintptr_t)w2 & 15)) return AFI_ERR_UNSUPPORTED;
     const size_t lds = (size_t)(3 * C + I) * sizeof(float);
     hipLaunchKernelGGL(afi_resnest_splat_attn_kernel, dim3(N), dim3(RS_ATTN_THREADS), lds, (hipStream_t)stream, part, gap_chunks(H, W, C), C, I,
-                       (float)((double)H * W), w1, b1, w2, b2, att);
+                       (float)((double)H * W), w1, b1, w2, b2, att, g_keep, h_keep);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+int afi_resnest_splat_attn(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
+                           const float* b2, float* att, void* stream) {
+    return splat_attn_launch(part, N, H, W, C, I, w1, b1, w2, b2, att, nullptr, nullptr, stream);
+}
+
+// the training forward: the same pass, also keeping g [N][C] (the pooled mean) and h [N][I] (fc1's post-ReLU output) for the backward
+int afi_resnest_splat_attn_keep(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
+                                const float* b2, float* att, float* g, float* h, void* stream) {
+    if (!g || !h) return AFI_ERR_BAD_ARG;
+    if (((uintptr_t)g & 15)) return AFI_ERR_UNSUPPORTED;
+    return splat_attn_launch(part, N, H, W, C, I, w1, b1, w2, b2, att, g, h, stream);
 }
 
 // out dense [N][Ho][Wo][C] = a0 * s0 + a1 * s1 per channel (avd 0: Ho = H), or its AvgPool2d(3, 2, padding 1) (avd 1: Ho = ceil(H / 2),

@@ -4,9 +4,10 @@ afi_detector_sgd_step launch, the trainer loop around it, and the step-3 meta-ar
   * ``DetectorOptim`` -- torch.optim.SGD as ``build_optimizer`` configures it (solver/build.py: per-parameter groups by key: ``norm.weight`` /
     ``norm.bias`` take WEIGHT_DECAY_NORM, other ``.bias`` keys BASE_LR * BIAS_LR_FACTOR and WEIGHT_DECAY_BIAS, the rest BASE_LR and
     WEIGHT_DECAY), every group's rate under one warm-up / multi-step factor.  ``zero_grad()`` / ``step()``: it drops into
-    ``Stage2Step(optimizer=...)``.  One kernel updates every parameter that has a gradient and, for the trainable convs of a
-    ``resnet_guide.ResNet``, writes the FrozenBN-folded weight beside the new one, so the next forward finds its prepared weights current
-    instead of refolding all convs in torch fp64.
+    ``Stage2Step(optimizer=...)``.  One kernel updates every parameter that has a gradient and, for the trainable bias-free convs of a
+    ``resnet_guide.ResNet`` or a ``resnest_backbone.ResNeSt``, writes the FrozenBN-folded weight beside the new one, so the next forward
+    finds its prepared weights current instead of refolding all convs in torch fp64 (a ResNeSt's tiny fc1 / fc2, whose fold depends on a
+    trainable bias, sit in a prepared slot of their own that the module refolds itself).
   * ``DetectorStep`` -- detectron2's ``SimpleTrainer.run_step`` (the reference's ``Target_Detector_Trainer``, step 3).
   * ``GeneralizedRCNN`` -- the step-3 detector: ``GeneralizedRCNN_AFExtractor`` on ``image`` / ``instances``, returning the loss dict alone.
 
@@ -41,14 +42,14 @@ class DetectorOptim:
     """torch.optim.SGD over detectron2's parameter groups and schedule, one launch per step (module docstring).
 
     `modules`: the modules of the model (``model.modules()``; ``build_detector_optimizer`` passes them).  The trainable
-    ``resnet_guide.ResNet`` bottom-ups among them get their folded weights written by the step.  One that is left out -- the default ``()``
+    ``resnet_guide.ResNet`` / ``resnest_backbone.ResNeSt`` bottom-ups among them get their folded weights written by the step.  One that is left out -- the default ``()``
     names none -- is still updated correctly, as plain tensors, but its next forward then refolds every conv: right, and slow."""
     FLAT_GRID = False                    # the (<= 512, ntensors) grid: the flat grid over work units measured the same (DESIGN 26) and needs a prefix table
 
     def __init__(self, named_params, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, weight_decay_norm: float = 0.0,
                  bias_lr_factor: float = 1.0, weight_decay_bias: float = 1e-4, lr_steps: Sequence[int] = (30000,), lr_gamma: float = 0.1,
                  warmup_factor: float = 1e-3, warmup_iters: int = 1000, modules=()):
-        from .resnet_guide import ResNet
+        from .resnet_guide import ResNetBase
         named = [(n, p) for n, p in named_params if p.requires_grad]
         if not named:
             raise AfiError("DetectorOptim: no parameter requires grad")
@@ -66,7 +67,7 @@ class DetectorOptim:
         offs = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in sizes])])             # every segment starts 16-byte aligned
         self._offs = [int(o) for o in offs[:-1]]
         self.flat_mom = torch.zeros(int(offs[-1]), device=dev, dtype=torch.float32)            # one buffer, each segment in its parameter's memory order
-        self.modules = [m for m in modules if isinstance(m, ResNet) and m._train_stages]
+        self.modules = [m for m in modules if isinstance(m, ResNetBase) and m._train_stages]      # a trainable ResNet or ResNeSt
         self.iter = 0
         self.relayouts = 0                                                                     # gradients that arrived in other strides than their parameter's
         self.device = dev

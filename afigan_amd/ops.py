@@ -373,15 +373,19 @@ def conv3x3_wino_infer(x, w, bias=None, act=0):
     return out
 
 
-def conv3x3_wino_dgrad(dy, w, z=None, *, z_act=None):
-    """Data gradient of the 3x3 conv in Winograd form: dx = conv^T(dy) [* lrelu'(z)]; z_act "lrelu" / "relu": afi_conv3x3_wino_dgrad_act."""
-    _check_cuda(dy, w, z)
+def conv3x3_wino_dgrad(dy, w, z=None, *, z_act=None, dx=None):
+    """Data gradient of the 3x3 conv in Winograd form: dx = conv^T(dy) [* lrelu'(z)]; z_act "lrelu" / "relu": afi_conv3x3_wino_dgrad_act.
+    dx=: the (pixel-major, possibly channel-sliced) tensor to write instead of a fresh one."""
+    _check_cuda(dy, w, z, dx)
     N, Cout, H, W = dy.shape
     Cin = w.shape[1]
     w = ohwi(w)
     n = _lib.load().afi_conv3x3_wino_ws_floats(N, H, W, Cin, Cout)
     ws = new_workspace(n, dy.device)
-    dx = new_pixel_major(N, Cin, H, W, dy.device)
+    if dx is None:
+        dx = new_pixel_major(N, Cin, H, W, dy.device)
+    elif tuple(dx.shape) != (N, Cin, H, W):
+        raise _lib.AfiError(f"conv3x3_wino_dgrad: dx {tuple(dx.shape)} is not the conv's input shape {(N, Cin, H, W)}")
     if z_act is not None:
         call("afi_conv3x3_wino_dgrad_act", view_of(dy), N, H, W, Cout, _p(w), Cin, view_of(dx), view_of(z), _z_act("conv3x3_wino_dgrad", z, z_act),
              _p(ws), n, stream_ptr())
@@ -836,10 +840,11 @@ def resnest_pool(x, mode):
     return out
 
 
-def splat_attention(s0, s1, w1, b1, w2, b2, avd=False):
+def splat_attention(s0, s1, w1, b1, w2, b2, avd=False, keep=False):
     """Split attention (radix 2) over two pixel-major splits [N,C,H,W] (bn0 + ReLU already applied), in three passes: per-chunk channel sums
     of s0 + s1, the per-image attention att = rsoftmax(fc2(relu(fc1(mean)))) with w1 [I,C] (bn1 folded) and w2 [2C,I], and the combine
-    att0 * s0 + att1 * s1 -- with avd, its avg_pool2d(3, 2, 1) in the same pass.  Returns (out, att [N, 2C])."""
+    att0 * s0 + att1 * s1 -- with avd, its avg_pool2d(3, 2, 1) in the same pass.  Returns (out, att [N, 2C]); with `keep` (the training
+    forward, afi_resnest_splat_attn_keep: the same kernel) (out, att, g [N, C], h [N, I]), the pooled mean and fc1's post-ReLU output."""
     _check_cuda(s0, s1, w1, b1, w2, b2)
     N, C_, H, W = s0.shape
     I = w1.shape[0]
@@ -852,11 +857,113 @@ def splat_attention(s0, s1, w1, b1, w2, b2, avd=False):
     part = new_workspace(n, s0.device)
     att = torch.empty((N, 2 * C_), device=s0.device, dtype=torch.float32)
     call("afi_resnest_splat_gap", view_of(s0), view_of(s1), N, H, W, C_, _p(part), n, stream_ptr())
-    call("afi_resnest_splat_attn", _p(part), N, H, W, C_, I, _p(w1), _p(b1.contiguous()), _p(w2), _p(b2.contiguous()), _p(att), stream_ptr())
+    if keep:
+        g, h = torch.empty((N, C_), device=s0.device, dtype=torch.float32), torch.empty((N, I), device=s0.device, dtype=torch.float32)
+        call("afi_resnest_splat_attn_keep", _p(part), N, H, W, C_, I, _p(w1), _p(b1.contiguous()), _p(w2), _p(b2.contiguous()), _p(att), _p(g),
+             _p(h), stream_ptr())
+    else:
+        call("afi_resnest_splat_attn", _p(part), N, H, W, C_, I, _p(w1), _p(b1.contiguous()), _p(w2), _p(b2.contiguous()), _p(att), stream_ptr())
     Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if avd else (H, W)
     out = new_pixel_major(N, C_, Ho, Wo, s0.device)
     call("afi_resnest_splat_combine", view_of(s0), view_of(s1), N, H, W, C_, _p(att), int(bool(avd)), _p(out), stream_ptr())
-    return out, att
+    return (out, att, g, h) if keep else (out, att)
+
+
+def _splat_bwd_shapes(name, dout, s0, s1, att, avd):
+    N, C_, H, W = s0.shape
+    want = (N, C_, (H + 1) // 2, (W + 1) // 2) if avd else (N, C_, H, W)
+    if tuple(s1.shape) != (N, C_, H, W) or tuple(dout.shape) != want or tuple(att.shape) != (N, 2 * C_):
+        raise _lib.AfiError(f"{name}: splits {tuple(s0.shape)} / {tuple(s1.shape)}, dout {tuple(dout.shape)} (expected {want}), att {tuple(att.shape)}")
+    return N, C_, H, W
+
+
+def splat_bwd_dots(dout, s0, s1, avd=False):
+    """part [N, chunks, 2, C]: per-chunk sums over the pixels of du * s0 and du * s1 (afi_resnest_splat_bwd_dots), du the cotangent of the
+    combine's un-pooled output: `dout` itself, or with avd the transposed avg_pool2d(3, 2, 1) of dout, gathered and never stored."""
+    _check_cuda(dout, s0, s1)
+    N, C_, H, W = s0.shape
+    n = _lib.load().afi_resnest_splat_bwd_ws_floats(N, H, W, C_)
+    if n <= 0:
+        raise _lib.AfiError(f"splat_bwd_dots: unsupported split width {C_}")
+    part = new_workspace(n, s0.device)
+    call("afi_resnest_splat_bwd_dots", view_of(dout), view_of(s0), view_of(s1), N, H, W, C_, int(bool(avd)), _p(part), n, stream_ptr())
+    return part.view(N, -1, 2, C_)
+
+
+def splat_bwd_attn(part, hw, att, h, w1, w2):
+    """(dz [N,2C], dh [N,I], dg [N,C]) from the partials of splat_bwd_dots (afi_resnest_splat_bwd_attn): dz0 = a0 a1 (da0 - da1), dz1 = -dz0,
+    dh = (w2^T dz) [h > 0], dg = w1^T dh / (H W); w1 [I,C] with bn1 folded, hw = (H, W) of the splits."""
+    _check_cuda(part, att, h, w1, w2)
+    N, C_, I = att.shape[0], att.shape[1] // 2, h.shape[1]
+    w1, w2 = w1.reshape(I, C_).contiguous(), w2.reshape(2 * C_, I).contiguous()
+    if tuple(part.shape) != (N, part.shape[1], 2, C_) or not part.is_contiguous() or tuple(h.shape) != (N, I):
+        raise _lib.AfiError(f"splat_bwd_attn: part {tuple(part.shape)}, att {tuple(att.shape)}, h {tuple(h.shape)}")
+    if part.numel() != _lib.load().afi_resnest_splat_bwd_ws_floats(N, hw[0], hw[1], C_):
+        raise _lib.AfiError(f"splat_bwd_attn: part {tuple(part.shape)} is not the partials of a {hw[0]}x{hw[1]} map of {C_} channels")
+    dz, dh, dg = (torch.empty((N, k), device=att.device, dtype=torch.float32) for k in (2 * C_, I, C_))
+    call("afi_resnest_splat_bwd_attn", _p(part), N, hw[0], hw[1], C_, I, _p(att.contiguous()), _p(h.contiguous()), _p(w1), _p(w2), _p(dz), _p(dh),
+         _p(dg), stream_ptr())
+    return dz, dh, dg
+
+
+def splat_bwd_params(dz, dh, g, h, s1_scale, dw1, db1, dw2, db2):
+    """dw2 += sum_n dz_n (x) h_n, db2 += sum_n dz_n, dw1 += s1 * sum_n dh_n (x) g_n, db1 += s1 * sum_n dh_n (afi_resnest_splat_bwd_params):
+    straight into the gradients of fc1.{weight,bias} / fc2.{weight,bias} (contiguous), s1_scale [I] the fold scale of bn1."""
+    _check_cuda(dz, dh, g, h, s1_scale, dw1, db1, dw2, db2)
+    N, C_, I = g.shape[0], g.shape[1], h.shape[1]
+    for name, t, n in (("dw1", dw1, I * C_), ("db1", db1, I), ("dw2", dw2, 2 * C_ * I), ("db2", db2, 2 * C_), ("s1_scale", s1_scale, I),
+                       ("dz", dz, N * 2 * C_), ("dh", dh, N * I)):
+        if t.numel() != n or not t.is_contiguous():
+            raise _lib.AfiError(f"splat_bwd_params: {name} {tuple(t.shape)} is not a contiguous tensor of {n} elements")
+    call("afi_resnest_splat_bwd_params", _p(dz), _p(dh), _p(g.contiguous()), _p(h.contiguous()), _p(s1_scale), N, C_, I, _p(dw1), _p(db1), _p(dw2),
+         _p(db2), stream_ptr())
+
+
+def splat_bwd_combine(dout, s0, s1, att, dg, avd=False, ds0=None, ds1=None):
+    """ds_r = (att_r du + dg) * [s_r > 0] for r = 0, 1 (afi_resnest_splat_bwd_combine); ds0 / ds1 may be views, e.g. the halves of one
+    [N,2C,H,W] tensor.  Masked elements are exact zeros."""
+    _check_cuda(dout, s0, s1, att, dg, ds0, ds1)
+    N, C_, H, W = _splat_bwd_shapes("splat_bwd_combine", dout, s0, s1, att, avd)
+    if ds0 is None:
+        ds0 = new_pixel_major(N, C_, H, W, s0.device)
+    if ds1 is None:
+        ds1 = new_pixel_major(N, C_, H, W, s0.device)
+    if tuple(ds0.shape) != (N, C_, H, W) or tuple(ds1.shape) != (N, C_, H, W) or tuple(dg.shape) != (N, C_):
+        raise _lib.AfiError(f"splat_bwd_combine: ds0 {tuple(ds0.shape)} / ds1 {tuple(ds1.shape)} / dg {tuple(dg.shape)} for splits {tuple(s0.shape)}")
+    call("afi_resnest_splat_bwd_combine", view_of(dout), view_of(s0), view_of(s1), N, H, W, C_, _p(att.contiguous()), _p(dg.contiguous()),
+         int(bool(avd)), view_of(ds0), view_of(ds1), stream_ptr())
+    return ds0, ds1
+
+
+def splat_attention_bwd(dout, s0, s1, att, g, h, w1, w2, s1_scale, avd, dw1, db1, dw2, db2, ds0=None, ds1=None):
+    """The backward of `splat_attention` in four passes: splat_bwd_dots, splat_bwd_attn, splat_bwd_params (adding into the
+    gradients dw1, db1, dw2, db2 of fc1 / fc2's PARAMETERS) and splat_bwd_combine.  Returns (ds0, ds1), the gradients of the two splits'
+    pre-activations."""
+    N, C_, H, W = _splat_bwd_shapes("splat_attention_bwd", dout, s0, s1, att, avd)
+    part = splat_bwd_dots(dout, s0, s1, avd)
+    dz, dh, dg = splat_bwd_attn(part, (H, W), att, h, w1, w2)
+    splat_bwd_params(dz, dh, g, h, s1_scale, dw1, db1, dw2, db2)
+    return splat_bwd_combine(dout, s0, s1, att, dg, avd, ds0, ds1)
+
+
+def resnest_pool_bwd(dy, mode, dx=None, beta=0.0, z=None, in_hw=None):
+    """dx = (beta * dx + pool^T(dy)) [* (z > 0)] (afi_resnest_pool_bwd) for "avg2s2_ceil" / "avg3s2p1" of `resnest_pool`; dx and z may be
+    views of pixel-major tensors; without dx, in_hw = (H, W) of the pool's input names its size.  "max3s2p1" is refused by the library."""
+    _check_cuda(dy, dx, z)
+    N, C_, Ho, Wo = dy.shape
+    if dx is None:
+        if in_hw is None:
+            raise _lib.AfiError("resnest_pool_bwd: dx= or in_hw= names the size of the pool's input")
+        dx = new_pixel_major(N, C_, in_hw[0], in_hw[1], dy.device)
+    H, W = dx.shape[2:]
+    if tuple(dx.shape[:2]) != (N, C_) or ((H + 1) // 2, (W + 1) // 2) != (Ho, Wo) or (z is not None and z.shape != dx.shape):
+        raise _lib.AfiError(f"resnest_pool_bwd: dy {tuple(dy.shape)} is not the pooled size of dx {tuple(dx.shape)}"
+                            + (f" / z {tuple(z.shape)}" if z is not None else ""))
+    if not is_dense_pm(dy):
+        raise _lib.AfiError("resnest_pool_bwd: dy must be a dense pixel-major tensor")
+    call("afi_resnest_pool_bwd", _p(dy), N, H, W, C_, POOL_MODES[mode], view_of(dx), float(beta), view_of(z) if z is not None else _NULL_VIEW,
+         stream_ptr())
+    return dx
 
 
 # ------------------------------------------------------------------------------------------------ frozen Swin bottom-up (swin_backbone.py)

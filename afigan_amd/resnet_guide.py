@@ -103,6 +103,9 @@ def _dense_pm(t, like):
     return t
 
 
+dense_cotangent = _dense_pm              # (the name resnest_backbone's _ResNeStTrainFn imports)
+
+
 class _ResNetTrainFn(torch.autograd.Function):
     """The trainable stages of a ResNet bottom-up as one node: ``(net, fuse_masks, x, *weights) -> out_features of those stages``, x the first
     trainable stage's input (no gradient: the stages below are frozen), weights the conv weights of ``net._train_convs()`` in that order.

@@ -589,6 +589,38 @@ int afi_resnest_splat_attn(const float* part, int N, int H, int W, int C, int I,
                            const float* b2, float* att, void* stream);
 int afi_resnest_splat_combine(afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, const float* att, int avd, float* out, void* stream);
 
+/* ------------------------------------------------------------------ the ResNeSt bottom-up in training
+ * The backward of split attention and of the two average pools; a block's convs go back through the conv entry points above.  With
+ * g = mean_HW(s0 + s1) [N][C], h = relu(w1 g + b1) [N][I] (bn1 folded), z = w2 h + b2, (a0, a1) = the pair softmax (att), u = a0 s0 + a1 s1 and
+ * out = avd ? AvgPool2d(3, 2, 1)(u) : u, dout [N][Ho][Wo][C] is out's cotangent (Ho = avd ? ceil(H/2) : H) and du, u's, is dout itself or, with
+ * avd, the transposed pool GATHERED: a u pixel adds the 1, 2 or 4 dout pixels whose windows hold it (ascending) and divides by 9; du is never
+ * stored.  C % 4 == 0, C <= 1024, I % 4 == 0, I <= 2048, N <= 65535, every pointer and view 16-byte aligned with strides multiples of 4
+ * (AFI_ERR_UNSUPPORTED otherwise).  No atomics: every sum has one fixed order, every result is bit-identical from run to run.
+ *   afi_resnest_splat_attn_keep    afi_resnest_splat_attn (same kernel, bit-identical att) also storing g and h.
+ *   afi_resnest_splat_bwd_dots     part [N][chunks][2][C] = per-chunk sums over pixels of du s0 and du s1, on afi_resnest_splat_gap's chunks,
+ *                                  accumulated in fp64 and rounded once (da0 - da1 cancels in the next pass);
+ *                                  part_floats >= afi_resnest_splat_bwd_ws_floats (AFI_ERR_WORKSPACE otherwise).
+ *   afi_resnest_splat_bwd_attn     one block per image: da_r = the chunks of `part` in order; dz [N][2C]: dz0 = a0 a1 (da0 - da1), dz1 = -dz0;
+ *                                  dh [N][I] = (w2^T dz) [h > 0]; dg [N][C] = w1^T dh / (H W).
+ *   afi_resnest_splat_bwd_params   dw2 [2C][I] += sum_n dz_n (x) h_n, db2 [2C] += sum_n dz_n, dw1 [I][C] += s1 * sum_n dh_n (x) g_n,
+ *                                  db1 [I] += s1 * sum_n dh_n: the gradients of the PARAMETERS (s1 [I] is bn1's fold scale), n ascending.
+ *   afi_resnest_splat_bwd_combine  ds_r = (a_r du + dg) [s_r > 0] for r = 0, 1, written through the views ds0, ds1 (exact zeros where masked).
+ *   afi_resnest_pool_bwd           dx = (beta dx + pool^T(dy)) [* (z > 0)] for x [N][H][W][C] (dx, z views; dy dense [N][ceil(H/2)][ceil(W/2)][C]):
+ *                                  AFI_POOL_AVG2S2_CEIL dy / the pixels its window covered; AFI_POOL_AVG3S2P1 the gather above; dx is read only
+ *                                  with beta != 0.  AFI_POOL_MAX3S2P1: AFI_ERR_UNSUPPORTED (the max-pool's backward does not exist). */
+int afi_resnest_splat_attn_keep(const float* part, int N, int H, int W, int C, int I, const float* w1, const float* b1, const float* w2,
+                                const float* b2, float* att, float* g, float* h, void* stream);
+long long afi_resnest_splat_bwd_ws_floats(int N, int H, int W, int C);
+int afi_resnest_splat_bwd_dots(afi_view_t dout, afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, int avd, float* part,
+                               long long part_floats, void* stream);
+int afi_resnest_splat_bwd_attn(const float* part, int N, int H, int W, int C, int I, const float* att, const float* h, const float* w1,
+                               const float* w2, float* dz, float* dh, float* dg, void* stream);
+int afi_resnest_splat_bwd_params(const float* dz, const float* dh, const float* g, const float* h, const float* s1, int N, int C, int I,
+                                 float* dw1, float* db1, float* dw2, float* db2, void* stream);
+int afi_resnest_splat_bwd_combine(afi_view_t dout, afi_view_t s0, afi_view_t s1, int N, int H, int W, int C, const float* att, const float* dg,
+                                  int avd, afi_view_t ds0, afi_view_t ds1, void* stream);
+int afi_resnest_pool_bwd(const float* dy, int N, int H, int W, int C, int mode, afi_view_t dx, float beta, afi_view_t z_or_null, void* stream);
+
 /* ------------------------------------------------------------------ frozen Swin Transformer bottom-up (afigan_amd/swin_backbone.py)
  * SwinTransformer (patch 4, head dim 32, window 7 or 12, no APE), forward only.  Its linears are afi_conv1x1_fwd over pixel-major tokens;
  * these cover the rest.  Outputs are dense pixel-major, channel counts multiples of 4, views 16-byte aligned with strides multiples of 4
