@@ -10,29 +10,7 @@
 //                          P V, and writes each real query's result to its un-rolled, cropped pixel.
 // No atomics anywhere: every sum has one fixed order, so a forward is bit-identical from run to run and under hipGraph replay.
 #include "../../include/afigan_hip.h"
-#include "afi_common.h"
-
-#define SW_EMBED_MAXC 256       // patch-embed channels (4 per lane)
-#define SW_LN_MAXV 12           // float4s per lane of a LayerNorm token: 12 * 4 * 64 = 3072 channels (4C of Swin-L's last merge)
-#define SW_HEAD_DIM 32
-#define SW_LDS_LD 36            // LDS row stride of the q / k / v tiles: 36 j + k (k < 4) covers 64 banks with 16 rows, and rows stay 16-byte aligned
-
-typedef float f32x4_mfma __attribute__((ext_vector_type(4)));
-
-static inline unsigned grid_of(long long work, long long per_block, long long cap) {
-    long long b = (work + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-static inline bool view_ok(const afi_view_t& v) {
-    return v.p && !((uintptr_t)v.p & 15) && !(v.sN & 3) && !(v.sH & 3) && !(v.sW & 3);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+#include "afi_swin.h"             // the constants, grid_of, view_ok and wave_sum, shared with swin_train.hip
 
 // ------------------------------------------------------------------------------------------------ patch embed
 // x dense NCHW [N][3][H][W]; w dense [C][3][4][4]; out dense [N][Ho][Wo][C], Ho = ceil(H/4).  One wave = one output pixel: lanes 0..47 hold
@@ -188,7 +166,8 @@ int afi_swin_gelu(float* x, long long n, void* stream) {
 // Window token t (row t / WS, column t % WS of the window at (wy0, wx0) of the rolled, padded Hp x Wp map) is pixel
 // ((wy0 + t / WS + shift) % Hp, (wx0 + t % WS + shift) % Wp) of the un-rolled map: torch.roll(x, -shift) then window_partition.  A pixel
 // outside H x W is a padded token: its q / k / v are the qkv bias exactly (norm1 runs before the zero padding).  Tokens t >= WS^2 (the tile
-// padding) are zero and are excluded from every softmax.
+// padding) are zero and are excluded from every softmax.  The kernel states this roll / region rule inline; afi_swin.h's swin_window_token is the
+// same rule for the backward kernels of swin_train.hip: a change to one is a change to both.
 // With the f32 MFMA 16x16x4 (A[l & 15][l >> 4], B[l >> 4][l & 15], D col l & 15, row 4 (l >> 4) + r) the wave computes S^T = K Q^T, so lane
 // l holds the scores of query i = 16 ti + (l & 15) against keys 16 tj + 4 (l >> 4) + r: a softmax row is spread over 4 lanes (shfl_xor 16,
 // 32), and the probabilities, in registers, are already the A operand of O = P V (k step (tj, r) <-> keys 16 tj + 4 k + r).

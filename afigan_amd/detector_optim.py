@@ -3,7 +3,8 @@ afi_detector_sgd_step launch, the trainer loop around it, and the step-3 meta-ar
 
   * ``DetectorOptim`` -- torch.optim.SGD as ``build_optimizer`` configures it (solver/build.py: per-parameter groups by key: ``norm.weight`` /
     ``norm.bias`` take WEIGHT_DECAY_NORM, other ``.bias`` keys BASE_LR * BIAS_LR_FACTOR and WEIGHT_DECAY_BIAS, the rest BASE_LR and
-    WEIGHT_DECAY), every group's rate under one warm-up / multi-step factor.  ``zero_grad()`` / ``step()``: it drops into
+    WEIGHT_DECAY; the parameters of ``nn.LayerNorm`` modules take WEIGHT_DECAY_NORM by module type, whatever their key: a Swin's norm1 /
+    norm2 / norm{i}), every group's rate under one warm-up / multi-step factor.  ``zero_grad()`` / ``step()``: it drops into
     ``Stage2Step(optimizer=...)``.  One kernel updates every parameter that has a gradient and, for the trainable bias-free convs of a
     ``resnet_guide.ResNet`` or a ``resnest_backbone.ResNeSt``, writes the FrozenBN-folded weight beside the new one, so the next forward
     finds its prepared weights current instead of refolding all convs in torch fp64 (a ResNeSt's tiny fc1 / fc2, whose fold depends on a
@@ -34,6 +35,21 @@ def param_group(name, base_lr=0.001, weight_decay=1e-4, weight_decay_norm=0.0, b
     return base_lr, weight_decay
 
 
+def norm_module_params(model):
+    """The parameters build_optimizer gives WEIGHT_DECAY_NORM by MODULE TYPE, which `param_group`'s key suffix misses: those of every
+    ``nn.LayerNorm`` (detectron2 v0.1.1's list names it beside the BatchNorm family; here only LayerNorm has keys -- norm1, norm2, norm0 ..
+    -- that do not end in ``norm.weight`` / ``norm.bias``)."""
+    return [p for m in model.modules() if isinstance(m, torch.nn.LayerNorm) for p in m.parameters(recurse=False)]
+
+
+def param_groups(named_params, norm_params=(), base_lr=0.001, weight_decay=1e-4, weight_decay_norm=0.0, bias_lr_factor=1.0, weight_decay_bias=1e-4):
+    """[(lr, weight_decay)] per (name, parameter): `param_group` by key, except that a parameter among `norm_params` (``norm_module_params``)
+    takes the norm group whatever its key."""
+    norm_ids = {id(p) for p in norm_params}
+    return [(base_lr, weight_decay_norm) if id(p) in norm_ids else
+            param_group(n, base_lr, weight_decay, weight_decay_norm, bias_lr_factor, weight_decay_bias) for n, p in named_params]
+
+
 def _same_layout(a, b):
     return a.shape == b.shape and all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n != 1)
 
@@ -48,7 +64,7 @@ class DetectorOptim:
 
     def __init__(self, named_params, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, weight_decay_norm: float = 0.0,
                  bias_lr_factor: float = 1.0, weight_decay_bias: float = 1e-4, lr_steps: Sequence[int] = (30000,), lr_gamma: float = 0.1,
-                 warmup_factor: float = 1e-3, warmup_iters: int = 1000, modules=()):
+                 warmup_factor: float = 1e-3, warmup_iters: int = 1000, modules=(), norm_params=()):
         from .resnet_guide import ResNetBase
         named = [(n, p) for n, p in named_params if p.requires_grad]
         if not named:
@@ -62,7 +78,7 @@ class DetectorOptim:
                 raise AfiError(f"DetectorOptim: {n} (shape {tuple(p.shape)}, strides {p.stride()}) is not dense in memory")
         self.base_lr, self.momentum = float(base_lr), float(momentum)
         self.sched = (tuple(lr_steps), lr_gamma, warmup_factor, warmup_iters)
-        self.groups = [param_group(n, self.base_lr, weight_decay, weight_decay_norm, bias_lr_factor, weight_decay_bias) for n in self.names]
+        self.groups = param_groups(named, norm_params, self.base_lr, weight_decay, weight_decay_norm, bias_lr_factor, weight_decay_bias)
         sizes = [p.numel() for p in self.params]
         offs = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in sizes])])             # every segment starts 16-byte aligned
         self._offs = [int(o) for o in offs[:-1]]
@@ -194,7 +210,7 @@ def build_detector_optimizer(cfg, model):
                          bias_lr_factor=cfg_get(s, "BIAS_LR_FACTOR", 1.0), weight_decay_bias=cfg_get(s, "WEIGHT_DECAY_BIAS", 1e-4),
                          lr_steps=tuple(cfg_get(s, "STEPS", (30000,))), lr_gamma=cfg_get(s, "GAMMA", 0.1),
                          warmup_factor=cfg_get(s, "WARMUP_FACTOR", 1.0 / 1000), warmup_iters=cfg_get(s, "WARMUP_ITERS", 1000),
-                         modules=list(model.modules()))
+                         modules=list(model.modules()), norm_params=norm_module_params(model))
 
 
 class DetectorStep:

@@ -1036,6 +1036,142 @@ def swin_window_attn(qkv, qkv_bias, bias_img, window, shift):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ training the Swin bottom-up
+def swin_layernorm_bwd(dy, x, gamma, eps=1e-5, merge=False, dx=None, beta=0.0, dgamma=None, dbeta=None, want_dx=True):
+    """The backward of ``swin_layernorm(x, gamma, ., eps, merge)`` for the dense pixel-major dy (afi_swin_layernorm_bwd): x-hat and rstd are
+    recomputed from x.  Returns dx = beta * dx + the input gradient, a pixel-major tensor of x's shape or the view given as ``dx=`` (with
+    merge: scattered to the four source pixels; every pixel of x receives exactly one store); ``want_dx=False``: None, only the parameter
+    gradients.  dgamma / dbeta (both or neither, contiguous [Ct]) += the sums over tokens of dy * x-hat / dy."""
+    _check_cuda(dy, x, gamma, dx, dgamma, dbeta)
+    N, C_, H, W = x.shape
+    Ct, Ho, Wo = (4 * C_, (H + 1) // 2, (W + 1) // 2) if merge else (C_, H, W)
+    if tuple(dy.shape) != (N, Ct, Ho, Wo) or not is_dense_pm(dy) or tuple(gamma.shape) != (Ct,):
+        raise _lib.AfiError(f"swin_layernorm_bwd: dy {tuple(dy.shape)} must be the dense pixel-major {(N, Ct, Ho, Wo)} and gamma [{Ct}] "
+                            f"(got {tuple(gamma.shape)})")
+    if (dgamma is None) != (dbeta is None):
+        raise _lib.AfiError("swin_layernorm_bwd: dgamma and dbeta go together")
+    for name, t in (("dgamma", dgamma), ("dbeta", dbeta)):
+        if t is not None and (tuple(t.shape) != (Ct,) or not t.is_contiguous()):
+            raise _lib.AfiError(f"swin_layernorm_bwd: {name} {tuple(t.shape)} must be a contiguous [{Ct}]")
+    if want_dx:
+        if dx is None:
+            if beta != 0.0:
+                raise _lib.AfiError("swin_layernorm_bwd: beta != 0 needs the dx= to add into")
+            dx = new_pixel_major(N, C_, H, W, x.device)
+        elif tuple(dx.shape) != (N, C_, H, W):
+            raise _lib.AfiError(f"swin_layernorm_bwd: dx {tuple(dx.shape)} is not x's shape {(N, C_, H, W)}")
+    elif dgamma is None:
+        raise _lib.AfiError("swin_layernorm_bwd: nothing to compute (no dx, no parameter gradients)")
+    ws, need = None, 0
+    if dgamma is not None:
+        need = int(_lib.load().afi_swin_layernorm_bwd_ws_floats(N, H, W, C_, int(bool(merge))))
+        ws = new_workspace(need, x.device)
+    call("afi_swin_layernorm_bwd", view_of(x), N, H, W, C_, _p(gamma.contiguous()), float(eps), int(bool(merge)), _p(dy),
+         view_of(dx) if want_dx else _NULL_VIEW, float(beta), _p(dgamma), _p(dbeta), _p(ws), need, stream_ptr())
+    return dx if want_dx else None
+
+
+def swin_gelu_bwd(dy, x, out=None):
+    """dy * (Phi(x) + x phi(x)), x the GELU's input; dense pixel-major tensors of one shape; ``out=dy`` runs in place (afi_swin_gelu_bwd)."""
+    _check_cuda(dy, x, out)
+    if out is None:
+        out = new_pixel_major(*x.shape, x.device)
+    if dy.shape != x.shape or out.shape != x.shape or not (is_dense_pm(x) and is_dense_pm(dy) and is_dense_pm(out)):
+        raise _lib.AfiError(f"swin_gelu_bwd: dense pixel-major tensors of one shape are required (x {tuple(x.shape)}, dy {tuple(dy.shape)})")
+    call("afi_swin_gelu_bwd", _p(x), _p(dy), _p(out), x.numel(), stream_ptr())
+    return out
+
+
+def swin_window_attn_bwd(dout, qkv, qkv_bias, bias_img, window, shift):
+    """The backward of ``swin_window_attn(qkv, qkv_bias, bias_img, window, shift)`` for dout [N,C,H,W] (afi_swin_window_attn_bwd).
+    Returns (dqkv_padded, ds_part):
+      dqkv_padded  pixel-major [N,3C,Hp,Wp] over the PADDED map: ``[:, :, :H, :W]`` is the gradient of qkv, the sum over every position (the
+                   padded ones too: their q / k / v are the bias) the gradient of qkv_bias;
+      ds_part      [N * groups, heads, NP, NP]: the sums of dS over groups of windows, what ``swin_bias_table_bwd`` reduces."""
+    _check_cuda(dout, qkv, qkv_bias, bias_img)
+    N, C3, H, W = qkv.shape
+    C_ = C3 // 3
+    if C3 % 3 or C_ % 32 or window not in SWIN_WINDOWS or not 0 <= shift < window or tuple(qkv_bias.shape) != (C3,) \
+            or tuple(dout.shape) != (N, C_, H, W):
+        raise _lib.AfiError(f"swin_window_attn_bwd: qkv {tuple(qkv.shape)} (head dim 32), dout {tuple(dout.shape)}, window {window} "
+                            f"(one of {SWIN_WINDOWS}), shift {shift}")
+    NP = (window * window + 15) // 16 * 16
+    heads = C_ // 32
+    if tuple(bias_img.shape) != (heads, NP, NP) or not bias_img.is_contiguous():
+        raise _lib.AfiError(f"swin_window_attn_bwd: bias image {tuple(bias_img.shape)}, expected dense {(heads, NP, NP)}")
+    Hp, Wp = -(-H // window) * window, -(-W // window) * window
+    lib = _lib.load()
+    groups = int(lib.afi_swin_window_attn_bwd_groups(N, H, W, C_, int(window)))
+    floats = int(lib.afi_swin_window_attn_bwd_ws_floats(N, H, W, C_, int(window)))
+    if groups <= 0 or floats != N * groups * heads * NP * NP:
+        raise _lib.AfiError(f"swin_window_attn_bwd: the library sizes the dS workspace as {floats} floats in {groups} groups")
+    dqkv = new_pixel_major(N, C3, Hp, Wp, qkv.device)
+    ds_part = new_workspace(floats, qkv.device).view(N * groups, heads, NP, NP)
+    call("afi_swin_window_attn_bwd", view_of(qkv), view_of(dout), N, H, W, C_, _p(qkv_bias.contiguous()), _p(bias_img), int(window), int(shift),
+         _p(dqkv), _p(ds_part), floats, stream_ptr())
+    return dqkv, ds_part
+
+
+def swin_bias_csr(index, window, rows):
+    """The CSR of a relative_position_index buffer as loaded, for ``swin_bias_table_bwd``: (row_off int32 [rows + 1], pairs int32 [window^4])
+    on the index's device, pairs = i * NP + j of the (i, j) with index[i, j] = r, ascending within each row.  Built on the host, once per
+    buffer (the caller caches it)."""
+    n = window * window
+    NP = (n + 15) // 16 * 16
+    idx = index.detach().reshape(-1).cpu().long()
+    if idx.numel() != n * n or int(idx.min()) < 0 or int(idx.max()) >= rows:
+        raise _lib.AfiError(f"swin_bias_csr: relative_position_index of {idx.numel()} entries does not index a {rows}-row table over window {window}")
+    order = torch.sort(idx, stable=True).indices                            # ascending r, then ascending (i, j)
+    pairs = ((order // n) * NP + order % n).to(torch.int32)
+    row_off = torch.zeros(rows + 1, dtype=torch.int64)
+    row_off[1:] = torch.cumsum(torch.bincount(idx, minlength=rows), 0)
+    return row_off.to(torch.int32).to(index.device), pairs.to(index.device)
+
+
+def swin_bias_table_bwd(ds_part, csr, window, dtable):
+    """dtable [R, heads] += the sum over ds_part's partials and the pairs of each table row (afi_swin_bias_table_bwd: fp64, one fixed order);
+    csr: ``swin_bias_csr``."""
+    _check_cuda(ds_part, dtable)
+    row_off, pairs = csr
+    NP = (window * window + 15) // 16 * 16
+    R, heads = dtable.shape
+    if ds_part.dim() != 4 or tuple(ds_part.shape[1:]) != (heads, NP, NP) or not ds_part.is_contiguous() or not dtable.is_contiguous() \
+            or row_off.numel() != R + 1 or pairs.numel() != (window * window) ** 2 or row_off.dtype != torch.int32 or pairs.dtype != torch.int32 \
+            or not (row_off.is_cuda and pairs.is_cuda):
+        raise _lib.AfiError(f"swin_bias_table_bwd: ds_part {tuple(ds_part.shape)} / dtable {tuple(dtable.shape)} / csr ({row_off.numel()}, "
+                            f"{pairs.numel()}) do not fit window {window} (partials [P, heads, {NP}, {NP}], int32 CSR on the GPU)")
+    need = int(_lib.load().afi_swin_bias_table_bwd_ws_floats(heads, int(window)))
+    ws = new_workspace(need, ds_part.device)
+    call("afi_swin_bias_table_bwd", _p(ds_part), ds_part.shape[0], heads, int(window), _p(row_off), _p(pairs), R, _p(dtable), _p(ws), need,
+         stream_ptr())
+    return dtable
+
+
+def swin_patch_gather(x):
+    """The zero-padded 4x4x3 patches of the NCHW batch x [N,3,H,W] as pixel-major [N,48,ceil(H/4),ceil(W/4)], channel 16 ci + 4 ky + kx: the
+    order of ``proj.weight.reshape(C, 48)``, so PatchEmbed's conv is a 1x1 over it (afi_swin_patch_gather)."""
+    _check_cuda(x)
+    N, Cin, H, W = x.shape
+    if Cin != 3:
+        raise _lib.AfiError(f"swin_patch_gather: a 3-channel batch only, got {tuple(x.shape)}")
+    out = new_pixel_major(N, 48, (H + 3) // 4, (W + 3) // 4, x.device)
+    call("afi_swin_patch_gather", _p(x.contiguous()), N, H, W, _p(out), stream_ptr())
+    return out
+
+
+def swin_scale_add(a, s, b, out=None):
+    """out = a + s[n] * b over dense pixel-major tensors (DropPath; a None: out = s[n] * b); s a [N] fp32 vector on the device
+    (afi_swin_scale_add).  ``out`` may be a or b."""
+    _check_cuda(a, s, b, out)
+    if out is None:
+        out = new_pixel_major(*b.shape, b.device)
+    N = b.shape[0]
+    if tuple(s.shape) != (N,) or not s.is_contiguous() or any(t is not None and (t.shape != b.shape or not is_dense_pm(t)) for t in (a, b, out)):
+        raise _lib.AfiError(f"swin_scale_add: dense pixel-major tensors of one shape and s [{N}] are required (b {tuple(b.shape)}, s {tuple(s.shape)})")
+    call("afi_swin_scale_add", _p(a), _p(b), _p(s), N, b.numel() // N, _p(out), stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ RPN selection (rpn.py)
 RPN_MAX_TOPK = 1024                         # per-level list length the selection kernels hold in LDS
 RPN_MAX_ANCHORS = 16

@@ -643,6 +643,46 @@ int afi_swin_gelu(float* x, long long n, void* stream);
 int afi_swin_window_attn(afi_view_t qkv, int N, int H, int W, int C, const float* qkv_bias, const float* bias_img, int window, int shift,
                          float* out, void* stream);
 
+/* ------------------------------------------------------------------ training the Swin bottom-up (afigan_amd/swin_backbone.py)
+ * The backward of the entry points above; the linears' gradients are afi_conv1x1_dgrad / _wgrad / afi_colsum_accum.  fp32, the constraints of
+ * the forward (AFI_ERR_UNSUPPORTED otherwise), no atomics: every result is bit-identical from run to run.
+ * afi_swin_layernorm_bwd: the backward of afi_swin_layernorm(x, ..., merge) for dy dense [N][Ho][Wo][Ct] (Ct = C, or 4C with merge): x-hat and
+ *   rstd are recomputed from x;  dx = beta dx + rstd (g - mean(g) - x-hat mean(g x-hat)), g = dy gamma, a view [N][H][W][C] (with merge the
+ *   four source pixels of every output token; quadrants past an odd edge are dropped); dx.p NULL: no dx.  dgamma / dbeta [Ct] (both or
+ *   neither) += sum over tokens of dy x-hat / dy: per-wave partials in ws (afi_swin_layernorm_bwd_ws_floats floats, 16-byte aligned; less:
+ *   AFI_ERR_WORKSPACE; read only after being written), added in fp64 in one fixed order (16 slices of consecutive rows, each ascending, then
+ *   the slice sums ascending).  afi_swin_layernorm_bwd_vecs(Ct): the float4s per
+ *   lane (2, 6 or 12) of the kernel instantiation a token of Ct channels runs on, -1 for a Ct the kernel does not take.
+ * afi_swin_gelu_bwd: dx[i] = dy[i] (Phi(x[i]) + x[i] phi(x[i])), x the GELU's input; dx may be dy; n % 4 == 0.
+ * afi_swin_window_attn_bwd: for afi_swin_window_attn(qkv, ...) and dout, a view [N][H][W][C]: dqkv dense [N][Hp][Wp][3C] over the PADDED map
+ *   (Hp, Wp = H, W rounded up to the window; Hp Wp 3C < 2^31), every position written: a padded position's entries are gradients of qkv_bias, so
+ *   d qkv_bias is the column sum of all of dqkv and the [H][W] crop is the gradient of qkv.  ds_part [N][groups][C/32][NP][NP] (groups =
+ *   afi_swin_window_attn_bwd_groups, floats = afi_swin_window_attn_bwd_ws_floats; fewer: AFI_ERR_WORKSPACE): the sum of dS = P (dP - rowsum(dP P))
+ *   over the windows of a group (at most 8 consecutive windows), every entry written.
+ * afi_swin_bias_table_bwd: dtable [R][heads] += sum over the nparts = N groups partials and the pairs (i, j) of table row r of ds_part[.][h][i][j],
+ *   in fp64 in a fixed order: first the partials of every (h, i, j) in ascending order (images, then groups of windows) into ws, heads NP NP
+ *   doubles (afi_swin_bias_table_bwd_ws_floats floats, 16-byte aligned; fewer: AFI_ERR_WORKSPACE), then the pairs of the row; row_off [R + 1] and
+ *   pairs (int32, DEVICE; pairs[p] = i NP + j < NP^2, ascending within a row) are the CSR of relative_position_index, which the caller builds and
+ *   answers for.
+ * afi_swin_patch_gather: out dense [N][ceil(H/4)][ceil(W/4)][48], channel 16 ci + 4 ky + kx = x[n][ci][4 oy + ky][4 ox + kx] of the dense NCHW
+ *   x [N][3][H][W], zero outside it: PatchEmbed's conv as a 1x1 over patches, in the order of proj.weight.reshape(C, 48).
+ * afi_swin_scale_add: out = a + s[n] b over dense [N][per_image] tensors (DropPath; s [N] on the device); a NULL: out = s[n] b; out may be a or b;
+ *   per_image % 4 == 0. */
+int afi_swin_layernorm_bwd_vecs(int Ct);
+long long afi_swin_layernorm_bwd_ws_floats(int N, int H, int W, int C, int merge);
+int afi_swin_layernorm_bwd(afi_view_t x, int N, int H, int W, int C, const float* gamma, float eps, int merge, const float* dy, afi_view_t dx,
+                           float beta, float* dgamma, float* dbeta, float* ws, long long ws_floats, void* stream);
+int afi_swin_gelu_bwd(const float* x, const float* dy, float* dx, long long n, void* stream);
+long long afi_swin_window_attn_bwd_ws_floats(int N, int H, int W, int C, int window);
+long long afi_swin_window_attn_bwd_groups(int N, int H, int W, int C, int window);
+int afi_swin_window_attn_bwd(afi_view_t qkv, afi_view_t dout, int N, int H, int W, int C, const float* qkv_bias, const float* bias_img, int window,
+                             int shift, float* dqkv, float* ds_part, long long ds_floats, void* stream);
+long long afi_swin_bias_table_bwd_ws_floats(int heads, int window);
+int afi_swin_bias_table_bwd(const float* ds_part, int nparts, int heads, int window, const int* row_off, const int* pairs, int R, float* dtable,
+                            float* ws, long long ws_floats, void* stream);
+int afi_swin_patch_gather(const float* x, int N, int H, int W, float* out, void* stream);
+int afi_swin_scale_add(const float* a, const float* b, const float* s, int N, long long per_image, float* out, void* stream);
+
 /* ------------------------------------------------------------------ frozen RPN proposal generator: selection (afigan_amd/rpn.py)
  * detectron2 v0.1.1's RPN at inference, after its head (which runs on afi_conv3x3_wino_infer / afi_conv3x3_fwd and one afi_conv1x1_fwd): per level
  * top-k, decode + clip + size test, greedy NMS; then the cross-level merge.  Anchor i of a level is (y W + x) A + a: cell anchor a shifted by
