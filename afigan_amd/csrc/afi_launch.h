@@ -25,6 +25,8 @@ int afi_launch_wgrad_gemm(const AfiWgradGemm& p, hipStream_t st);
 int afi_launch_wgrad_gemm_group(const AfiWgradGemm* probs, int n, int wide, hipStream_t st);   // igemm.hip -> smallmap.hip
 int afi_launch_wgrad_gemm_group6(const AfiWgradGemm* probs, int n, hipStream_t st);            // the wide group on the bf16 matrix cores (bf16x6)
 int afi_launch_pix_gemm_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st);
+void* afi_prof_open(hipStream_t st, int kind, double flops, long long m, int n, int k);   // the per-launch profiler's bracket for launchers of other files:
+void afi_prof_close(void* scope);                                                         // open before the launch, close after it (null: profiling is off)
 
 // ---- smallmap.hip
 long long afi_wk6_image_bytes(int Ncols, int Ck, int ntaps, int nKphase);                       // bf16x6 weight images of the small-map kernels
@@ -33,6 +35,11 @@ int afi_launch_pix_gemm_sk(const AfiPixGemm& p, int b_rc, hipStream_t st);      
 int afi_launch_pix_gemm_wk_group(const AfiPixGemm* probs, int n, int b_rc, hipStream_t st);
 int afi_launch_wgrad_group(const AfiWgradGemm* probs, int n, int wide, hipStream_t st);
 int afi_launch_wgrad6_group(const AfiWgradGemm* probs, int n, hipStream_t st);
+
+// ---- frozen1x1.hip
+#define AFI_FROZEN1X1_PLAN_SLOTS 12
+// what afi_frozen1x1_plan fills (long long each): M, BM, BN, KC, row tiles, column tiles, grid, LDS bytes, byte extent of x, of out (= add), of the image, x dense
+enum { AFI_F1_M = 0, AFI_F1_BM, AFI_F1_BN, AFI_F1_KC, AFI_F1_NTM, AFI_F1_NTN, AFI_F1_GRID, AFI_F1_LDS, AFI_F1_XBYTES, AFI_F1_OBYTES, AFI_F1_IBYTES, AFI_F1_XDENSE };
 
 // ---- halfio.hip
 int afi_launch_nchw_to_nhwc(const float* in, float* out, int N, int C, int P, hipStream_t st);

@@ -646,8 +646,9 @@ const char* kKindNames[] = {
     "wgrad_group6 (grouped weight gradients of a small-map backward pass on the bf16 MFMA, bf16x6 operands, fp32 accumulate)",
     "pix_gemm_wk6 (small-map pixel GEMM on the bf16 MFMA, bf16x6 operands on pre-split weight images, fp32 accumulate; grouped launches included)",
     "gemm_nt_f16x3 (batched Winograd GEMM on the f16 MFMA, 256x256 tiles where the grid fills the chip and 128x128 below: two scaled fp16 pieces per operand, three products, fp32 accumulate)",
-    "gemm_tn_f16x3<128x128> (Winograd weight-gradient GEMM on the f16 MFMA: two scaled fp16 pieces per operand, three products, fp32 accumulate)"};   // one kind per kernel, as rocprofv3 lists them
-constexpr int kNumKinds = 23;
+    "gemm_tn_f16x3<128x128> (Winograd weight-gradient GEMM on the f16 MFMA: two scaled fp16 pieces per operand, three products, fp32 accumulate)",
+    "frozen1x1 (forward 1x1 conv of frozen weights on the bf16 MFMA: bf16x6 operands, weights pre-split into a fragment image built once, fp32 accumulate)"};   // one kind per kernel, as rocprofv3 lists them
+constexpr int kNumKinds = 24;
 hipEvent_t prof_event() {                                   // (callers hold g_prof.mu)
     if (g_prof.used == g_prof.pool.size()) {
         hipEvent_t e;
@@ -669,6 +670,14 @@ struct ProfScope {
     }
 };
 }  // namespace
+// the same bracket for launchers of other files (afi_launch.h): null when profiling is off
+void* afi_prof_open(hipStream_t st, int kind, double flops, long long m, int n, int k) {
+    if (!g_prof.on) return nullptr;
+    ProfScope* s = new ProfScope(st, kind, flops);
+    s->m = m; s->n = n; s->k = k;
+    return s;
+}
+void afi_prof_close(void* scope) { delete (ProfScope*)scope; }
 
 extern "C" int afi_profile_enable(int on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);

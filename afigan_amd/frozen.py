@@ -1,6 +1,7 @@
 """What the frozen, forward-only networks (resnet_guide, resnest_backbone, swin_backbone, rpn, roi_heads, bifpn_sr's eval path) share: the
 frozen conv and its fp64 fold, the 1x1 / 3x3 conv dispatch, the cache of prepared weights, the forward-only / GPU-only checks and the
-config lookup.  A new prepared form of a weight is one more `prepared` slot of its module and, if a conv reads it, one more branch here."""
+config lookup.  A new prepared form of a weight is one more `prepared` slot of its module and, if a conv reads it, one more branch here
+(so far one: the bf16x6 image of a 1x1 weight, `conv1x1_image`, read by `conv1x1` for the large maps of forward-only callers)."""
 import torch
 import torch.nn as nn
 
@@ -56,12 +57,25 @@ class Conv2d(nn.Module):
         return fold_conv(self, self.norm, scale)
 
 
-def conv1x1(x, wb, stride=1, add=None, relu=False, alpha=1.0, add_scale=1.0):
+def conv1x1(x, wb, stride=1, add=None, relu=False, alpha=1.0, add_scale=1.0, owner=None):
+    """`owner`: the frozen module the folded (weight, bias) `wb` belongs to, given by forward-only callers: a large map then runs on the
+    bf16 matrix cores over the weight's prepared image (conv1x1_image); without it, and for every map the host plan does not route, the
+    fp32-MFMA pixel GEMM as before."""
     if stride != 1:
         x = x[:, :, ::stride, ::stride]                                 # (a view: the kernel walks the strides)
     if add is not None and add.shape[-2:] != x.shape[-2:]:
         raise AfiError(f"resnet_guide: addend {tuple(add.shape)} does not match the conv output {tuple(x.shape[-2:])}")
+    if owner is not None and ops.conv1x1_frozen_routed(x, wb[0].shape[0], add):
+        return ops.conv1x1_frozen_fwd(x, conv1x1_image(owner, wb[0]), wb[1], wb[0].shape[0], add=add, add_scale=add_scale, alpha=alpha,
+                                      act=2 if relu else 0)
     return ops.conv1x1_fwd(x, wb[0], wb[1], add=add, add_scale=add_scale, alpha=alpha, act=2 if relu else 0)
+
+
+def conv1x1_image(module, w, name="image1x1"):
+    """The prepared form "1x1 bf16x6 image" of `module`'s folded weight `w` [Cout, Cin]: built by one launch when a parameter or buffer of
+    the module -- everything `w` is folded from -- has changed, the same tensor otherwise.  Keyed per conv, so a write to one conv's weight
+    rebuilds that conv's image only (the fold of a whole network is one slot and hands out fresh `w` tensors for all of them)."""
+    return prepared(module, name, list(module.parameters()) + list(module.buffers()), lambda: ops.conv1x1_frozen_image(w))
 
 
 def conv3x3(x, wb, stride=1, relu=False):

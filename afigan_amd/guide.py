@@ -5,7 +5,8 @@ contains the same work as stage1_trainer.py:320-321 (two guide forwards per iter
 
 To keep a fresh GPU box from spending minutes in MIOpen's just-in-time kernel builds, the guide avoids MIOpen entirely:
 1x1 convs run on this package's pixel GEMM (afi_conv1x1_fwd: bias, the residual / top-down addend and the ReLU in its epilogue; a stride-2
-conv reads every second pixel in place), the 7x7 stem is unfold + GEMM, every 3x3
+conv reads every second pixel in place) or, on maps of ops.FROZEN1X1_MIN_PIXELS pixels and more, on the bf16 matrix cores over a weight
+image built once per weight (afi_conv1x1_frozen_fwd, same epilogue), the 7x7 stem with its ReLU and max-pool is afi_resnet_stem_fwd, every 3x3
 conv (stride 1 under detectron2's STRIDE_IN_1X1=True) runs on this package's own fp32-MFMA conv kernels with a fused
 bias + ReLU epilogue (the >= 128-channel ones in the inference Winograd form, afi_conv3x3_wino_infer), and the frozen BatchNorms are folded into weights / biases at construction.
 """
@@ -15,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import frozen, ops
 
 
 def _kaiming(shape, fan_in, gain=1.0):
@@ -35,7 +36,10 @@ class _Conv1x1(nn.Module):
     def forward(self, x, add=None, relu=None):                          # x: [N,C,H,W] pixel-major; out = act(conv(x) + b + add)
         if self.stride != 1:
             x = x[:, :, ::self.stride, ::self.stride]                   # (a view: the kernel walks the strides)
-        return ops.conv1x1_fwd(x, self.w, self.b, add=add, act=2 if (self.relu if relu is None else relu) else 0)
+        act = 2 if (self.relu if relu is None else relu) else 0
+        if ops.conv1x1_frozen_routed(x, self.w.shape[0], add):          # large maps: the bf16 matrix cores over the weight's image, built once
+            return ops.conv1x1_frozen_fwd(x, frozen.conv1x1_image(self, self.w), self.b, self.w.shape[0], add=add, act=act)
+        return ops.conv1x1_fwd(x, self.w, self.b, add=add, act=act)
 
 
 class _Conv3x3(nn.Module):
@@ -89,11 +93,10 @@ class GuideR50FPN(nn.Module):
         ph, pw = (32 - H % 32) % 32, (32 - W % 32) % 32
         if ph or pw:
             x = F.pad(x, (0, pw, 0, ph))                         # ImageList.from_tensors(size_divisibility=32)
-        N, _, H, W = x.shape
-        cols = F.unfold(x, kernel_size=7, padding=3, stride=2)   # [N, 147, H/2*W/2]: the 7x7/2 stem as a GEMM
-        y = F.relu_(torch.baddbmm(self.stem_b.view(1, 1, -1), cols.transpose(1, 2), self.stem_w.unsqueeze(0).expand(N, -1, -1)))
-        x = y.view(N, H // 2, W // 2, 64).permute(0, 3, 1, 2)
-        x = F.max_pool2d(x, 3, 2, 1).contiguous(memory_format=torch.channels_last)
+        # the 7x7/2 conv + bias + ReLU + 3x3/2 max-pool in one kernel (the conv map is never written); stem_w stays the [147, 64] GEMM
+        # matrix (row c*49 + ky*7 + kx), the kernel reads its [64][3][7][7] re-layout, kept until stem_w changes
+        w7 = frozen.prepared(self, "stem_w7", [self.stem_w], lambda: self.stem_w.t().reshape(64, 3, 7, 7).contiguous())
+        x = ops.resnet_stem(x, w7, self.stem_b)
         feats = []
         for st in self.stages:
             x = st(x)

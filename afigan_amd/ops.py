@@ -481,6 +481,68 @@ def conv1x1_fwd(x, w, bias=None, add=None, add_scale=1.0, alpha=1.0, out=None, a
     return out
 
 
+# ---- the 1x1 conv of FROZEN weights on the bf16 matrix cores (csrc/frozen1x1.hip): the weight is turned into a pre-split image once
+# (frozen.conv1x1_image keeps it per module), large maps then run afi_conv1x1_frozen_fwd instead of the fp32-MFMA pixel GEMM.
+FROZEN1X1_MIN_PIXELS = 8192          # maps below it stay on conv1x1_fwd (the per-shape table that decided it) ...
+FROZEN1X1_MIN_PIXELS_EXPANDING = 2048   # ... but for the convs with Cout >= 2 Cin (conv3, shortcuts): enough column tiles to fill the chip from here on
+frozen1x1_route = True               # False: every caller takes conv1x1_fwd (A/B runs, and the route test's reference)
+frozen1x1_images_built = 0           # image launches so far (an unchanged weight must not add to it)
+_F1_PLAN = ("M", "BM", "BN", "KC", "ntile_m", "ntile_n", "grid", "lds_bytes", "x_bytes", "out_bytes", "image_bytes", "x_dense")
+
+
+def conv1x1_frozen_plan(N, H, W, Cin, Cout, x_strides, out_strides=None, add_strides=None):
+    """The host plan of afi_conv1x1_frozen_fwd for x [N, Cin, H, W] with element strides (sN, sH, sW), a dense output unless `out_strides`
+    says otherwise and an optional addend: a dict (M, BM, BN, KC, ntile_m, ntile_n, grid, lds_bytes, x_bytes, out_bytes, image_bytes,
+    x_dense), or None when the kernel does not take the problem.  Pure host code: no device, no launch."""
+    o = out_strides if out_strides is not None else (H * W * Cout, W * Cout, Cout)
+    a = add_strides if add_strides is not None else (0, 0, 0)
+    plan = (C.c_longlong * len(_F1_PLAN))()
+    st = _lib.load().afi_frozen1x1_plan(N, H, W, Cin, Cout, *[int(s) for s in x_strides], *[int(s) for s in o], int(add_strides is not None),
+                                        *[int(s) for s in a], plan)
+    if st == _lib.DEFINES["AFI_ERR_UNSUPPORTED"]:
+        return None
+    _lib.check(st, "afi_frozen1x1_plan")
+    return dict(zip(_F1_PLAN, plan))
+
+
+def conv1x1_frozen_routed(x, Cout, add=None):
+    """True when a frozen 1x1 conv of `x` to `Cout` channels goes to the bf16x6 kernel: the route is on, the map has at least
+    FROZEN1X1_MIN_PIXELS pixels (FROZEN1X1_MIN_PIXELS_EXPANDING when Cout >= 2 Cin) and the host plan takes the views."""
+    N, Cin, H, W = x.shape
+    least = min(FROZEN1X1_MIN_PIXELS, FROZEN1X1_MIN_PIXELS_EXPANDING) if Cout >= 2 * Cin else FROZEN1X1_MIN_PIXELS
+    if not frozen1x1_route or N * H * W < least or x.stride(1) != 1 or (add is not None and not is_dense_pm(add)):
+        return False
+    return conv1x1_frozen_plan(N, H, W, Cin, Cout, (x.stride(0), x.stride(2), x.stride(3)),
+                               add_strides=(add.stride(0), add.stride(2), add.stride(3)) if add is not None else None) is not None
+
+
+def conv1x1_frozen_image(w):
+    """The bf16x6 fragment image of w [Cout, Cin] (or [Cout, Cin, 1, 1]), both multiples of 32: a uint8 tensor afi_conv1x1_frozen_fwd reads."""
+    global frozen1x1_images_built
+    _check_cuda(w)
+    Cout, Cin = w.shape[0], w.shape[1]
+    w2 = w.reshape(Cout, Cin).contiguous()
+    nbytes = _lib.load().afi_frozen1x1_image_bytes(Cout, Cin)
+    if nbytes <= 0:
+        raise _lib.AfiError(f"conv1x1_frozen_image: Cout {Cout} and Cin {Cin} must be positive multiples of 32")
+    image = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
+    call("afi_conv1x1_frozen_image", _p(w2), Cout, Cin, _p(image), nbytes, stream_ptr())
+    frozen1x1_images_built += 1
+    return image
+
+
+def conv1x1_frozen_fwd(x, image, bias, Cout, add=None, add_scale=1.0, alpha=1.0, out=None, act=0):
+    """out = act(alpha*conv1x1(x, w) + bias + add_scale*add) with w given as its conv1x1_frozen_image; what conv1x1_frozen_plan refuses
+    raises AfiError (callers ask conv1x1_frozen_routed first and take conv1x1_fwd otherwise)."""
+    _check_cuda(x, bias, add, out)
+    N, Cin, H, W = x.shape
+    if out is None:
+        out = new_pixel_major(N, Cout, H, W, x.device)
+    call("afi_conv1x1_frozen_fwd", view_of(x), N, H, W, Cin, _p(image), _p(bias), Cout, view_of(out), float(alpha),
+         view_of(add) if add is not None else _NULL_VIEW, float(add_scale), int(act), stream_ptr())
+    return out
+
+
 def conv1x1_dgrad(dy, w, dx=None, alpha=1.0, beta=0.0, out_dtype=torch.float32, *, z=None, z_act="lrelu", add=None, add_scale=1.0):
     """out_dtype bf16 / fp16: a fresh 2-byte dx rounded by the epilogue (afi_conv1x1_dgrad_out16; beta must be 0).
     With z= and / or add= (afi_conv1x1_dgrad_act): dx = (alpha*W^T dy + beta*dx + add_scale*add) * act'(z), z_act "lrelu" or "relu"; dx, add

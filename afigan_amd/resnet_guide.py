@@ -69,11 +69,13 @@ class BottleneckBlock(nn.Module):
         self.conv2 = Conv2d(bottleneck, bottleneck, 3, stride=s3)
         self.conv3 = Conv2d(bottleneck, cout, 1)
 
-    def run(self, x, f):
-        s = x if self.shortcut is None else conv1x1(x, f[id(self.shortcut)], self.shortcut.stride)
-        y = conv1x1(x, f[id(self.conv1)], self.conv1.stride, relu=True)
+    def run(self, x, f, route=False):
+        """`route`: the forward-only inference path -- large maps take frozen.conv1x1's bf16x6 kernel over each conv's prepared image."""
+        own = (lambda m: m) if route else (lambda m: None)
+        s = x if self.shortcut is None else conv1x1(x, f[id(self.shortcut)], self.shortcut.stride, owner=own(self.shortcut))
+        y = conv1x1(x, f[id(self.conv1)], self.conv1.stride, relu=True, owner=own(self.conv1))
         y = conv3x3(y, f[id(self.conv2)], self.conv2.stride, relu=True)
-        return conv1x1(y, f[id(self.conv3)], add=s, relu=True)
+        return conv1x1(y, f[id(self.conv3)], add=s, relu=True, owner=own(self.conv3))
 
     def convs(self):
         """The block's convs in the order ``_ResNetTrainFn`` takes their weights: conv1, conv2, conv3, then the shortcut if there is one."""
@@ -268,6 +270,7 @@ class ResNetBase(_Frozen):
 
     _train_stages = ()                   # ResNet.trainable_: the stages that run under autograd
     _fuse_masks = True
+    _route_frozen1x1 = False             # the forward-only path hands its blocks `route=True` (ResNet; the ResNeSt blocks are not routed)
 
     def _wants_graph(self):
         """The differentiable path: grad mode on, ``trainable_`` has named stages and a parameter requires grad (BiFPN_AFIGAN._wants_graph's
@@ -286,7 +289,7 @@ class ResNetBase(_Frozen):
                 out["stem"] = y
             for name in self.stage_names:
                 for blk in getattr(self, name):
-                    y = blk.run(y, f)
+                    y = blk.run(y, f, route=True) if self._route_frozen1x1 else blk.run(y, f)
                 if name in self._out_features:
                     out[name] = y
         return out
@@ -294,6 +297,7 @@ class ResNetBase(_Frozen):
 
 class ResNet(ResNetBase):
     """The bottom-up of detectron2's ResNet-50 / -101 (see ResNetBase for the forward)."""
+    _route_frozen1x1 = True
 
     def __init__(self, depth=50, out_features=("res2", "res3", "res4", "res5"), stride_in_1x1=True, width_per_group=64,
                  res2_out_channels=256, stem_out_channels=64):
@@ -454,14 +458,15 @@ class FPN(_Frozen):
         with torch.no_grad():
             f = self._prepare()
             xs = [feats[k] for k in self.in_features[::-1]]
-            prev = conv1x1(xs[0], f[id(self.lateral_convs[0])])
+            own = (lambda m: m) if getattr(self.bottom_up, "_route_frozen1x1", False) else (lambda m: None)   # (over a ResNeSt: not routed)
+            prev = conv1x1(xs[0], f[id(self.lateral_convs[0])], owner=own(self.lateral_convs[0]))
             results = [conv3x3(prev, f[id(self.output_convs[0])])]
             for feat, lat, out in zip(xs[1:], self.lateral_convs[1:], self.output_convs[1:]):
                 td = ops.nearest(prev, up=2)
                 if self._fuse_type == "avg":
-                    prev = conv1x1(feat, f[("avg", id(lat))], add=td, alpha=0.5, add_scale=0.5)
+                    prev = conv1x1(feat, f[("avg", id(lat))], add=td, alpha=0.5, add_scale=0.5, owner=own(lat))
                 else:
-                    prev = conv1x1(feat, f[id(lat)], add=td)
+                    prev = conv1x1(feat, f[id(lat)], add=td, owner=own(lat))
                 results.insert(0, conv3x3(prev, f[id(out)]))
             results.append(ops.nearest(results[-1], up=1, down=2))          # LastLevelMaxPool on the coarsest output
         return dict(zip(self._out_features, results))

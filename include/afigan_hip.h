@@ -561,6 +561,25 @@ int afi_normalize_pad_u8(const unsigned char* img_chw, int C, int H, int W, cons
 int afi_resnet_stem_fwd(const float* x, int N, int H, int W, const float* w, const float* bias, float* out, void* stream);
 int afi_nearest_nhwc(afi_view_t x, int N, int H, int W, int C, int up, int down, float* out, void* stream);
 
+/* ------------------------------------------------------------------ forward 1x1 conv of FROZEN weights on the bf16 matrix cores (csrc/frozen1x1.hip)
+ * out = act(alpha*conv1x1(x, w) + bias + add_scale*add), act 0 / 1 / 2 as afi_conv1x1_fwd, in the bf16x6 arithmetic (every fp32 operand split
+ * exactly into three bf16, six products summed smallest first into fp32): for the large maps of a frozen guide, whose weights are turned into
+ * a pre-split image ONCE.  fp32 in memory on both sides; no atomics, no scratch: bit-reproducible and capturable into a graph.
+ * afi_frozen1x1_image_bytes: size of the image of w [Cout][Cin] (0 unless both are positive multiples of 32).
+ * afi_conv1x1_frozen_image: one launch that writes it (image 16-byte aligned, image_bytes >= the size above: AFI_ERR_WORKSPACE otherwise).
+ * afi_frozen1x1_plan (host only, no device): AFI_OK when afi_conv1x1_frozen_fwd takes the problem, and then plan[0..12) = M, BM, BN, KC (the
+ *   64 x BN output tile and the channels per K chunk), row tiles, column tiles, grid, LDS bytes, byte extents of x / out / image, x dense;
+ *   AFI_ERR_UNSUPPORTED (nothing would be launched; the caller runs afi_conv1x1_fwd) unless: Cin % 32 == 0 and Cout % 32 == 0; x is every
+ *   s-th pixel (s >= 1, both directions) of a pixel-major tensor of Cin channels (x.sW = s Cin, x.sH >= s ((W-1) s + 1) Cin) -- a channel
+ *   slice of a wider tensor is refused --; out dense [N][H][W][Cout] and add, if given, dense like out; every byte extent below 2 GB.
+ * afi_conv1x1_frozen_fwd: any M = N H W >= 1 that the plan accepts; `image` must hold the image of this conv's w.  ctx is unused (reserved). */
+long long afi_frozen1x1_image_bytes(int Cout, int Cin);
+int afi_frozen1x1_plan(int N, int H, int W, int Cin, int Cout, long long x_sN, long long x_sH, long long x_sW, long long o_sN, long long o_sH,
+                       long long o_sW, int has_add, long long a_sN, long long a_sH, long long a_sW, long long* plan);
+int afi_conv1x1_frozen_image(afi_ctx_t* ctx, const float* w, int Cout, int Cin, void* image, long long image_bytes, void* stream);
+int afi_conv1x1_frozen_fwd(afi_ctx_t* ctx, afi_view_t x, int N, int H, int W, int Cin, const void* image, const float* bias, int Cout, afi_view_t out,
+                           float alpha, afi_view_t add_or_null, float add_scale, int act, void* stream);
+
 /* ------------------------------------------------------------------ frozen ResNeSt bottom-up (afigan_amd/resnest_backbone.py)
  * detectron2-ResNeSt (radix 2, cardinality 1, deep stem, AVD, avg_down), forward only.  Its 1x1 convs are afi_conv1x1_fwd, its stride-1 3x3
  * convs afi_conv3x3_fwd / afi_conv3x3_wino_infer (a split-attention conv: one launch per radix group, through channel views); these cover
