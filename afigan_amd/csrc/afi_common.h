@@ -20,6 +20,8 @@ struct AfiView {
     float* p;
     long long sN, sH, sW;
 };
+// true where a kernel may read the view with 16-byte loads at channel offsets that are multiples of 4: base and every stride on a float4 boundary
+static inline bool afi_view_takes_f32x4(const AfiView& v) { return !(((uintptr_t)v.p & 15) || (v.sN & 3) || (v.sH & 3) || (v.sW & 3)); }
 
 // A tensor that is read THROUGH a BatchNorm affine and LeakyReLU(0.2): the reader sees lrelu(((x - mean) * invstd) * gamma + beta) per channel
 // (csrc/afi_bn.h: the exact arithmetic of the stand-alone apply pass).  mean = null: off.  Taken by the discriminator's fused tail

@@ -218,9 +218,9 @@ __global__ void afi_maxpool3s2_same_bwd_kernel(const float* __restrict__ dout, c
     }
 }
 extern "C" int afi_maxpool3s2_same_fwd_idx(afi_view_t xv, int N, int H, int W, int C, float* out, unsigned char* idx, void* stream) {
-    if (N <= 0 || H < 2 || W < 2 || C <= 0 || !out || !idx) return AFI_ERR_BAD_ARG;
-    if ((C & 3) || (((unsigned long long)idx) & 3)) return AFI_ERR_UNSUPPORTED;
+    if (N <= 0 || H < 2 || W < 2 || C <= 0 || !xv.p || !out || !idx) return AFI_ERR_BAD_ARG;
     AfiView x; x.p = (float*)xv.p; x.sN = xv.sN; x.sH = xv.sH; x.sW = xv.sW;
+    if ((C & 3) || (((unsigned long long)idx) & 3) || !afi_view_takes_f32x4(x) || ((uintptr_t)out & 15)) return AFI_ERR_UNSUPPORTED;
     const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
     hipLaunchKernelGGL(afi_maxpool3s2_same_idx_kernel, dim3(afi_bt_grid((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, (hipStream_t)stream, x, N, H, W,
                        C, Ho, Wo, out, (unsigned*)idx);

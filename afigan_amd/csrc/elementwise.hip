@@ -1235,13 +1235,14 @@ __global__ void afi_dwconv3x3_kernel(const AfiView x, int N, int H, int W, int C
     }
 }
 int afi_launch_dwconv3x3(AfiView x, int N, int H, int W, int C, const float* w, float* out, hipStream_t st) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return AFI_ERR_BAD_ARG;
-    if (C & 3) return AFI_ERR_UNSUPPORTED;
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || !x.p || !w || !out) return AFI_ERR_BAD_ARG;
+    if ((C & 3) || !afi_view_takes_f32x4(x) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15)) return AFI_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(afi_dwconv3x3_kernel, dim3(afi_ew_grid((long long)N * H * W * (C >> 2))), dim3(256), 0, st, x, N, H, W, C, w, out);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 // MaxPool2d(3, 2, "static_same"): F.pad(0 left/top, 1 right/bottom, ZEROS) then max_pool2d(3, 2): out[oy][ox] = max over rows
 // 2oy..2oy+2, cols 2ox..2ox+2 where positions == H / == W count as 0.0 (the zero pad takes part in the max), Ho = (H-2)/2 + 1.
+// The value is that of the FIRST maximum in scan order: bit-identical to afi_maxpool3s2_same_idx_kernel's (the train-mode forward).
 __global__ void afi_maxpool3s2_same_kernel(const AfiView x, int N, int H, int W, int C, int Ho, int Wo, float* __restrict__ out) {
     const int C4 = C >> 2;
     const long long total = (long long)N * Ho * Wo * C4;
@@ -1255,14 +1256,16 @@ __global__ void afi_maxpool3s2_same_kernel(const AfiView x, int N, int H, int W,
             f32x4 v = {0.f, 0.f, 0.f, 0.f};                  // the pad row / column
             if (y2 < H && x2 < W) v = *(const f32x4*)(x.p + (long long)n * x.sN + (long long)y2 * x.sH + (long long)x2 * x.sW + c);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], v[j]);
+            for (int j = 0; j < 4; ++j)
+                if (v[j] > m[j] || t == 0) m[j] = v[j];     // the scan of afi_maxpool3s2_same_idx_kernel and of torch's max_pool2d: among equal maxima
+                                                             // the first stays, so a window of -0.0 and +0.0 keeps the sign of the first (fmaxf gave +0.0)
         }
         *(f32x4*)(out + i * 4) = m;
     }
 }
 int afi_launch_maxpool3s2_same(AfiView x, int N, int H, int W, int C, float* out, hipStream_t st) {
-    if (N <= 0 || H < 2 || W < 2 || C <= 0) return AFI_ERR_BAD_ARG;
-    if (C & 3) return AFI_ERR_UNSUPPORTED;
+    if (N <= 0 || H < 2 || W < 2 || C <= 0 || !x.p || !out) return AFI_ERR_BAD_ARG;
+    if ((C & 3) || !afi_view_takes_f32x4(x) || ((uintptr_t)out & 15)) return AFI_ERR_UNSUPPORTED;
     const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
     hipLaunchKernelGGL(afi_maxpool3s2_same_kernel, dim3(afi_ew_grid((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, st, x, N, H, W, C, Ho, Wo, out);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;

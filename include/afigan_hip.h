@@ -408,6 +408,8 @@ int afi_relu_bwd(const float* g, const float* act, float* out, long long n, floa
  *   afi_maxpool3s2_same_fwd  MaxPool2d(3, 2, "static_same"): zero pad right/bottom by 1 (the zeros take part in the max),
  *                            out dense [N, (H-2)/2+1, (W-2)/2+1, C]
  *   afi_fuse_swish_fwd       out = swish(w[0]*a + w[1]*b (+ w[2]*c)); a, b, c, out dense and equal-sized, w a DEVICE pointer
+ * The depthwise conv and both max-pool forwards read x, w9c and write out with 16-byte accesses: C % 4 == 0, x.p / w9c / out 16-byte
+ * aligned and the view's strides multiples of 4 (AFI_ERR_UNSUPPORTED otherwise, as afi_nearest_nhwc).
  * The pointwise 1x1 conv (+ folded eval-mode norm) is afi_conv1x1_fwd. */
 int afi_dwconv3x3_fwd(afi_view_t x, int N, int H, int W, int C, const float* w9c, float* out, void* stream);
 int afi_maxpool3s2_same_fwd(afi_view_t x, int N, int H, int W, int C, float* out, void* stream);
