@@ -1,6 +1,6 @@
 // detectron2's pairwise_iou and Matcher as device functions over boxes held in registers or LDS, whatever they were read from: the RPN's label
 // assignment (rpn_loss.hip: anchors formed from their index, ground truth from a padded tensor) and the ROI heads' proposal labelling (roi_loss.hip).
-// Every operation is rounded to fp32 once and nothing is contracted into a fused multiply-add, as in afi_nms_kernel (afi_select.h): an IoU
+// Every operation is rounded to fp32 once and nothing is contracted into a fused multiply-add, as in rpn_overlaps (afi_select.h): an IoU
 // computed here is the same bit pattern wherever it is computed, so two sweeps may compare their results for equality.
 #pragma once
 #include "afi_common.h"

@@ -18,10 +18,11 @@
 //                    is compiled without fused multiply-adds: inter / (area_a + area_b - inter) > thresh, each operation rounded to fp32.
 //   afi_rpn_merge    the kept boxes of all levels of an image in (logit descending, level, rank) order, cut to post_k: every level's list is
 //                    already sorted, so an entry's place is its own rank plus one binary search per other level.  No sort, no atomics.
-// The "wide" forms (lists of 1025 .. 4096 per level: PRE_NMS_TOPK_TRAIN of the reference's base config is 2000) are the last section of the file:
-//   afi_rpn_topk_wide   the same histogram, filter and radix select; the pick holds sel[4096] and sorts the next power of two >= k.
+// The "wide" forms (lists of 1025 .. 4096 per level: PRE_NMS_TOPK_TRAIN of the reference's base config is 2000):
+//   afi_rpn_topk_wide   afi_rpn_topk's kernels, the pick instantiated with sel[4096]: it sorts the next power of two >= k.
 //   afi_rpn_nms_wide    the bit matrix in a workspace, its upper triangle built by one block per 64 x 64 tile; one wave per image sweeps it.
-//   afi_rpn_merge_wide  afi_rpn_merge with threads looping over a level's entries, 5 x 4096 entries in all.
+//                       The overlap test and the diagonal resolve are afi_rpn_nms's (afi_select.h).
+//   afi_rpn_merge_wide  afi_rpn_merge's kernel instantiated for 5 x 4096 entries in all.
 // Nothing here synchronises with the host, and every result is bit-identical from run to run and under hipGraph replay.
 #include "../../include/afigan_hip.h"
 #include "afi_common.h"
@@ -104,15 +105,17 @@ __global__ __launch_bounds__(256) void afi_rpn_filter_kernel(const AfiView lg, i
 }
 
 // ------------------------------------------------------------------------------------------------ top-k: select k of m words, sort, write
-// DIRECT: the m = n words are formed from the logits; else they are the filter's list (hdr[RPN_BINS] of them).  One block per image.
-template <bool DIRECT>
+// DIRECT: the m = n words are formed from the logits; else they are the filter's list (hdr[RPN_BINS] of them).  One block per image, k <= MAXK
+// (RPN_MAXK or RPN_MAXK_WIDE).  The selected words are sorted in LDS (bitonic): P = 1024 words for RPN_MAXK, a thread per word; 2048 or 4096
+// for RPN_MAXK_WIDE, P / 2 compare-exchanges per step over the 1024 threads.  The words are distinct apart from the zero padding.
+template <bool DIRECT, int MAXK>
 __global__ __launch_bounds__(1024) void afi_rpn_pick_kernel(const AfiView lg, int W, int A, int n, int k, const int* __restrict__ hdr,
                                                             const u64* __restrict__ cand_all, float* __restrict__ vals, int* __restrict__ idx,
                                                             long long ld) {
     __shared__ int hist[2048];
     __shared__ int wtot[16];
     __shared__ int res[2];
-    __shared__ u64 sel[RPN_MAXK];
+    __shared__ u64 sel[MAXK];
     __shared__ int nsel;
     const int img = blockIdx.x, tid = threadIdx.x;
     int m = n;
@@ -123,55 +126,47 @@ __global__ __launch_bounds__(1024) void afi_rpn_pick_kernel(const AfiView lg, in
         cand = cand_all + (long long)img * n;
     }
     auto word = [&](int i) -> u64 { return DIRECT ? rpn_word(*rpn_at(lg, img, i, W, A), i) : cand[i]; };
-    int need = k < m ? k : m, group = m, shift = 32 + RPN_IDX_BITS;
-    u64 prefix = 0;
-    const int widths[5] = {11, 11, 10, 11, 11};
-    for (int p = 0; p < 5 && need < group; ++p) {
-        const int bits = widths[p], nb = 1 << bits;
-        shift -= bits;
-        for (int i = tid; i < nb; i += 1024) hist[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < m; i += 1024) {
-            const u64 c = word(i);
-            if ((c >> (shift + bits)) == prefix) atomicAdd(&hist[(int)(c >> shift) & (nb - 1)], 1);
-        }
-        __syncthreads();
-        rpn_find_digit(hist, nb, need, wtot, res);
-        need -= res[1];
-        group = hist[res[0]];
-        prefix = (prefix << bits) | (u64)res[0];
-        __syncthreads();
-    }
+    const RpnCut cut = rpn_radix_select([&](int i, u64* c) { *c = word(i); return true; }, m, m, k < m ? k : m, RPN_IDX_BITS, hist, wtot, res);
     // the words above the open group and the group itself (taken whole): min(k, m) words
     if (tid == 0) nsel = 0;
     __syncthreads();
     for (int i = tid; i < m; i += 1024) {
         const u64 c = word(i);
-        if ((c >> shift) >= prefix) {
+        if ((c >> cut.shift) >= cut.prefix) {
             const int s = atomicAdd(&nsel, 1);
-            if (s < RPN_MAXK) sel[s] = c;
+            if (s < MAXK) sel[s] = c;                      // (never more than min(k, m) <= MAXK: the guard keeps a wrong count inside the array)
         }
     }
     __syncthreads();
-    const int ns = nsel < RPN_MAXK ? nsel : RPN_MAXK;
-    if (tid >= ns) sel[tid] = 0;                       // below every real word (a real word's index field is never all ones: n <= RPN_IDX_MASK)
+    const int ns = nsel < MAXK ? nsel : MAXK;
+    const int P = (MAXK > RPN_MAXK && k <= MAXK / 2 && ns <= MAXK / 2) ? MAXK / 2 : MAXK;
+    for (int i = ns + tid; i < P; i += 1024) sel[i] = 0;   // below every real word (a real word's index field is never all ones: n <= RPN_IDX_MASK)
     __syncthreads();
-    for (int ksz = 2; ksz <= RPN_MAXK; ksz <<= 1)
+    for (int ksz = 2; ksz <= P; ksz <<= 1)
         for (int j = ksz >> 1; j > 0; j >>= 1) {
-            const int o = tid ^ j;
-            if (o > tid) {
-                const u64 a = sel[tid], b = sel[o];
-                const bool desc = (tid & ksz) == 0;
-                if (desc ? a < b : a > b) { sel[tid] = b; sel[o] = a; }
+            if constexpr (MAXK == RPN_MAXK) {              // P = the block: a thread per word, the lower word's thread exchanges the pair
+                const int o = tid ^ j;                     // (the inference path's sort; the pair form with half the threads idle was
+                if (o > tid) {                             // measured beside it: DESIGN 25)
+                    const u64 a = sel[tid], b = sel[o];
+                    const bool desc = (tid & ksz) == 0;
+                    if (desc ? a < b : a > b) { sel[tid] = b; sel[o] = a; }
+                }
+            } else {
+                for (int t = tid; t < (P >> 1); t += 1024) {
+                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;    // the t-th pair of this step: bit j clear / set
+                    const u64 a = sel[i], b = sel[o];
+                    const bool desc = (i & ksz) == 0;
+                    if (desc ? a < b : a > b) { sel[i] = b; sel[o] = a; }
+                }
             }
             __syncthreads();
         }
-    if (tid < k) {
-        const u64 c = sel[tid];
+    for (int t = tid; t < k; t += 1024) {
+        const u64 c = sel[t];
         int i = (int)((~(unsigned)c) & RPN_IDX_MASK);
-        if (c == 0 || i >= n) i = 0;                   // (never: k <= m real words)
-        idx[(long long)img * ld + tid] = i;
-        vals[(long long)img * ld + tid] = *rpn_at(lg, img, i, W, A);
+        if (c == 0 || i >= n) i = 0;                       // (never: k <= m real words)
+        idx[(long long)img * ld + t] = i;
+        vals[(long long)img * ld + t] = *rpn_at(lg, img, i, W, A);
     }
 }
 
@@ -183,18 +178,22 @@ long long afi_rpn_topk_ws_floats(int N, int H, int W, int A) {
     return (long long)N * RPN_HDR + 2 * (long long)N * n;
 }
 
-int afi_rpn_topk(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
-                 void* stream) {
+long long afi_rpn_topk_wide_ws_floats(int N, int H, int W, int A) { return afi_rpn_topk_ws_floats(N, H, W, A); }
+
+// k_above < k <= MAXK: afi_rpn_topk is (0, RPN_MAXK], afi_rpn_topk_wide (RPN_MAXK, RPN_MAXK_WIDE] -- a k of the other's range is refused.
+template <int MAXK>
+static int rpn_topk_launch(int k_above, afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws,
+                           long long ws_floats, void* stream) {
     if (!logits.p || !vals || !idx || N <= 0 || N > 65535 || H <= 0 || W <= 0 || A <= 0 || k <= 0 || ld < k) return AFI_ERR_BAD_ARG;
     const long long nn = (long long)H * W * A;
-    if (A > RPN_MAX_A || k > RPN_MAXK || nn >= RPN_IDX_MASK) return AFI_ERR_UNSUPPORTED;
+    if (A > RPN_MAX_A || k <= k_above || k > MAXK || nn >= RPN_IDX_MASK) return AFI_ERR_UNSUPPORTED;
     if (k > nn) return AFI_ERR_BAD_ARG;
     const int n = (int)nn;
     const AfiView lg{(float*)logits.p, logits.sN, logits.sH, logits.sW};
     hipStream_t st = (hipStream_t)stream;
     if (n <= RPN_DIRECT_MAX) {
-        hipLaunchKernelGGL(afi_rpn_pick_kernel<true>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)nullptr, (const u64*)nullptr, vals,
-                           idx, ld);
+        hipLaunchKernelGGL((afi_rpn_pick_kernel<true, MAXK>), dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)nullptr, (const u64*)nullptr,
+                           vals, idx, ld);
         return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
     }
     const long long need = afi_rpn_topk_ws_floats(N, H, W, A);
@@ -206,8 +205,19 @@ int afi_rpn_topk(afi_view_t logits, int N, int H, int W, int A, int k, float* va
     if (gx > 512) gx = 512;
     hipLaunchKernelGGL(afi_rpn_hist_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, hdr);
     hipLaunchKernelGGL(afi_rpn_filter_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, k, hdr, cand);
-    hipLaunchKernelGGL(afi_rpn_pick_kernel<false>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)hdr, (const u64*)cand, vals, idx, ld);
+    hipLaunchKernelGGL((afi_rpn_pick_kernel<false, MAXK>), dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)hdr, (const u64*)cand, vals,
+                       idx, ld);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+int afi_rpn_topk(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                 void* stream) {
+    return rpn_topk_launch<RPN_MAXK>(0, logits, N, H, W, A, k, vals, idx, ld, ws, ws_floats, stream);
+}
+
+int afi_rpn_topk_wide(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
+                      void* stream) {
+    return rpn_topk_launch<RPN_MAXK_WIDE>(RPN_MAXK, logits, N, H, W, A, k, vals, idx, ld, ws, ws_floats, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ decode
@@ -278,195 +288,11 @@ int afi_rpn_nms(const float* boxes, const int* valid, int N, int k, long long ld
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
 }
 
-// ------------------------------------------------------------------------------------------------ merge
-// boxes [N][Ktot][4], vals / keep [N][Ktot]: the levels side by side, level l in columns [off[l], off[l + 1]), each sorted by afi_rpn_topk.
-__global__ __launch_bounds__(1024) void afi_rpn_merge_kernel(const float* __restrict__ boxes, const float* __restrict__ vals,
-                                                             const int* __restrict__ keep, const RpnLevels lv, int post_k,
-                                                             float* __restrict__ ob, float* __restrict__ ol, int* __restrict__ counts) {
-    __shared__ unsigned ckey[RPN_MAX_LEVELS * RPN_MAXK];
-    __shared__ unsigned short cpos[RPN_MAX_LEVELS * RPN_MAXK];
-    __shared__ int cnt[RPN_MAX_LEVELS];
-    __shared__ int wtot[16];
-    const int img = blockIdx.x, tid = threadIdx.x, Ktot = lv.off[lv.L];
-    const long long row0 = (long long)img * Ktot;
-    for (int l = 0; l < lv.L; ++l) {
-        const int o = lv.off[l], kl = lv.off[l + 1] - o;
-        const int f = (tid < kl) && keep[row0 + o + tid] != 0;
-        int tot;
-        const int inc = rpn_block_scan(f, wtot, &tot);
-        if (f) {
-            ckey[o + inc - 1] = rpn_key(vals[row0 + o + tid]);
-            cpos[o + inc - 1] = (unsigned short)(o + tid);
-        }
-        if (tid == 0) cnt[l] = tot;
-    }
-    __syncthreads();
-    int total = 0;
-    for (int l = 0; l < lv.L; ++l) total += cnt[l];
-    for (int l = 0; l < lv.L; ++l) {
-        if (tid >= cnt[l]) continue;
-        const unsigned key = ckey[lv.off[l] + tid];
-        int rank = tid;
-        for (int b = 0; b < lv.L && rank < post_k; ++b) {
-            if (b == l) continue;
-            const unsigned* arr = ckey + lv.off[b];
-            int lo = 0, hi = cnt[b];
-            while (lo < hi) {                          // entries of level b in front: >= key for an earlier level, > key for a later one
-                const int mid = (lo + hi) >> 1;
-                const bool front = b < l ? arr[mid] >= key : arr[mid] > key;
-                if (front) lo = mid + 1; else hi = mid;
-            }
-            rank += lo;
-        }
-        if (rank < post_k) {
-            const long long src = row0 + cpos[lv.off[l] + tid], dst = (long long)img * post_k + rank;
-            const float* q = boxes + 4 * src;
-            float* p = ob + 4 * dst;
-            p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; p[3] = q[3];
-            ol[dst] = vals[src];
-        }
-    }
-    const int c = total < post_k ? total : post_k;
-    if (tid == 0) counts[img] = c;
-    for (int r = c + tid; r < post_k; r += 1024) {
-        const long long dst = (long long)img * post_k + r;
-        float* p = ob + 4 * dst;
-        p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; p[3] = 0.f;
-        ol[dst] = 0.f;
-    }
-}
-
-int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
-                  float* out_logits, int* counts, void* stream) {
-    if (!boxes || !vals || !keep || !level_off || !out_boxes || !out_logits || !counts || N <= 0 || N > 65535 || L <= 0 || post_k <= 0)
-        return AFI_ERR_BAD_ARG;
-    if (L > RPN_MAX_LEVELS) return AFI_ERR_UNSUPPORTED;
-    RpnLevels lv;
-    lv.L = L;
-    if (level_off[0] != 0) return AFI_ERR_BAD_ARG;
-    for (int l = 0; l <= RPN_MAX_LEVELS; ++l) lv.off[l] = level_off[l < L ? l : L];
-    for (int l = 0; l < L; ++l) {
-        const int kl = level_off[l + 1] - level_off[l];
-        if (kl < 0) return AFI_ERR_BAD_ARG;
-        if (kl > RPN_MAXK) return AFI_ERR_UNSUPPORTED;
-    }
-    if (level_off[L] <= 0) return AFI_ERR_BAD_ARG;
-    hipLaunchKernelGGL(afi_rpn_merge_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes, out_logits,
-                       counts);
-    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
-}
-
-// ================================================================================================ the wide forms: 1024 < k <= 4096 per level
-// ------------------------------------------------------------------------------------------------ top-k
-// afi_rpn_pick_kernel with sel[RPN_MAXK_WIDE]: the same select (restated: the narrow kernel's code object stays as it is), then a bitonic sort
-// of P = 2048 or 4096 words, P / 2 compare-exchanges per step over the 1024 threads.
-template <bool DIRECT>
-__global__ __launch_bounds__(1024) void afi_rpn_pick_wide_kernel(const AfiView lg, int W, int A, int n, int k, const int* __restrict__ hdr,
-                                                                 const u64* __restrict__ cand_all, float* __restrict__ vals,
-                                                                 int* __restrict__ idx, long long ld) {
-    __shared__ int hist[2048];
-    __shared__ int wtot[16];
-    __shared__ int res[2];
-    __shared__ u64 sel[RPN_MAXK_WIDE];
-    __shared__ int nsel;
-    const int img = blockIdx.x, tid = threadIdx.x;
-    int m = n;
-    const u64* cand = nullptr;
-    if (!DIRECT) {
-        m = hdr[(long long)img * RPN_HDR + RPN_BINS];
-        m = m < 0 ? 0 : (m > n ? n : m);
-        cand = cand_all + (long long)img * n;
-    }
-    auto word = [&](int i) -> u64 { return DIRECT ? rpn_word(*rpn_at(lg, img, i, W, A), i) : cand[i]; };
-    int need = k < m ? k : m, group = m, shift = 32 + RPN_IDX_BITS;
-    u64 prefix = 0;
-    const int widths[5] = {11, 11, 10, 11, 11};
-    for (int p = 0; p < 5 && need < group; ++p) {
-        const int bits = widths[p], nb = 1 << bits;
-        shift -= bits;
-        for (int i = tid; i < nb; i += 1024) hist[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < m; i += 1024) {
-            const u64 c = word(i);
-            if ((c >> (shift + bits)) == prefix) atomicAdd(&hist[(int)(c >> shift) & (nb - 1)], 1);
-        }
-        __syncthreads();
-        rpn_find_digit(hist, nb, need, wtot, res);
-        need -= res[1];
-        group = hist[res[0]];
-        prefix = (prefix << bits) | (u64)res[0];
-        __syncthreads();
-    }
-    if (tid == 0) nsel = 0;
-    __syncthreads();
-    for (int i = tid; i < m; i += 1024) {
-        const u64 c = word(i);
-        if ((c >> shift) >= prefix) {
-            const int s = atomicAdd(&nsel, 1);
-            if (s < RPN_MAXK_WIDE) sel[s] = c;             // (never more than min(k, m) <= 4096: the guard keeps a wrong count inside the array)
-        }
-    }
-    __syncthreads();
-    const int ns = nsel < RPN_MAXK_WIDE ? nsel : RPN_MAXK_WIDE;
-    const int P = (k > 2048 || ns > 2048) ? 4096 : 2048;
-    for (int i = ns + tid; i < P; i += 1024) sel[i] = 0;   // below every real word
-    __syncthreads();
-    for (int ksz = 2; ksz <= P; ksz <<= 1)
-        for (int j = ksz >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += 1024) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;        // the t-th pair of this step: bit j clear / set
-                const u64 a = sel[i], b = sel[o];
-                const bool desc = (i & ksz) == 0;
-                if (desc ? a < b : a > b) { sel[i] = b; sel[o] = a; }
-            }
-            __syncthreads();
-        }
-    for (int t = tid; t < k; t += 1024) {
-        const u64 c = sel[t];
-        int i = (int)((~(unsigned)c) & RPN_IDX_MASK);
-        if (c == 0 || i >= n) i = 0;                       // (never: k <= m real words)
-        idx[(long long)img * ld + t] = i;
-        vals[(long long)img * ld + t] = *rpn_at(lg, img, i, W, A);
-    }
-}
-
-long long afi_rpn_topk_wide_ws_floats(int N, int H, int W, int A) { return afi_rpn_topk_ws_floats(N, H, W, A); }
-
-int afi_rpn_topk_wide(afi_view_t logits, int N, int H, int W, int A, int k, float* vals, int* idx, long long ld, float* ws, long long ws_floats,
-                      void* stream) {
-    if (!logits.p || !vals || !idx || N <= 0 || N > 65535 || H <= 0 || W <= 0 || A <= 0 || k <= 0 || ld < k) return AFI_ERR_BAD_ARG;
-    const long long nn = (long long)H * W * A;
-    if (A > RPN_MAX_A || k <= RPN_MAXK || k > RPN_MAXK_WIDE || nn >= RPN_IDX_MASK) return AFI_ERR_UNSUPPORTED;      // k <= 1024: afi_rpn_topk
-    if (k > nn) return AFI_ERR_BAD_ARG;
-    const int n = (int)nn;
-    const AfiView lg{(float*)logits.p, logits.sN, logits.sH, logits.sW};
-    hipStream_t st = (hipStream_t)stream;
-    if (n <= RPN_DIRECT_MAX) {
-        hipLaunchKernelGGL(afi_rpn_pick_wide_kernel<true>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)nullptr, (const u64*)nullptr,
-                           vals, idx, ld);
-        return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
-    }
-    const long long need = afi_rpn_topk_wide_ws_floats(N, H, W, A);
-    if (!ws || ws_floats < need || ((uintptr_t)ws & 7)) return AFI_ERR_WORKSPACE;
-    int* hdr = (int*)ws;
-    u64* cand = (u64*)(hdr + (long long)N * RPN_HDR);
-    hipLaunchKernelGGL(afi_rpn_zero_kernel, dim3((N * RPN_HDR + 255) / 256), dim3(256), 0, st, hdr, N * RPN_HDR);
-    int gx = (n + 256 * 8 - 1) / (256 * 8);
-    if (gx > 512) gx = 512;
-    hipLaunchKernelGGL(afi_rpn_hist_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, hdr);
-    hipLaunchKernelGGL(afi_rpn_filter_kernel, dim3(gx, N), dim3(256), 0, st, lg, W, A, n, k, hdr, cand);
-    hipLaunchKernelGGL(afi_rpn_pick_wide_kernel<false>, dim3(N), dim3(1024), 0, st, lg, W, A, n, k, (const int*)hdr, (const u64*)cand, vals, idx,
-                       ld);
-    return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
-}
-
-// ------------------------------------------------------------------------------------------------ NMS
-// The bit matrix in the workspace: per image k rows of nw = ceil(k / 64) words, mask[i][w] bit j as in afi_nms_kernel.  Build: one block per
-// 64 x 64 tile (column word w, row tile rt <= w) of the upper triangle, blockIdx.x = w (w + 1) / 2 + rt; a wave takes sixteen rows, a lane is a
-// column, a wave's __ballot is the word.  The overlap test is afi_nms_kernel's expression, restated (that kernel's code object stays as it is).
+// afi_rpn_nms_wide, lists of up to RPN_MAXK_WIDE boxes.  The bit matrix in the workspace: per image k rows of nw = ceil(k / 64) words,
+// mask[i][w] bit j as in afi_nms_kernel.  Build: one block per 64 x 64 tile (column word w, row tile rt <= w) of the upper triangle,
+// blockIdx.x = w (w + 1) / 2 + rt; a wave takes sixteen rows, a lane is a column, a wave's __ballot is the word.
 __global__ __launch_bounds__(256) void afi_rpn_nms_build_kernel(const float* __restrict__ boxes, const int* __restrict__ valid, int k, long long ld,
                                                                 float thresh, u64* __restrict__ mask_all) {
-#pragma clang fp contract(off)                          // the overlap test is the stated fp32 expression, operation by operation
     const int img = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nw = (k + 63) >> 6, t = blockIdx.x;
     int w = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
@@ -482,7 +308,6 @@ __global__ __launch_bounds__(256) void afi_rpn_nms_build_kernel(const float* __r
         c = make_float4(q[0], q[1], q[2], q[3]);
         cok = valid[(long long)img * ld + j] != 0;
     }
-    const float carea = (c.z - c.x) * (c.w - c.y);
     u64* mask = mask_all + (long long)img * k * nw;
     const int i0 = 64 * rt + 16 * wave;
     for (int s = 0; s < 16; ++s) {
@@ -490,16 +315,14 @@ __global__ __launch_bounds__(256) void afi_rpn_nms_build_kernel(const float* __r
         if (i >= k) break;
         const float* q = boxes + 4 * ((long long)img * ld + i);
         const float4 r = make_float4(q[0], q[1], q[2], q[3]);
-        const float iw = fmaxf(fminf(r.z, c.z) - fmaxf(r.x, c.x), 0.f), ih = fmaxf(fminf(r.w, c.w) - fmaxf(r.y, c.y), 0.f);
-        const float inter = iw * ih, rarea = (r.z - r.x) * (r.w - r.y);
-        const bool hit = cok && j > i && (inter / (rarea + carea - inter) > thresh);
+        const bool hit = cok && j > i && rpn_overlaps(r, c, thresh);
         const u64 word = __ballot(hit);
         if (lane == 0) mask[(long long)i * nw + w] = word;
     }
 }
 
-// One wave per image; lane w holds word w of the boxes suppressed so far.  Per chunk of 64 rows: the diagonal word resolved in registers as in
-// afi_nms_kernel, then the kept rows' words OR-ed in -- sixteen rows' loads issued together (a row is nw <= 64 words: one coalesced read), rows
+// One wave per image; lane w holds word w of the boxes suppressed so far.  Per chunk of 64 rows: the diagonal word resolved in registers
+// (rpn_resolve_diag), then the kept rows' words OR-ed in -- sixteen rows' loads issued together (a row is nw <= 64 words: one coalesced read), rows
 // of a group that were not kept are read and masked out, a group without a kept row is skipped.  Only words the build wrote are read: column
 // words w > c of rows 64 c .. min(64 c + 63, k - 1), and the diagonal words.
 __global__ __launch_bounds__(64) void afi_rpn_nms_sweep_kernel(const u64* __restrict__ mask_all, const int* __restrict__ valid, int k, long long ld,
@@ -512,15 +335,7 @@ __global__ __launch_bounds__(64) void afi_rpn_nms_sweep_kernel(const u64* __rest
         const int row = 64 * c + lane;
         const u64 diag = (row < k) ? mask[(long long)row * nw + c] : 0ull;
         const u64 V = __ballot(row < k && valid[(long long)img * ld + (row < k ? row : 0)] != 0);
-        u64 R = rpn_readlane64(remv, c) | ~V;           // an invalid box is neither kept nor suppresses anything
-        u64 K = 0;
-#pragma unroll
-        for (int b = 0; b < 64; ++b) {
-            if (!((R >> b) & 1ull)) {
-                K |= 1ull << b;
-                R |= rpn_readlane64(diag, b);
-            }
-        }
+        const u64 K = rpn_resolve_diag(rpn_readlane64(remv, c) | ~V, diag);      // an invalid box is neither kept nor suppresses anything
         if (row < k) keep[(long long)img * ld + row] = (int)((K >> lane) & 1ull);
         const bool mine = lane > c && lane < nw;
         u64 acc = 0;
@@ -561,13 +376,15 @@ int afi_rpn_nms_wide(const float* boxes, const int* valid, int N, int k, long lo
 }
 
 // ------------------------------------------------------------------------------------------------ merge
-// afi_rpn_merge_kernel with levels of up to RPN_MAXK_WIDE entries: the threads loop over a level's entries in chunks of 1024 (one block scan per
-// chunk), positions are 16 bits (RPN_WIDE_TOTAL < 65536).  The same order: logit descending, then level, then rank.
-__global__ __launch_bounds__(1024) void afi_rpn_merge_wide_kernel(const float* __restrict__ boxes, const float* __restrict__ vals,
-                                                                  const int* __restrict__ keep, const RpnLevels lv, int post_k,
-                                                                  float* __restrict__ ob, float* __restrict__ ol, int* __restrict__ counts) {
-    __shared__ unsigned ckey[RPN_WIDE_TOTAL];
-    __shared__ unsigned short cpos[RPN_WIDE_TOTAL];
+// boxes [N][Ktot][4], vals / keep [N][Ktot]: the levels side by side, level l in columns [off[l], off[l + 1]), each sorted by afi_rpn_topk.
+// Ktot <= TOTAL < 65536 (positions are 16 bits).  The threads take a level's entries in chunks of 1024, one block scan per chunk: one chunk
+// for a level of <= RPN_MAXK entries.
+template <int TOTAL>
+__global__ __launch_bounds__(1024) void afi_rpn_merge_kernel(const float* __restrict__ boxes, const float* __restrict__ vals,
+                                                             const int* __restrict__ keep, const RpnLevels lv, int post_k,
+                                                             float* __restrict__ ob, float* __restrict__ ol, int* __restrict__ counts) {
+    __shared__ unsigned ckey[TOTAL];
+    __shared__ unsigned short cpos[TOTAL];
     __shared__ int cnt[RPN_MAX_LEVELS];
     __shared__ int wtot[16];
     const int img = blockIdx.x, tid = threadIdx.x, Ktot = lv.off[lv.L];
@@ -625,8 +442,10 @@ __global__ __launch_bounds__(1024) void afi_rpn_merge_wide_kernel(const float* _
     }
 }
 
-int afi_rpn_merge_wide(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
-                       float* out_logits, int* counts, void* stream) {
+// Levels of at most LEVEL_MAX entries, TOTAL over all levels (RPN_MAX_LEVELS levels of RPN_MAXK never exceed the narrow TOTAL).
+template <int LEVEL_MAX, int TOTAL>
+static int rpn_merge_launch(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k,
+                            float* out_boxes, float* out_logits, int* counts, void* stream) {
     if (!boxes || !vals || !keep || !level_off || !out_boxes || !out_logits || !counts || N <= 0 || N > 65535 || L <= 0 || post_k <= 0)
         return AFI_ERR_BAD_ARG;
     if (L > RPN_MAX_LEVELS) return AFI_ERR_UNSUPPORTED;
@@ -637,11 +456,21 @@ int afi_rpn_merge_wide(const float* boxes, const float* vals, const int* keep, i
     for (int l = 0; l < L; ++l) {
         const int kl = level_off[l + 1] - level_off[l];
         if (kl < 0) return AFI_ERR_BAD_ARG;
-        if (kl > RPN_MAXK_WIDE) return AFI_ERR_UNSUPPORTED;
+        if (kl > LEVEL_MAX) return AFI_ERR_UNSUPPORTED;
     }
     if (level_off[L] <= 0) return AFI_ERR_BAD_ARG;
-    if (level_off[L] > RPN_WIDE_TOTAL) return AFI_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(afi_rpn_merge_wide_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes,
+    if (level_off[L] > TOTAL) return AFI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(afi_rpn_merge_kernel<TOTAL>, dim3(N), dim3(1024), 0, (hipStream_t)stream, boxes, vals, keep, lv, post_k, out_boxes,
                        out_logits, counts);
     return hipGetLastError() == hipSuccess ? AFI_OK : AFI_ERR_LAUNCH;
+}
+
+int afi_rpn_merge(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                  float* out_logits, int* counts, void* stream) {
+    return rpn_merge_launch<RPN_MAXK, RPN_MAX_LEVELS * RPN_MAXK>(boxes, vals, keep, N, L, level_off, post_k, out_boxes, out_logits, counts, stream);
+}
+
+int afi_rpn_merge_wide(const float* boxes, const float* vals, const int* keep, int N, int L, const int* level_off, int post_k, float* out_boxes,
+                       float* out_logits, int* counts, void* stream) {
+    return rpn_merge_launch<RPN_MAXK_WIDE, RPN_WIDE_TOTAL>(boxes, vals, keep, N, L, level_off, post_k, out_boxes, out_logits, counts, stream);
 }

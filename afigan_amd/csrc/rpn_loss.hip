@@ -182,27 +182,13 @@ __global__ __launch_bounds__(1024) void afi_rpn_sample_kernel(const signed char*
     __syncthreads();
     const int npos = tp < P ? tp : P, nneg = tn < B - npos ? tn : B - npos;
     const int m = cls ? tp : tn, want = cls ? npos : nneg, base = cls ? 0 : npos;
-    int need = want, group = m, shift = 32 + RPNL_IDX_BITS;
-    u64 prefix = 0;
-    const int widths[5] = {11, 11, 10, 11, 11};
-    for (int p = 0; p < 5 && need > 0 && need < group; ++p) {
-        const int bits = widths[p], nb = 1 << bits;
-        shift -= bits;
-        for (int i = tid; i < nb; i += 1024) hist[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < R; i += 1024) {
-            if (lab[i] != cls) continue;
-            const u64 c = rpn_sample_word(key[i], i);
-            if ((c >> (shift + bits)) == prefix) atomicAdd(&hist[(int)(c >> shift) & (nb - 1)], 1);
-        }
-        __syncthreads();
-        rpn_find_digit(hist, nb, need, wtot, res);
-        need -= res[1];
-        group = hist[res[0]];
-        prefix = (prefix << bits) | (u64)res[0];
-        __syncthreads();
-    }
-    // the members whose word, cut at `shift`, is at or above the prefix: exactly `want` of them (all of them when want == m, none when 0)
+    auto word = [&](int i, u64* c) {                    // the members of this block's class take part
+        if (lab[i] != cls) return false;
+        *c = rpn_sample_word(key[i], i);
+        return true;
+    };
+    const RpnCut cut = rpn_radix_select(word, R, m, want, RPNL_IDX_BITS, hist, wtot, res);
+    // the members whose word, cut at cut.shift, is at or above the prefix: exactly `want` of them (all of them when want == m, none when 0)
     signed char* out = labels_out + (long long)img * R;
     int* list = sidx + (long long)img * B;
     int run = 0;
@@ -210,7 +196,7 @@ __global__ __launch_bounds__(1024) void afi_rpn_sample_kernel(const signed char*
         const int i = c0 + tid;
         const int l = i < R ? (int)lab[i] : -2;
         const bool member = l == cls;
-        const bool s = member && want > 0 && (rpn_sample_word(key[i], i) >> shift) >= prefix;
+        const bool s = member && want > 0 && (rpn_sample_word(key[i], i) >> cut.shift) >= cut.prefix;
         int tot;
         const int inc = rpn_block_scan(s ? 1 : 0, wtot, &tot);
         if (s) {

@@ -1259,14 +1259,12 @@ def _rpn_rows(t, k, inner=()):
     return t.stride(0) // per
 
 
-def rpn_topk(head, A, k, vals=None, idx=None):
-    """The k highest of channels 0..A-1 of the pixel-major head output [N, Cpad, H, W], per image: (vals [N, k] fp32, idx [N, k] int32), sorted
-    by (logit descending, anchor index (y W + x) A + a ascending); NaN below every number (afi_rpn_topk).  vals / idx may be column slices of wider
-    [N, K] buffers (the levels of an image side by side)."""
+def _rpn_topk(name, k_lo, k_hi, head, A, k, vals, idx):
+    """The body of rpn_topk / rpn_topk_wide: k_lo <= k <= k_hi, the entry points afi_<name> and afi_<name>_ws_floats."""
     _check_cuda(head)
     N, Cp, H, W = head.shape
-    if not 0 < A <= min(Cp, RPN_MAX_ANCHORS) or not 0 < k <= min(RPN_MAX_TOPK, H * W * A):
-        raise _lib.AfiError(f"rpn_topk: A {A} (1..{min(Cp, RPN_MAX_ANCHORS)}), k {k} (1..{min(RPN_MAX_TOPK, H * W * A)}) for a head of shape {tuple(head.shape)}")
+    if not 0 < A <= min(Cp, RPN_MAX_ANCHORS) or not k_lo <= k <= min(k_hi, H * W * A):
+        raise _lib.AfiError(f"{name}: A {A} (1..{min(Cp, RPN_MAX_ANCHORS)}), k {k} ({k_lo}..{min(k_hi, H * W * A)}) for a head of shape {tuple(head.shape)}")
     if vals is None:
         vals = torch.empty((N, k), device=head.device, dtype=torch.float32)
         idx = torch.empty((N, k), device=head.device, dtype=torch.int32)
@@ -1274,13 +1272,20 @@ def rpn_topk(head, A, k, vals=None, idx=None):
     _check_i32(idx)
     ld = _rpn_rows(vals, k)
     if vals.shape[0] != N or idx.shape[0] != N or _rpn_rows(idx, k) != ld:
-        raise _lib.AfiError("rpn_topk: vals and idx must be [N, >= k] with one row stride")
-    n = _lib.load().afi_rpn_topk_ws_floats(N, H, W, A)
+        raise _lib.AfiError(f"{name}: vals and idx must be [N, >= k] with one row stride")
+    n = getattr(_lib.load(), f"afi_{name}_ws_floats")(N, H, W, A)
     if n < 0:
-        raise _lib.AfiError(f"rpn_topk: unsupported map {H}x{W}x{A}")
+        raise _lib.AfiError(f"{name}: unsupported map {H}x{W}x{A}")
     ws = new_workspace(n, head.device) if n else None
-    call("afi_rpn_topk", view_of(head), N, H, W, A, k, _p(vals), _p(idx), ld, _p(ws), n, stream_ptr())
+    call(f"afi_{name}", view_of(head), N, H, W, A, k, _p(vals), _p(idx), ld, _p(ws), n, stream_ptr())
     return vals, idx
+
+
+def rpn_topk(head, A, k, vals=None, idx=None):
+    """The k highest of channels 0..A-1 of the pixel-major head output [N, Cpad, H, W], per image: (vals [N, k] fp32, idx [N, k] int32), sorted
+    by (logit descending, anchor index (y W + x) A + a ascending); NaN below every number (afi_rpn_topk).  vals / idx may be column slices of wider
+    [N, K] buffers (the levels of an image side by side)."""
+    return _rpn_topk("rpn_topk", 1, RPN_MAX_TOPK, head, A, k, vals, idx)
 
 
 def rpn_decode(head, c0, A, cell_anchors, stride, idx, k, image_hw, weights=(1.0, 1.0, 1.0, 1.0), scale_clamp=4.135166556742356, min_size=0.0,
@@ -1309,43 +1314,61 @@ def rpn_decode(head, c0, A, cell_anchors, stride, idx, k, image_hw, weights=(1.0
     return boxes, valid
 
 
-def rpn_nms(boxes, valid, thresh, keep=None):
-    """Greedy NMS of the lists boxes [N, k, 4] (k <= 1024, in score order), valid [N, k] int32: keep [N, k] int32 (afi_rpn_nms)."""
+def _rpn_nms(name, k_max, ws_query, boxes, valid, thresh, keep):
+    """The body of rpn_nms / rpn_nms_wide: lists of at most k_max boxes; ws_query (N, k) -> floats of workspace, None for the form without one."""
     _check_cuda(boxes)
     _check_i32(valid)
     N, k = valid.shape
     if keep is None:
         keep = torch.empty((N, k), device=boxes.device, dtype=torch.int32)
     _check_i32(keep)
-    if k > RPN_MAX_TOPK:
-        raise _lib.AfiError(f"rpn_nms: lists of at most {RPN_MAX_TOPK} boxes, got {k}")
+    if k > k_max:
+        raise _lib.AfiError(f"{name}: lists of at most {k_max} boxes, got {k}")
     if k == 0:
         return keep
     ld = _rpn_rows(valid, k)
     if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(keep, k) != ld or not (boxes.shape[0] == keep.shape[0] == N):
-        raise _lib.AfiError("rpn_nms: boxes, valid and keep must be lists of one row stride")
-    call("afi_rpn_nms", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), stream_ptr())
+        raise _lib.AfiError(f"{name}: boxes, valid and keep must be lists of one row stride")
+    if ws_query is None:
+        call(f"afi_{name}", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), stream_ptr())
+        return keep
+    n = ws_query(N, k)
+    ws = new_workspace(n, boxes.device)                      # held until after the launch
+    call(f"afi_{name}", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), _p(ws), n, stream_ptr())
     return keep
 
 
-def rpn_merge(boxes, vals, keep, level_off, post_k):
-    """The kept entries of every level of an image in (logit descending, level, rank) order, the first post_k: boxes [N, K, 4], vals / keep
-    [N, K] dense with level l in columns [level_off[l], level_off[l + 1]); returns (boxes [N, post_k, 4], logits [N, post_k], counts [N] int32),
-    rows past counts zero (afi_rpn_merge)."""
+def rpn_nms(boxes, valid, thresh, keep=None):
+    """Greedy NMS of the lists boxes [N, k, 4] (k <= 1024, in score order), valid [N, k] int32: keep [N, k] int32 (afi_rpn_nms)."""
+    return _rpn_nms("rpn_nms", RPN_MAX_TOPK, None, boxes, valid, thresh, keep)
+
+
+def _rpn_merge(name, level_max, total_max, boxes, vals, keep, level_off, post_k):
+    """The body of rpn_merge / rpn_merge_wide.  level_max None: the level and total bounds are left to afi_rpn_merge (RPN_MAX_TOPK a level)."""
     _check_cuda(boxes, vals)
     _check_i32(keep)
     N, K = vals.shape
     L = len(level_off) - 1
     if not (boxes.is_contiguous() and vals.is_contiguous() and keep.is_contiguous()) or tuple(boxes.shape) != (N, K, 4) or tuple(keep.shape) != (N, K) \
             or level_off[0] != 0 or level_off[-1] != K or not 0 < L <= RPN_MAX_LEVELS or post_k <= 0:
-        raise _lib.AfiError(f"rpn_merge: dense boxes [N, K, 4], vals / keep [N, K] and 1..{RPN_MAX_LEVELS} levels ending at K expected, got "
+        raise _lib.AfiError(f"{name}: dense boxes [N, K, 4], vals / keep [N, K] and 1..{RPN_MAX_LEVELS} levels ending at K expected, got "
                             f"{tuple(boxes.shape)}, {tuple(vals.shape)}, {tuple(keep.shape)}, offsets {list(level_off)}")
+    if level_max is not None and (K > total_max or any(level_off[l + 1] - level_off[l] > level_max for l in range(L))):
+        raise _lib.AfiError(f"{name}: levels of at most {level_max} entries, {total_max} in all; got offsets {list(level_off)}")
     ob = torch.empty((N, post_k, 4), device=boxes.device, dtype=torch.float32)
     ol = torch.empty((N, post_k), device=boxes.device, dtype=torch.float32)
     counts = torch.empty((N,), device=boxes.device, dtype=torch.int32)
     off = (C.c_int * (L + 1))(*[int(o) for o in level_off])
-    call("afi_rpn_merge", _p(boxes), _p(vals), _p(keep), N, L, off, int(post_k), _p(ob), _p(ol), _p(counts), stream_ptr())
+    call(f"afi_{name}", _p(boxes), _p(vals), _p(keep), N, L, off, int(post_k), _p(ob), _p(ol), _p(counts), stream_ptr())
     return ob, ol, counts
+
+
+def rpn_merge(boxes, vals, keep, level_off, post_k):
+    """The kept entries of every level of an image in (logit descending, level, rank) order, the first post_k: boxes [N, K, 4], vals / keep
+    [N, K] dense with level l in columns [level_off[l], level_off[l + 1]); returns (boxes [N, post_k, 4], logits [N, post_k], counts [N] int32),
+    rows past counts zero (afi_rpn_merge)."""
+    # no bounds here: a level above RPN_MAX_TOPK has always been refused by afi_rpn_merge itself, with the library's status message
+    return _rpn_merge("rpn_merge", None, None, boxes, vals, keep, level_off, post_k)
 
 
 # The wide forms: per-level lists of 1025 .. 4096 (PRE_NMS_TOPK_TRAIN of the reference's base config is 2000).  RPN.select uses them for the
@@ -1357,67 +1380,18 @@ RPN_MAX_MERGE_WIDE = 5 * RPN_MAX_TOPK_WIDE  # entries of all levels of an image 
 def rpn_topk_wide(head, A, k, vals=None, idx=None):
     """rpn_topk for RPN_MAX_TOPK < k <= RPN_MAX_TOPK_WIDE: the same order, tie rule, NaN rule and output layout (afi_rpn_topk_wide).  A k of
     at most RPN_MAX_TOPK is rpn_topk's and is refused here."""
-    _check_cuda(head)
-    N, Cp, H, W = head.shape
-    if not 0 < A <= min(Cp, RPN_MAX_ANCHORS) or not RPN_MAX_TOPK < k <= min(RPN_MAX_TOPK_WIDE, H * W * A):
-        raise _lib.AfiError(f"rpn_topk_wide: A {A} (1..{min(Cp, RPN_MAX_ANCHORS)}), k {k} ({RPN_MAX_TOPK + 1}..{min(RPN_MAX_TOPK_WIDE, H * W * A)}) "
-                            f"for a head of shape {tuple(head.shape)}")
-    if vals is None:
-        vals = torch.empty((N, k), device=head.device, dtype=torch.float32)
-        idx = torch.empty((N, k), device=head.device, dtype=torch.int32)
-    _check_cuda(vals)
-    _check_i32(idx)
-    ld = _rpn_rows(vals, k)
-    if vals.shape[0] != N or idx.shape[0] != N or _rpn_rows(idx, k) != ld:
-        raise _lib.AfiError("rpn_topk_wide: vals and idx must be [N, >= k] with one row stride")
-    n = _lib.load().afi_rpn_topk_wide_ws_floats(N, H, W, A)
-    if n < 0:
-        raise _lib.AfiError(f"rpn_topk_wide: unsupported map {H}x{W}x{A}")
-    ws = new_workspace(n, head.device) if n else None
-    call("afi_rpn_topk_wide", view_of(head), N, H, W, A, k, _p(vals), _p(idx), ld, _p(ws), n, stream_ptr())
-    return vals, idx
+    return _rpn_topk("rpn_topk_wide", RPN_MAX_TOPK + 1, RPN_MAX_TOPK_WIDE, head, A, k, vals, idx)
 
 
 def rpn_nms_wide(boxes, valid, thresh, keep=None):
     """rpn_nms for lists of up to RPN_MAX_TOPK_WIDE boxes, the suppression bit matrix in a workspace (afi_rpn_nms_wide).  For k <= RPN_MAX_TOPK
     the keep set is rpn_nms's."""
-    _check_cuda(boxes)
-    _check_i32(valid)
-    N, k = valid.shape
-    if keep is None:
-        keep = torch.empty((N, k), device=boxes.device, dtype=torch.int32)
-    _check_i32(keep)
-    if k > RPN_MAX_TOPK_WIDE:
-        raise _lib.AfiError(f"rpn_nms_wide: lists of at most {RPN_MAX_TOPK_WIDE} boxes, got {k}")
-    if k == 0:
-        return keep
-    ld = _rpn_rows(valid, k)
-    if _rpn_rows(boxes, k, (4,)) != ld or _rpn_rows(keep, k) != ld or not (boxes.shape[0] == keep.shape[0] == N):
-        raise _lib.AfiError("rpn_nms_wide: boxes, valid and keep must be lists of one row stride")
-    n = _lib.load().afi_rpn_nms_wide_ws_floats(N, k)
-    ws = new_workspace(n, boxes.device)
-    call("afi_rpn_nms_wide", _p(boxes), _p(valid), N, k, ld, float(thresh), _p(keep), _p(ws), n, stream_ptr())
-    return keep
+    return _rpn_nms("rpn_nms_wide", RPN_MAX_TOPK_WIDE, lambda N, k: _lib.load().afi_rpn_nms_wide_ws_floats(N, k), boxes, valid, thresh, keep)
 
 
 def rpn_merge_wide(boxes, vals, keep, level_off, post_k):
     """rpn_merge with levels of up to RPN_MAX_TOPK_WIDE entries, at most RPN_MAX_MERGE_WIDE over all levels (afi_rpn_merge_wide)."""
-    _check_cuda(boxes, vals)
-    _check_i32(keep)
-    N, K = vals.shape
-    L = len(level_off) - 1
-    if not (boxes.is_contiguous() and vals.is_contiguous() and keep.is_contiguous()) or tuple(boxes.shape) != (N, K, 4) or tuple(keep.shape) != (N, K) \
-            or level_off[0] != 0 or level_off[-1] != K or not 0 < L <= RPN_MAX_LEVELS or post_k <= 0:
-        raise _lib.AfiError(f"rpn_merge_wide: dense boxes [N, K, 4], vals / keep [N, K] and 1..{RPN_MAX_LEVELS} levels ending at K expected, got "
-                            f"{tuple(boxes.shape)}, {tuple(vals.shape)}, {tuple(keep.shape)}, offsets {list(level_off)}")
-    if K > RPN_MAX_MERGE_WIDE or any(level_off[l + 1] - level_off[l] > RPN_MAX_TOPK_WIDE for l in range(L)):
-        raise _lib.AfiError(f"rpn_merge_wide: levels of at most {RPN_MAX_TOPK_WIDE} entries, {RPN_MAX_MERGE_WIDE} in all; got offsets {list(level_off)}")
-    ob = torch.empty((N, post_k, 4), device=boxes.device, dtype=torch.float32)
-    ol = torch.empty((N, post_k), device=boxes.device, dtype=torch.float32)
-    counts = torch.empty((N,), device=boxes.device, dtype=torch.int32)
-    off = (C.c_int * (L + 1))(*[int(o) for o in level_off])
-    call("afi_rpn_merge_wide", _p(boxes), _p(vals), _p(keep), N, L, off, int(post_k), _p(ob), _p(ol), _p(counts), stream_ptr())
-    return ob, ol, counts
+    return _rpn_merge("rpn_merge_wide", RPN_MAX_TOPK_WIDE, RPN_MAX_MERGE_WIDE, boxes, vals, keep, level_off, post_k)
 
 
 # ------------------------------------------------------------------------------------------------ RPN training (rpn.py: RPN.losses)

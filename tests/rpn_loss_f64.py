@@ -221,6 +221,9 @@ def sample_cases():
     c["duplicate_keys"] = (np.stack([lab(60, 700), lab(50, 50)]), rng.integers(0, 4, size=(2, R)).astype(np.uint32), 32, 0.25)
     c["constant_keys"] = (np.stack([lab(60, 700), lab(20, 892)]), np.full((2, R), 0xDEADBEEF, np.uint32), 16, 0.5)
     c["extreme_keys"] = (np.stack([lab(100, 700), lab(100, 700)]), np.where(rng.random((2, R)) < 0.5, 0, 0xFFFFFFFF).astype(np.uint32), 64, 0.5)
+    # nothing wanted of a class that has members (the cases above want 0 only of an empty class): the select must take none of them
+    c["no_positive_quota"] = (np.stack([lab(40, 500), lab(9, 3)]), keys(), 8, 0.0)
+    c["positives_fill_the_batch"] = (np.stack([lab(40, 500), lab(8, 300)]), keys(), 8, 1.0)
     return c
 
 

@@ -69,6 +69,8 @@ TOPK_CASES = [  # kind, N, A, H, W, k, Cpad
     ("rand", 1, 3, 1, 1, 3, 16), ("rand", 2, 1, 1, 1, 1, 8), ("rand", 2, 3, 7, 9, 189, 16),       # H W A < PRE_NMS_TOPK: all of them, sorted
     ("rand", 2, 1, 50, 84, 1000, 8), ("ties", 2, 1, 200, 336, 1024, 8), ("zeros", 2, 3, 25, 42, 700, 16), ("equal", 2, 3, 50, 84, 1000, 16),
     ("rand", 2, 16, 40, 40, 1000, 80),
+    ("rand", 2, 4, 16, 16, 1024, 8), ("nan", 2, 4, 16, 16, 1023, 8),       # k = n = 1024: the sort is full, no padding word; and one short of it
+    ("ties", 2, 1, 200, 336, 1, 8),                                        # k = 1 through the filter
 ]
 
 
@@ -291,6 +293,37 @@ def test_merge_ties_across_levels_and_the_cut(amd):
             assert int(counts[n]) == c
             assert np.array_equal(ol[n, :c].cpu().numpy(), vals[n].numpy()[order]) and np.array_equal(ob[n, :c].cpu().numpy(), boxes[n].numpy()[order])
             assert not ob[n, c:].any() and not ol[n, c:].any()
+
+
+def test_merge_at_its_bound_and_what_it_refuses(amd):
+    """afi_rpn_merge with all it holds: eight levels of 1024, ties across levels and at the cut, one level with nothing kept."""
+    g = torch.Generator().manual_seed(6)
+    N, off = 2, [1024 * l for l in range(9)]
+    K = off[-1]
+    vals = torch.empty((N, K))
+    for l in range(8):
+        v = torch.round(torch.randn((N, 1024), generator=g) * 4) / 4
+        vals[:, off[l]:off[l + 1]] = torch.sort(v, dim=1, descending=True).values
+    keep = (torch.rand((N, K), generator=g) < 0.6).to(torch.int32)
+    keep[:, off[5]:off[6]] = 0
+    boxes = torch.rand((N, K, 4), generator=g)
+    ob, ol, counts = amd.ops.rpn_merge(boxes.cuda(), vals.cuda(), keep.cuda(), off, 1000)
+    torch.cuda.synchronize()
+    for n in range(N):
+        order = R.merge(vals[n].numpy(), keep[n].numpy() != 0, off, 1000)
+        assert int(counts[n]) == len(order) == 1000
+        assert np.array_equal(ol[n].cpu().numpy(), vals[n].numpy()[order]) and np.array_equal(ob[n].cpu().numpy(), boxes[n].numpy()[order])
+        cut = np.sort(vals[n].numpy()[keep[n].numpy() != 0])[::-1]
+        assert cut[999] == cut[1000], "no tie at the cut"
+
+    def lists(K):
+        return torch.zeros((1, K, 4), device="cuda"), torch.zeros((1, K), device="cuda"), torch.ones((1, K), dtype=torch.int32, device="cuda")
+    with pytest.raises(amd.AfiError):
+        amd.ops.rpn_merge(*lists(9), list(range(10)), 5)                # a ninth level
+    with pytest.raises(amd.AfiError):
+        amd.ops.rpn_merge(*lists(1025), [0, 1025], 5)                   # a level of 1025 is rpn_merge_wide's
+    _, _, c = amd.ops.rpn_merge_wide(*lists(1025), [0, 1025], 5)
+    assert c.tolist() == [5]
 
 
 # ------------------------------------------------------------------------------------------------ 5. the head

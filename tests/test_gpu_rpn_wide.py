@@ -63,6 +63,7 @@ TOPK_WIDE_CASES = [  # kind, N, A, H, W, k, Cpad
     ("rand", 2, 3, 37, 37, 4096, 16), ("ties", 2, 3, 37, 37, 4096, 16),                       # n = 4107: almost the whole map
     ("rand", 2, 4, 32, 32, 4096, 16), ("nan", 2, 4, 32, 32, 4096, 16), ("equal", 2, 4, 32, 32, 4096, 16),     # k = n: everything, sorted
     ("zeros", 2, 3, 40, 40, 2049, 16), ("equal", 2, 3, 40, 40, 2048, 16),
+    ("rand", 2, 2, 32, 32, 2048, 8),                                                          # k = n = 2048: the 2048-sort without padding
     # through the grid histogram and the filter (n = 23 040)
     ("rand", 2, 3, 80, 96, 2000, 16), ("rand", 2, 3, 80, 96, 4096, 16), ("ties", 2, 3, 80, 96, 2000, 16), ("ties", 2, 3, 80, 96, 4096, 16),
     ("equal", 2, 3, 80, 96, 4096, 16), ("zeros", 2, 3, 80, 96, 2000, 16), ("nan", 2, 3, 80, 96, 4096, 16),
